@@ -22,7 +22,7 @@ indexes are not offline); proofs are minted by the repo's CPU orac
 onto helper streams of its own and joins them before the verdict kernel, and every kernel but the state hash raises its wave priority: profiles/r06_dev_fork.md).  Not in the job: bin_prot / bincode parsing of the containers and the
 consensus pre-checks (host side of the boundary, done by the caller before the timed region).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--jobs B] [--pipeline L]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--jobs B] [--pipeline L] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Multi-GPU: proof-level sharding (SURVEY.md 8e variant 1): every rank verifies its own proofs against its replica of the
@@ -30,9 +30,10 @@ SRS tables; the ranks' verdict words are all-gathered over RCCL inside the timed
 `python bench.py --gpus N` WITHOUT a torch.distributed launch (WORLD_SIZE unset) starts its N ranks itself (`launch_ranks`): one child
 process per GPU with RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* set, rank 0's JSON line passed through.  On a box with fewer than N GPUs the
 ranks share GPU 0 and rendezvous over gloo (`"shared_gpu": true`, `"gpus_physical"` in the line): the N > 1 code path is exercised, the
-figure is NOT a scaling number.  At N > 1 rank 0 also times the PRODUCT's own multi-device path -- ONE process, $MINA_VERIFY_DEVICES = the N
+figure is NOT a scaling number.  At N > 1 with `--full` rank 0 also times the PRODUCT's own multi-device path -- ONE process, $MINA_VERIFY_DEVICES = the N
 GPUs, `mina_verify_state_batch` on serialized proofs (`boundary_bytes_to_bools.all_devices`) -- while the other ranks wait.
 
+A plain run sets up, warms up, times the K steps, writes their last outputs (`--dump-outputs`) and prints the line.  Everything else below runs with `--full` only.
 Secondary legs that need a process of their own run in one (rank 0, before the main process touches the GPU): the bytes -> bools boundary, BASELINE C4, `one_proof_per_call` (the
 reference's call shape) and BASELINE C2 (`c2_accumulator_only`, incl. ONE check alone on the chip).  In the main process the lone-call latencies and the isolated launches that time the
 dominant kernel come BEFORE anything creates more streams than the process has hardware queues (such a process stays slower for life).
@@ -225,9 +226,17 @@ def le32(x: int) -> np.ndarray:
     return np.frombuffer(int(x).to_bytes(32, "little"), np.uint8)
 
 
-def fresh_randomiser() -> np.ndarray:
-    r = np.frombuffer(os.urandom(32), np.uint8).copy(); r[31] &= 0x3F
+def randomisers(rng, n: int) -> np.ndarray:
+    """n canonical scalars (< 2^254, 32-byte LE rows) from `rng`"""
+    r = rng.integers(0, 256, size=(n, 32), dtype=np.uint8); r[:, 31] &= 0x3F
     return r
+
+
+def dump_outputs(path: str, arrays: dict) -> None:
+    """--dump-outputs: every array as path/<name>.npy in float32 (verdict and flag words are small integers: exact)"""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.asarray(a).astype(np.float32))
 
 
 def make_chains(ctx, n_chains: int, seed: int):
@@ -321,13 +330,15 @@ def build_full_job(ctx, m, B: int, seed: int, distinct_chains: int = 0):
     nd = min(B, distinct_chains or B)
     recs, nf, hashes = make_chains(ctx, nd, seed)
     ci = np.arange(B) % nd
-    # folding randomisers of the kernel-level job are the CALLER's to supply (include/mina_verify.h): drawn from the OS CSPRNG, as the
-    # reference-shaped boundary does per job (api_verify.hip draw_randomisers); their values do not change the work
-    rho = np.frombuffer(os.urandom(B * 32), np.uint8).reshape(B, 32).copy(); rho[:, 31] &= 0x3F
+    # folding randomisers of the kernel-level job are the CALLER's to supply (include/mina_verify.h); the reference-shaped boundary draws them from the
+    # OS CSPRNG per job (api_verify.hip draw_randomisers).  Here they come from `seed`, so that the same arguments give the same inputs run after run
+    # (--dump-outputs); their values do not change the work
+    rr = np.random.Generator(np.random.PCG64([seed, 1]))
+    rand2, rho = randomisers(rr, 2), randomisers(rr, B)
     same = nd == B
     arrays = dict(state_records=recs.reshape(-1) if same else recs[ci].reshape(-1), state_nfields=nf.reshape(-1) if same else nf[ci].reshape(-1),
                   expected_hashes=hashes.reshape(-1) if same else hashes[ci].reshape(-1),
-                  rand_base=fresh_randomiser(), sg_rand_base=fresh_randomiser(), acc_prechallenges=tile(None, "acc_prechallenges"), acc_sg=tile(None, "acc_sg"), acc_rho=rho.reshape(-1),
+                  rand_base=rand2[0].copy(), sg_rand_base=rand2[1].copy(), acc_prechallenges=tile(None, "acc_prechallenges"), acc_sg=tile(None, "acc_sg"), acc_rho=rho.reshape(-1),
                   **{name: tile("opening", name) for name in ("lr", "delta", "sg", "z1", "z2")})
     scal = dict(with_states=1, with_ipa=1, with_accumulator=1, log2_domain=LOG2_DOMAIN, npub=NPUB, k=WRAP_K, n_evalpoints=NPTS, n_comms=NCOMMS + 2, acc_k=ACC_K, kimchi=kp)
     return m.MinaContext.make_state_jobs(B, arrays, **scal), kp, (recs[0].copy(), nf[0].copy(), hashes[0].copy()), {"chains": int(nd), "wrap_proofs": int(min(n, B))}
@@ -915,11 +926,22 @@ def main():
     ap.add_argument("--no-boundary", action="store_true", help="skip the bytes -> bools legs (mina_verify_state_batch on serialized proofs)")
     ap.add_argument("--boundary-jobs", type=int, default=0, help="proofs per call of the bytes -> bools legs (default: min(--jobs, 8192))")
     ap.add_argument("--power-trace", default="", help="write the timed region's raw (seconds, watts, MHz) hwmon samples to this file (sampled every 10 ms instead of 200)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every secondary leg: the bytes -> bools, C4, one-proof-per-call and C2 processes, the lone-call latencies, the isolated kernel launches, "
+                         "the sustained / C5 / exchange-variant loops, the CPU baseline and the toolchain record (--no-probes / --no-boundary / --no-cpu-baseline still "
+                         "leave theirs out).  Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last one handed its caller as DIR/<name>.npy (float32): verdicts (one per proof; every rank's under "
+                         "torch.distributed) and flags (the step's 4 flag words).  The inputs are seeded: the same arguments give the same inputs run after run")
     ap.add_argument("--preflight", action="store_true",
                     help="the check to run FIRST on a multi-GPU node (VERDICT r04 next #7; no node was available to any round): every rank reports LOCAL_RANK, the device it bound and "
                          "that device's PCI bus id, the rank count the collectives backend saw, runs ONE small step + the verdict all-gather; rank 0 prints one JSON line and the "
                          "exit code is non-zero if two ranks share a device without shared_gpu, the backend saw != N ranks, or a verdict is wrong.  No throughput figure.")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:                                          # a plain run does what its headline needs: every secondary leg is --full's
+        args.no_probes, args.no_boundary, args.no_cpu_baseline = True, True, True
     if args.preflight:
         args.steps, args.warmup, args.jobs, args.pipeline, args.no_probes, args.no_boundary, args.no_cpu_baseline = 1, 1, min(args.jobs, 64), 1, True, True, True
     if args.kimchi:
@@ -1095,6 +1117,9 @@ def main():
     assert verdicts_ok(args.steps), "timed-region verdicts must be ACCEPT"
     if gathered is not None:
         assert all(int(g.sum()) == B for g in gathered), "every rank's shard must be ACCEPT"
+    if args.dump_outputs and rank == 0:                        # the last timed step's verdict words and flags, before any later leg reuses the slot
+        last = d_out[(it[0] - 1) % nslots].cpu().numpy()
+        dump_outputs(args.dump_outputs, {"verdicts": torch.cat([g.cpu() for g in gathered]).numpy() if gathered is not None else last[:B], "flags": last[B:B + 4]})
 
     if args.preflight:
         import socket
@@ -1321,7 +1346,7 @@ def main():
             "call_latency_ms_by_size": call_latency_by_size,
             "joules_per_proof": (power["socket_power_w_avg"] * elapsed / (args.steps * B)) if power and not (dist_on and share_gpu) else None,
             "power": power,
-            "toolchain": toolchain(),
+            "toolchain": toolchain() if args.full else None,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "u32x8-montgomery (255-bit prime fields, integer)", "data": "synthetic",
             "config": {"workload": "C3: full Proof-of-State job per proof -- 17 protocol-state hashes (chain of 16 + bridge tip) vs public inputs + linkage, "
@@ -1337,7 +1362,7 @@ def main():
                                                              "is the fixture's, not the hash of the chain beside it (that binding: tests/test_verify_fullsize.py)"},
                                            "kimchi": "32 chains, 4 wrap proofs (tests/golden/kimchi_k15.json), 32 accumulators per rank",
                                            "prepared": "32 chains, 8 wrap openings (tests/golden/state_job_k15.json), 32 accumulators per rank"}[args.mode],
-                       "folding": "IPA and accumulator checks folded over the step's batch (kimchi batch_verify's shape); randomisers drawn from the OS CSPRNG by the caller",
+                       "folding": "IPA and accumulator checks folded over the step's batch (kimchi batch_verify's shape); randomisers supplied by the caller (seeded here: the same inputs run after run)",
                        "not_in_job": {"full": "bin_prot / bincode parsing of the containers and the consensus pre-checks (host side of the boundary, before the timed region)",
                                       "kimchi": "parsing and the Pickles statement -> public-input derivation (public inputs given)",
                                       "prepared": "kimchi oracles/linearisation, the statement derivation, parsing (BatchEvaluationProof rows given)"}[args.mode],
@@ -1400,7 +1425,7 @@ def main():
                                             "(8192 proofs: 6.5 waves per SIMD, isolated launch 0.82 of the ceiling; 16384: 12.95)"}
         else:
             out["roofline"] = {"bound": "valu_int32", "kernel": "pstate_hash_kernel", "achieved": None, "peak": CHIP_SIMDS * 64 * CLOCK_HZ / PURE_MAC_ISSUE_CYCLES / 1e12, "unit": "T limb-MAC/s",
-                               "frac": None, "traffic": hbm_view["traffic"], "hbm": hbm_view, "note": "no isolated kernel timing in this run (--no-probes without the stage events, or ranks that share one GPU)"}
+                               "frac": None, "traffic": hbm_view["traffic"], "hbm": hbm_view, "note": "no isolated kernel timing in this run (no --full, or --no-probes, without the stage events; or ranks that share one GPU)"}
         if args.mode == "full" and not share_gpu:            # (ranks sharing one GPU: a step's time is not one GPU's)
             out["step_valu"] = step_valu(out["ms_per_step"], B)  # the pipelined step as a whole against instruction issue (secondary; `roofline` stays the dominant kernel's)
         if out.get("step_valu"):

@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -42,7 +43,7 @@ def test_gpus_2_without_a_gpu_fails_loudly():
 def test_gpus_2_starts_two_ranks_and_reports_them():
     """`python bench.py --gpus 2` as the driver runs it (no torch.distributed launcher): two ranks, barriers, MAX over ranks, verdict all-gather, the
     aggregate value, and the multi-device boundary leg with a tampered proof in every shard"""
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--boundary-jobs", "64"] + SMALL, capture_output=True, text=True, timeout=1500, env=clean_env())
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--full", "--boundary-jobs", "64"] + SMALL, capture_output=True, text=True, timeout=1500, env=clean_env())
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     line = json_line(r.stdout)
     assert line["n_gpus"] == 2 and line["launcher"] == "bench.py launch_ranks"
@@ -71,9 +72,29 @@ def test_collectives_of_the_multi_gpu_path_on_a_one_rank_rccl_group():
 
 
 @pytest.mark.gpu
+def test_plain_run_times_its_steps_and_dumps_the_last_step_s_outputs(tmp_path):
+    """a plain run (no --full): --steps timed steps, `ms_per_step` in the line, no secondary leg; --dump-outputs writes the last step's verdict words and flags as
+    float32 .npy, the same from run to run (seeded inputs)"""
+    dumps = []
+    for i in range(2):
+        d = tmp_path / f"out{i}"
+        r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--steps", "3", "--warmup", "1", "--jobs", "64", "--pipeline", "2", "--dump-outputs", str(d)],
+                           capture_output=True, text=True, timeout=900, env=clean_env())
+        assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+        line = json_line(r.stdout)
+        assert line["steps"] == 3 and line["ms_per_step"] > 0 and abs(line["value"] - 3 * 64 / (line["ms_per_step"] * 3 * 1e-3)) < 1e-6 * line["value"]
+        assert line["higher_is_better"] is True and line["unit"] == "proofs/s" and line["dtype"]
+        assert line["boundary_bytes_to_bools"] is None and line["sustained"] is None and line["c5_4096_total_strong"] is None and "cpu_baseline" not in line
+        dumps.append({n: np.load(d / f"{n}.npy") for n in ("verdicts", "flags")})
+    for got in dumps:
+        assert got["verdicts"].dtype == np.float32 and got["verdicts"].tolist() == [1.0] * 64 and got["flags"].tolist() == [1.0, 0.0, 1.0, 0.0]
+    assert all((dumps[0][n] == dumps[1][n]).all() for n in dumps[0])
+
+
+@pytest.mark.gpu
 def test_gpus_2_reports_the_exchange_variant():
-    """with the probes on, the N > 1 line also carries SURVEY.md 8e.2 for the whole job (`exchange_variant_8e2`: ShardedStateJob over the ranks)"""
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--steps", "2", "--warmup", "1", "--jobs", "256", "--pipeline", "2", "--no-boundary", "--no-cpu-baseline"],
+    """with --full and the probes on, the N > 1 line also carries SURVEY.md 8e.2 for the whole job (`exchange_variant_8e2`: ShardedStateJob over the ranks)"""
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--full", "--steps", "2", "--warmup", "1", "--jobs", "256", "--pipeline", "2", "--no-boundary", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=1500, env=clean_env())
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     line = json_line(r.stdout)
@@ -143,9 +164,9 @@ def test_c_abi_all_devices_leg_over_eight_logical_contexts():
 
 @pytest.mark.gpu
 def test_exchange_variant_leg_on_a_one_rank_rccl_group():
-    """with the probes on, the forced 1-rank RCCL run also times `exchange_variant_8e2` over the real backend: nccl collectives of HBM tensors on the context's pinned
+    """with --full and the probes on, the forced 1-rank RCCL run also times `exchange_variant_8e2` over the real backend: nccl collectives of HBM tensors on the context's pinned
     stream -- the leg's code path on a real node (the 2-rank runs on this box move host tensors over gloo)"""
-    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--no-boundary", "--no-cpu-baseline", "--steps", "2", "--warmup", "1", "--jobs", "1024", "--pipeline", "2"],
+    r = subprocess.run([sys.executable, BENCH, "--gpus", "1", "--full", "--no-boundary", "--no-cpu-baseline", "--steps", "2", "--warmup", "1", "--jobs", "1024", "--pipeline", "2"],
                        capture_output=True, text=True, timeout=1500, env=clean_env(MINA_BENCH_FORCE_DIST="1"))
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     x = json_line(r.stdout)["exchange_variant_8e2"]

@@ -15,6 +15,6 @@ rm -f $O/.stop; sample microbench > $O/samples_microbench.jsonl & S=$!
 timeout 300 mina_bridge_amd/microbench --sustain 8 > $O/microbench_sustain.jsonl 2>&1
 touch $O/.stop; wait $S
 rm -f $O/.stop; sample bench > $O/samples_bench.jsonl & S=$!
-timeout 600 python bench.py --no-cpu-baseline --no-boundary --steps 200 --warmup 8 > $O/bench.json 2> $O/bench.err
+timeout 600 python bench.py --full --no-cpu-baseline --no-boundary --steps 200 --warmup 8 > $O/bench.json 2> $O/bench.err
 touch $O/.stop; wait $S; rm -f $O/.stop
 wc -l $O/samples_*.jsonl; tail -4 $O/microbench_sustain.jsonl

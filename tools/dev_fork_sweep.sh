@@ -3,7 +3,7 @@
 # usage: tools/dev_fork_sweep.sh <tag> [--probes] "4:16384:dev_fork=1" "20:16384:dev_fork=0" ...   -> gpurun_out/<tag>/sweep.jsonl (one line per setting)
 cd ${GRAFT_REPO_ROOT:-$(dirname $0)/..}
 TAG=$1; shift
-EXTRA="--no-probes"; if [ "$1" = "--probes" ]; then EXTRA=""; shift; fi
+EXTRA=""; if [ "$1" = "--probes" ]; then EXTRA="--full"; shift; fi
 O=gpurun_out/$TAG; mkdir -p $O
 for cfg in "$@"; do
   IFS=: read P J T <<< "$cfg"

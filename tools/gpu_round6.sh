@@ -7,8 +7,8 @@ O=gpurun_out/$TAG; mkdir -p $O
 for st in "$@"; do
   case $st in
     pytest)   ( time timeout 3000 python -m pytest tests -m gpu -q --durations=8 ) > $O/pytest_gpu.log 2>&1; echo "pytest rc=$?" >> $O/pytest_gpu.log; tail -6 $O/pytest_gpu.log ;;
-    bench)    ( time timeout 900 python bench.py ) > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; cut -c1-600 $O/bench.json | tail -1 ;;
-    bench20)  ( time timeout 900 python bench.py --steps 20 --warmup 3 ) > $O/bench_steps20.json 2>> $O/bench.err; echo "bench20 rc=$?" ;;
+    bench)    ( time timeout 900 python bench.py --full ) > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; cut -c1-600 $O/bench.json | tail -1 ;;
+    bench20)  ( time timeout 900 python bench.py --full --steps 20 --warmup 3 ) > $O/bench_steps20.json 2>> $O/bench.err; echo "bench20 rc=$?" ;;
     profile)  timeout 900 bash tools/profile_round.sh $TAG > $O/profile_round.log 2>&1; tail -2 $O/profile_round.log | cut -c1-200
               timeout 900 bash tools/profile_sq.sh $TAG > $O/profile_sq.log 2>&1
               python tools/profile_report.py $TAG $O/bench.json > $O/${TAG}_rocprof.md 2> $O/report.err; wc -l $O/${TAG}_rocprof.md ;;
@@ -32,8 +32,8 @@ for st in "$@"; do
     timeline) # a lone forked call of 16384 proofs, kernel by kernel (profiles/r06_dev_fork.md)
               ( cd /tmp && export TMPDIR=/tmp; rocprofv3 --kernel-trace -f csv -d $GRAFT_REPO_ROOT/$O/tl -o t -- python $GRAFT_REPO_ROOT/tools/dev_fork_rate.py 16384 "1:dev_fork=1" > $GRAFT_REPO_ROOT/$O/tl.log 2>&1 )
               python tools/call_timeline.py $(find $O/tl -name "*kernel_trace.csv" | head -1) 100 0.2 > $O/timeline_lone_fork.txt; rm -rf $O/tl; tail -3 $O/timeline_lone_fork.txt ;;
-    gpus2)    ( time timeout 1200 python bench.py --gpus 2 ) > $O/bench_gpus2_shared.json 2> $O/bench_gpus2.err; echo "gpus2 rc=$?" ;;
-    gpus8)    ( time timeout 2400 python bench.py --gpus 8 --steps 10 ) > $O/bench_gpus8_shared.json 2> $O/bench_gpus8.err; echo "gpus8 rc=$?" ;;
+    gpus2)    ( time timeout 1200 python bench.py --full --gpus 2 ) > $O/bench_gpus2_shared.json 2> $O/bench_gpus2.err; echo "gpus2 rc=$?" ;;
+    gpus8)    ( time timeout 2400 python bench.py --full --gpus 8 --steps 10 ) > $O/bench_gpus8_shared.json 2> $O/bench_gpus8.err; echo "gpus8 rc=$?" ;;
     preflight) ( timeout 1200 python bench.py --gpus 8 --preflight ) > $O/preflight_gpus8.json 2> $O/preflight.err; echo "preflight rc=$?"; cut -c1-400 $O/preflight_gpus8.json ;;
     callers)  timeout 600 python tools/concurrent_callers.py 6 > $O/concurrent_callers.log 2>&1; tail -12 $O/concurrent_callers.log ;;
     soak)     for t in "soak.py 120" "soak_ipa.py 90" "soak_sponge.py 120" "soak_lanes.py 120" "soak_fork.py 120" "soak_verifier.py 180" "soak_boundary.py 300"; do set -- $t
