@@ -87,7 +87,7 @@ void mb_ctx_refresh_view(mina_ctx *v, mina_ctx *p) {
         if (a.srs_gen != b.srs_gen || a.lagrange_log2 != b.lagrange_log2 || (a.lagrange_host.empty() && !b.lagrange_host.empty())) { a.lagrange_host = b.lagrange_host; a.lagrange_log2 = b.lagrange_log2; a.srs_gen = b.srs_gen; }
         a.lagrange_table.alias(b.lagrange_table); a.lagrange_table_n = b.lagrange_table_n; a.lagrange_table_log2 = b.lagrange_table_log2;
         a.lagrange_digits.alias(b.lagrange_digits); a.lagrange_digits29.alias(b.lagrange_digits29); a.lagrange_digits_n = b.lagrange_digits_n;
-        v->pparams[i].alias(p->pparams[i]); v->have_pparams[i] = p->have_pparams[i]; v->pparams_surrogate[i] = p->pparams_surrogate[i];
+        v->pparams[i].alias(p->pparams[i]); v->have_pparams[i] = p->have_pparams[i]; v->pparams_surrogate[i] = p->pparams_surrogate[i]; v->pparams_rows1[i] = p->pparams_rows1[i];
         v->merkle_salts[i].alias(p->merkle_salts[i]); v->merkle_depth[i] = p->merkle_depth[i];
     }
     v->kimchi_index.alias(p->kimchi_index); v->kimchi_tokens.alias(p->kimchi_tokens); v->kimchi_literals.alias(p->kimchi_literals);
@@ -215,7 +215,8 @@ extern "C" int mina_field_sqrt(mina_ctx *c, int field, size_t n, const uint8_t *
 // ------------------------------------------------------------------------------------------------
 // stage timing
 static const char *PROF_NAMES[PS_COUNT] = {"msm_digits", "msm_scan", "msm_scatter", "msm_accumulate", "msm_bucket_sum", "msm_segsum",
-                                           "msm_reduce2d", "msm_finish", "bpoly_tables", "bpoly_fold", "bpoly_finish", "pstate_hash", "ipa_transcript", "kimchi_to_batch", "pickles_statement"};
+                                           "msm_reduce2d", "msm_finish", "bpoly_tables", "bpoly_fold", "bpoly_finish", "pstate_hash", "ipa_transcript", "kimchi_to_batch", "pickles_statement",
+                                           "pstate_hash1"};
 void mb_prof_begin(mina_ctx *c, int stage) {
     ProfState &p = c->prof;
     if (p.used == p.recs.size()) {

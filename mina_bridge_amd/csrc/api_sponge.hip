@@ -117,15 +117,45 @@ template <int F> static void params_to_mont(const uint8_t *params, const FieldK 
     for (int r = 0; r < 55; ++r) for (int j = 0; j < 3; ++j) pp.rc[r][j] = load(9 + 3 * r + j);
 }
 
+// The single-lane form's diagonal-normalised rows (sponge.cuh PoseidonRows1) from the Montgomery constants: d = 1 into round 0, d'_i = d_i^7 / M_ii after rounds 0 .. 53,
+// d' = 1 after round 54.  Returns false -- nothing usable, the 3-lane form runs -- when a diagonal entry is 0.
+template <int F> static bool poseidon_rows1(const PoseidonParams &pp, const FieldK &k, const fe_t &two5, const fe_t &two522, PoseidonRows1 &out) {
+    for (int i = 0; i < 3; ++i) if (fe_is_zero(pp.mds[i][i])) return false;
+    auto pow7 = [&](const fe_t &a) { const fe_t a2 = fe_mul<F>(a, a), a4 = fe_mul<F>(a2, a2); return fe_mul<F>(fe_mul<F>(a4, a2), a); };
+    auto to29 = [&](const fe_t &a, const fe_t &scale) { return fe29_from_words(fe_mul<F>(a, scale)); };   // (x 2^256)(scale) / 2^256
+    fe_t minv[3], d[3] = {k.one, k.one, k.one};
+    for (int i = 0; i < 3; ++i) minv[i] = fe_inv<F>(pp.mds[i][i], k);
+    for (int r = 0; r < 55; ++r) {
+        fe_t d7inv[3], dn[3];
+        for (int j = 0; j < 3; ++j) { const fe_t d7 = pow7(d[j]); d7inv[j] = fe_inv<F>(d7, k); dn[j] = r < 54 ? fe_mul<F>(d7, minv[j]) : k.one; }
+        for (int i = 0; i < 3; ++i) {
+            fe_t a[3];
+            for (int j = 0; j < 3; ++j) a[j] = fe_mul<F>(fe_mul<F>(dn[i], pp.mds[i][j]), d7inv[j]);
+            const fe_t rc = fe_mul<F>(dn[i], pp.rc[r][i]);
+            if (r < 54) {
+                if (!fe_eq(a[i], k.one)) return false;                // A_ii = 1 by construction
+                PoseidonRow1 &w = out.row[r][i];
+                w.a[0] = to29(a[i == 2 ? 0 : i + 1], two5); w.a[1] = to29(a[i == 0 ? 2 : i - 1], two5); w.rc = to29(rc, two522);
+            } else {
+                for (int j = 0; j < 3; ++j) out.last[i][j] = to29(a[j], two5);
+                out.last_rc[i] = to29(rc, two522);
+            }
+        }
+        for (int j = 0; j < 3; ++j) d[j] = dn[j];
+    }
+    out.ok = 1;
+    return true;
+}
+
 bool mb_params_are_surrogate(int field, const uint8_t *params);   // api_verify.hip (the compiled-in tables)
 extern "C" int mina_poseidon_set_params(mina_ctx *c, int field, const uint8_t *params) {
     if (!c || !params) return fail(MINA_ERR_ARG, "null argument");
     if (bad_field(field)) return fail(MINA_ERR_ARG, "bad field");
     HIPC(hipSetDevice(c->device));
     c->use_lane0();
-    struct { PoseidonParams pp; PoseidonParams29 q; } both;
+    struct { PoseidonParams pp; PoseidonParams29 q; PoseidonRows1 q1; } both;
     PoseidonParams &pp = both.pp;
-    static_assert(sizeof(both) == sizeof(PoseidonParams) + sizeof(PoseidonParams29), "PoseidonParams29 sits right behind PoseidonParams");
+    static_assert(sizeof(both) == sizeof(PoseidonParams) + sizeof(PoseidonParams29) + sizeof(PoseidonRows1), "PoseidonParams29 sits right behind PoseidonParams, PoseidonRows1 behind it");
     memset(&both, 0, sizeof both);
     DISPATCH_FIELD(field, {
         params_to_mont<F_>(params, c->fk[F_], pp);
@@ -139,12 +169,14 @@ extern "C" int mina_poseidon_set_params(mina_ctx *c, int field, const uint8_t *p
         for (int r = 0; r < 55; ++r) for (int i = 0; i < 3; ++i) both.q.rc2[r][i] = fe29_from_words(fe_mul<F_>(pp.rc[r][i], two522));   // (rc 2^256)(2^522) / 2^256 = rc 2^522
         both.q.absorb = fe29_from_words(two522);                 // the integer 2^522 mod p: (canonical words)(2^522) / 2^261 = x 2^261
         both.q.leave = fe29_from_words(k.one);                   // Mont(1) = 2^256 mod p:           (x 2^261)(2^256) / 2^261 = x 2^256
+        if (!poseidon_rows1<F_>(pp, k, two5, two522, both.q1)) memset(&both.q1, 0, sizeof both.q1);
     });
     int rc;
     if ((rc = c->pparams[field].ensure(sizeof both))) return rc;
     HIPC(hipMemcpyAsync(c->pparams[field].p, &both, sizeof both, hipMemcpyHostToDevice, c->L->stream));
     HIPC(hipStreamSynchronize(c->L->stream));
     c->have_pparams[field] = true;
+    c->pparams_rows1[field] = both.q1.ok != 0;
     c->pparams_surrogate[field] = mb_params_are_surrogate(field, params);
     c->merkle_depth[field] = 0;
     if (field == FIELD_FP) c->have_state_salts = false;

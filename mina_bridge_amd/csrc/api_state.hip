@@ -91,6 +91,48 @@ pstate_hash_kernel(uint32_t n, FieldK fk, const PoseidonParams *__restrict__ pp,
     }
 }
 
+// The same hashes, ONE lane per state (64 per wave) -- the largest batches (pstate_hash_dev).  The whole sponge state lives on its lane in the 29-bit form from the first
+// absorb to the last squeeze, as in the 3-lane form; the rounds use the diagonal-normalised rows (sponge.cuh poseidon_rounds_one): no cross-lane move, the row
+// constants in SGPRs: 2103 multiply-accumulates per sponge-round in the build's code object (2106 written: the first product of a column starts its accumulator) against
+// 2322.  Five waves per SIMD (91 VGPRs; amdgpu_waves_per_eu caps them at 96): the three S-box chains of a lane hide each other's latency.
+static constexpr uint32_t PSTATE_HASH1_WAVES = 5;
+template <int F>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PSTATE_HASH1_WAVES, PSTATE_HASH1_WAVES)))
+pstate_hash1_kernel(uint32_t n, const PoseidonParams *__restrict__ pp, const fe_t *__restrict__ salts /* [0..3) body, [3..6) state */,
+                    const uint32_t *__restrict__ records, const uint32_t *__restrict__ nfields, uint32_t *__restrict__ out_hash /* n*8 */,
+                    uint32_t *__restrict__ out_body /* n*8 or null */) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint32_t sp = blockIdx.x * blockDim.x + threadIdx.x;
+    if (sp >= n) return;                                             // nothing crosses lanes: a dead lane just leaves
+    const uint32_t *rec = records + (size_t)sp * MINA_PSTATE_SLOTS * 8;
+    uint32_t nf = nfields[sp]; if (nf > MINA_PSTATE_SLOTS - 1) nf = MINA_PSTATE_SLOTS - 1;
+    const PoseidonParams29 *__restrict__ q = pparams29_of(pp);
+    const PoseidonRows1 *__restrict__ q1 = prows1_of(pp);
+    auto field29 = [&](const uint32_t *w) { return fe29_mul_sg<F>(fe29_from_words(ld_fe<F>(w)), q->absorb); };   // (words)(2^522) / 2^261 = x 2^261
+    fe29_t x[3];
+#pragma unroll
+    for (int e = 0; e < 3; ++e) x[e] = fe29_mul_asm<F>(fe29_from_words(salts[e]), q->enter);
+    const uint32_t nblk = (nf + 1) / 2;
+#pragma unroll 1
+    for (uint32_t k = 0; k < nblk; ++k) {
+        if (k) poseidon_rounds_one<F>(x, q1);
+        x[0] = fe29_add(x[0], field29(rec + (size_t)(1 + 2 * k) * 8));
+        if (2 * k + 1 < nf) x[1] = fe29_add(x[1], field29(rec + (size_t)(2 + 2 * k) * 8));
+    }
+    poseidon_rounds_one<F>(x, q1);
+    fe29_t y[3];
+#pragma unroll
+    for (int e = 0; e < 3; ++e) y[e] = fe29_mul_asm<F>(fe29_from_words(salts[3 + e]), q->enter);
+    y[0] = fe29_add(y[0], field29(rec));
+    y[1] = fe29_add(y[1], x[0]);                                     // the body hash, still x 2^261
+    poseidon_rounds_one<F>(y, q1);
+    const fe_t w = fe_from_mont<F>(fe_cond_sub_p<F>(fe29_to_words(fe29_mul_asm<F>(y[0], q->leave)))); for (int i = 0; i < 8; ++i) out_hash[(size_t)sp * 8 + i] = w.v[i];
+    if (out_body) { const fe_t bw = fe_from_mont<F>(fe_cond_sub_p<F>(fe29_to_words(fe29_mul_asm<F>(x[0], q->leave)))); for (int i = 0; i < 8; ++i) out_body[(size_t)sp * 8 + i] = bw.v[i]; }
+#else
+    (void)n; (void)pp; (void)salts; (void)records; (void)nfields; (void)out_hash; (void)out_body;
+#endif
+}
+
 // salts of the hash prefixes: state after absorbing the prefix element into the zero state and permuting (3 elements each)
 template <int F>
 __global__ void prefix_salt_kernel(uint32_t n, FieldK fk, const PoseidonParams *__restrict__ pp, const uint32_t *__restrict__ prefixes, fe_t *__restrict__ salts) {
@@ -172,12 +214,23 @@ static int ensure_state_salts(mina_ctx *c) {
 
 int mb_ensure_state_salts(mina_ctx *c) { return ensure_state_salts(c); }
 
-static int pstate_hash_dev(mina_ctx *c, size_t n, const uint32_t *d_records, const uint32_t *d_nfields, uint32_t *d_hashes, uint32_t *d_bodies) {
+// `n` states of a leg of `leg` states (a piece of it, or all of it): the form follows the leg (ctx.h hash_one_lane), so that callers that cut a leg into
+// pieces (hash_piece_states) and this function agree on it
+static int pstate_hash_dev(mina_ctx *c, size_t n, size_t leg, const uint32_t *d_records, const uint32_t *d_nfields, uint32_t *d_hashes, uint32_t *d_bodies) {
     const PoseidonParams *pp = c->pparams[FIELD_FP].as<PoseidonParams>();
     const fe_t *salts = c->state_salts.as<fe_t>();
     ProfScope ps_(c, PS_STATE_HASH);
-    // below ~8 k states the chip is latency-bound: 8 lanes per state (shortest chain); above, wave-packed triples (63 of 64 lanes busy)
-    if (use_coop16(c, (n + MINA_STATES_PER_PROOF - 1) / MINA_STATES_PER_PROOF))
+    // below ~8 k states the chip is latency-bound: 8 lanes per state (shortest chain); above, wave-packed triples (63 of 64 lanes busy); with several
+    // jobs in flight and HASH1_MIN_STATES between them, one lane per state (ctx.h hash_one_lane)
+    if (hash_one_lane(c, leg)) {
+        ProfScope ps1_(c, PS_STATE_HASH1);
+        const size_t per = c->hash_piece_waves ? hash_piece_states(c, leg) : n;      // `hash_piece_waves` waves of 64 states
+        for (size_t lo = 0; lo < n; lo += per) {
+            const size_t cnt = std::min(per, n - lo);
+            mb::pstate_hash1_kernel<FIELD_FP><<<cdiv(cnt, 256), 256, c->hash_lds_bytes, c->L->stream>>>((uint32_t)cnt, pp, salts, d_records + lo * MINA_PSTATE_SLOTS * 8, d_nfields + lo,
+                                                                                                      d_hashes + lo * 8, d_bodies ? d_bodies + lo * 8 : nullptr);
+        }
+    } else if (use_coop16(c, (n + MINA_STATES_PER_PROOF - 1) / MINA_STATES_PER_PROOF))
         mb::pstate_hash_kernel<FIELD_FP, 16><<<cdiv(n * 16, 256), 256, 0, c->L->stream>>>((uint32_t)n, c->fk[FIELD_FP], pp, salts, d_records, d_nfields, d_hashes, d_bodies);
     else if (use_coop8(c, n))
         mb::pstate_hash_kernel<FIELD_FP, 8><<<cdiv(n * 8, 256), 256, 0, c->L->stream>>>((uint32_t)n, c->fk[FIELD_FP], pp, salts, d_records, d_nfields, d_hashes, d_bodies);
@@ -212,7 +265,7 @@ extern "C" int mina_protocol_state_hash_batch(mina_ctx *c, size_t n, const uint8
     if ((rc = h2d(c, L.tmp_b, n_body_fields, n * 4))) return rc;
     if ((rc = L.tmp_c.ensure(n * 32))) return rc;
     if ((rc = L.tmp_d.ensure(n * 32))) return rc;
-    if ((rc = pstate_hash_dev(c, n, L.tmp_a.as<uint32_t>(), L.tmp_b.as<uint32_t>(), L.tmp_c.as<uint32_t>(), body_hashes_out ? L.tmp_d.as<uint32_t>() : nullptr))) return rc;
+    if ((rc = pstate_hash_dev(c, n, n, L.tmp_a.as<uint32_t>(), L.tmp_b.as<uint32_t>(), L.tmp_c.as<uint32_t>(), body_hashes_out ? L.tmp_d.as<uint32_t>() : nullptr))) return rc;
     if (body_hashes_out) HIPC(hipMemcpyAsync(body_hashes_out, L.tmp_d.p, n * 32, hipMemcpyDeviceToHost, L.stream));
     return d2h_sync(c, hashes_out, L.tmp_c, n * 32);
 }
@@ -331,7 +384,7 @@ int mb_state_hashes_early(mina_ctx *c, Lane *LS, size_t ns_total, size_t lo, siz
     if (after) HIPC(hipStreamWaitEvent(LS->stream, after, 0));
     Lane *const L0 = c->L;
     c->L = LS;
-    rc = pstate_hash_dev(c, cnt, d_records + lo * MINA_PSTATE_SLOTS * 8, d_nfields + lo, LS->st_hashes.as<uint32_t>() + lo * 8, nullptr);
+    rc = pstate_hash_dev(c, cnt, ns_total, d_records + lo * MINA_PSTATE_SLOTS * 8, d_nfields + lo, LS->st_hashes.as<uint32_t>() + lo * 8, nullptr);
     c->L = L0;
     return rc;
 }
@@ -386,7 +439,7 @@ int mb_state_jobs_on_lane(mina_ctx *c, const mina_state_jobs *j, uint32_t *d_ver
         if ((rc = S.st_hashes.ensure(ns * 32))) return rc;
         const size_t early = std::min(c->state_hashes_early, ns);      // already queued on this lane by mb_state_hashes_early
         c->state_hashes_early = 0;
-        if (early < ns && (rc = pstate_hash_dev(c, ns - early, (const uint32_t *)j->state_records + early * MINA_PSTATE_SLOTS * 8, (const uint32_t *)j->state_nfields + early,
+        if (early < ns && (rc = pstate_hash_dev(c, ns - early, ns, (const uint32_t *)j->state_records + early * MINA_PSTATE_SLOTS * 8, (const uint32_t *)j->state_nfields + early,
                                                 S.st_hashes.as<uint32_t>() + early * 8, nullptr))) return rc;
         mb::pstate_chain_check_kernel<<<cdiv(B, 64), 64, 0, S.stream>>>((uint32_t)B, S.st_hashes.as<uint32_t>(), (const uint32_t *)j->expected_hashes,
                                                                          (const uint32_t *)j->state_records, (const uint8_t *)j->precheck, S.st_ok.as<uint32_t>());
@@ -479,7 +532,7 @@ int mb_state_jobs_on_lane(mina_ctx *c, const mina_state_jobs *j, uint32_t *d_ver
 // then in force (a stream keeps its CU mask / priority for life).  A pinned lane (mina_ctx_pin_lane: the caller queues its own work on that lane's stream) forks as well: the legs
 // start behind an event recorded on the lane and the lane waits for them before its verdict kernel, so everything the caller queued before the call is seen by every leg and
 // everything it queues after the call sees every leg's output -- the exchange variant (mina_state_job_fold_dev under sharded.py's `ordered()` scope) keeps its ONE ordering stream.
-static int dev_fork_lanes(mina_ctx *c, Lane **LI, Lane **LA, Lane **LS) {
+static int dev_fork_lanes(mina_ctx *c, size_t leg_states, Lane **LI, Lane **LA, Lane **LS) {
     const mina_verify_tuning tu = mb_tune();
     const int li = (int)(c->L - c->lanes);
     if (!(tu.dev_fork & 1u) || c->nlanes > MB_DEV_FORK_MAX || li < 0 || li >= MB_DEV_FORK_MAX) return MINA_OK;
@@ -510,9 +563,11 @@ static int dev_fork_lanes(mina_ctx *c, Lane **LI, Lane **LA, Lane **LS) {
     c->acc_first = tu.dev_acc_lane == 2;
     // The hashes of a forked job go out in pieces, so that the jobs in flight together ask for ~6 state-hash waves per SIMD (five fit beside nothing else, 96 VGPRs):
     // measured with the wave priorities on (lanes x piece grid at 4096 / 8192 / 16 384 proofs per call, profiles/r06_dev_fork.md) the best piece is ~6144 / lanes waves
-    // whatever the call size -- 2 lanes 3072, 3: 2048, 4: 1536, 6: 1024 -- and a lone call is best left whole.
+    // whatever the call size -- 2 lanes 3072, 3: 2048, 4: 1536, 6: 1024 -- and a lone call is best left whole.  The single-lane form (ctx.h hash_one_lane) wants twice
+    // as many of its waves of 64 states (profiles/r07_one_lane_hash.md, 4 lanes: 768 / 1536 / 3072 waves 253 / 262 / 282 k proofs/s; pieces of the 3-lane form's
+    // states, 21 per wave, left a lone wave on half the SIMDs: -13 % on the step).
     uint32_t piece = tu.dev_piece_waves;
-    if (piece == 0 && in_flight >= 2) piece = 6144u / (uint32_t)in_flight;
+    if (piece == 0 && in_flight >= 2) piece = (hash_one_lane(c, leg_states) ? 12288u : 6144u) / (uint32_t)in_flight;
     if (piece == 0xffffffffu) piece = 0;
     c->hash_piece_waves = piece;
     // A lone forked job: its hashes would hold every wave slot their 96 VGPRs allow (5 per SIMD) and the chain's waves would wait for one to retire (~13 ms): the
@@ -534,7 +589,7 @@ extern "C" int mina_state_job_batch_dev(mina_ctx *c, const mina_state_jobs *jobs
     HIPC(hipSetDevice(c->device));
     c->next_lane();
     Lane *LI = nullptr, *LA = nullptr, *LS = nullptr;
-    if ((rc = dev_fork_lanes(c, &LI, &LA, &LS))) return rc;
+    if ((rc = dev_fork_lanes(c, jobs->with_states ? jobs->batch * MINA_STATES_PER_PROOF : 0, &LI, &LA, &LS))) return rc;
     rc = mb_state_jobs_on_lane(c, jobs, (uint32_t *)d_verdicts, (uint32_t *)d_flags, LI, LA, nullptr, LS);
     c->hash_piece_waves = 0; c->hash_lds_bytes = 0; c->acc_first = false;
     return rc;
@@ -562,7 +617,7 @@ extern "C" int mina_state_job_fold_dev(mina_ctx *c, const mina_state_jobs *jobs,
     mina_ctx::FoldExport fe; fe.ipa_scalars = (uint32_t *)d_ipa_scalars; fe.ipa_point = (uint32_t *)d_ipa_point; fe.acc_scalars = (uint32_t *)d_acc_scalars; fe.acc_point = (uint32_t *)d_acc_point;
     c->fold_export = &fe;
     Lane *LI = nullptr, *LA = nullptr, *LS = nullptr;
-    if (!(rc = dev_fork_lanes(c, &LI, &LA, &LS))) rc = mb_state_jobs_on_lane(c, jobs, (uint32_t *)d_verdicts, (uint32_t *)d_flags, LI, LA, nullptr, LS);
+    if (!(rc = dev_fork_lanes(c, jobs->with_states ? jobs->batch * MINA_STATES_PER_PROOF : 0, &LI, &LA, &LS))) rc = mb_state_jobs_on_lane(c, jobs, (uint32_t *)d_verdicts, (uint32_t *)d_flags, LI, LA, nullptr, LS);
     c->hash_piece_waves = 0; c->hash_lds_bytes = 0; c->acc_first = false;
     c->fold_export = nullptr;
     return rc;

@@ -780,10 +780,11 @@ int run_device_shape(Device &D, const CallIn &in, const std::vector<size_t> &idx
             HIPC(hipMemcpyAsync(lay.at(dbase, S_NF, lo), lay.at(hbase, S_NF, lo), (hi - lo) * lay.stride[S_NF], hipMemcpyHostToDevice, up));
             HIPC(hipEventRecord(S.rec_ev[r], up));
             lane_forms();
-            // hashes in WHOLE pieces (a piece = `hash_piece_waves` waves of 21 states = two waves on every SIMD of the state leg's 128 CUs): a run of
+            // hashes in WHOLE pieces (a piece = `hash_piece_waves` waves of the form that runs -- 21 states each in the 3-lane form, 64 in the single-lane one (ctx.h
+            // hash_piece_states) -- = two waves on every SIMD of the state leg's 128 CUs): a run of
             // 1024 entries is 829 waves -- launched run by run, a fifth of the leg's SIMDs would hold one wave where the others hold two, for as long
             // The odd piece goes FIRST: it is complete after fewer runs, so the leg starts earlier, and it ends with a full piece instead of a half-empty one.
-            const size_t piece = (size_t)c->hash_piece_waves * 21, ready = hi * MINA_STATES_PER_PROOF, total = ch.n * MINA_STATES_PER_PROOF;
+            const size_t total = ch.n * MINA_STATES_PER_PROOF, piece = hash_piece_states(c, total), ready = hi * MINA_STATES_PER_PROOF;
             const size_t first = piece ? (total % piece ? total % piece : piece) : 0;
             const size_t upto = (r + 1 == ch.nsub || !piece) ? ready : (ready < first ? 0 : first + (ready - first) / piece * piece);
             int rc = MINA_OK;

@@ -89,7 +89,8 @@ struct MsmWorkspace {
 
 // HIP-event stage timing on the context stream (off by default; bench.py turns it on for the timed region)
 enum ProfStage : int { PS_DIGITS = 0, PS_SCAN, PS_SCATTER, PS_ACCUMULATE, PS_BUCKET_SUM, PS_REDUCE_A, PS_REDUCE_BC, PS_FINISH,
-                       PS_BPOLY_TABLES, PS_BPOLY_FOLD, PS_BPOLY_FINISH, PS_STATE_HASH, PS_IPA_TRANSCRIPT, PS_KIMCHI, PS_PICKLES, PS_COUNT };
+                       PS_BPOLY_TABLES, PS_BPOLY_FOLD, PS_BPOLY_FINISH, PS_STATE_HASH, PS_IPA_TRANSCRIPT, PS_KIMCHI, PS_PICKLES,
+                       PS_STATE_HASH1 /* the single-lane launches inside PS_STATE_HASH */, PS_COUNT };
 struct ProfState {
     int mask = 0;                                   // bit per stage; 0 = off
     struct Rec { hipEvent_t a, b; int stage; };
@@ -146,12 +147,14 @@ struct mina_ctx {
     DevBuf pickles_index, pickles_tokens, pickles_literals; bool have_pickles_dev = false, pickles_ms_valid = false;   // installed step index (api_pickles.hip); ms = the Tick sponge after the wrap index commitments
     void *step_host = nullptr; void (*step_host_free)(void *) = nullptr;   // host half of the installed step index (api_pickles.hip), owned by the context
     bool pparams_surrogate[2] = {false, false};                  // the installed Poseidon tables are the library's UNPINNED surrogate set
+    bool pparams_rows1[2] = {false, false};                      // the installed tables have the single-lane form's normalised rows (sponge.cuh PoseidonRows1: no zero on the MDS diagonal)
     DevBuf state_salts; bool have_state_salts = false;           // salted initial states of the named hash prefixes (Fp): MB_SALT_*
     bool legs_forked = false;        // the job being queued runs its legs on separate streams (api_state.hip)
     bool is_view = false;            // a view of another context (mb_ctx_create_view: the culprit search's): creates no stream beyond its lane 0 -- its lanes 1 .. 3 borrow the failed chunk's, and the opening check's side stream is off
     size_t state_hashes_early = 0;   // states of the next job's protocol-state leg already queued on its lane (mb_state_hashes_early), consumed by mb_state_jobs_on_lane
     uint32_t hash_piece_waves = 0;   // > 0: the protocol-state hashes of a job are launched in pieces of this many waves (api_state.hip pstate_hash_dev)
-    uint32_t hash_lds_bytes = 0;     // > 0: dynamic LDS a 3-lane state-hash workgroup reserves, to cap its waves per SIMD beside the other legs of a forked job (mina_verify_tuning.dev_hash_lds_kb)
+    uint32_t hash_lds_bytes = 0;     // > 0: dynamic LDS a state-hash workgroup reserves (3-lane or single-lane form), to cap its waves per SIMD beside the other legs of a forked job (mina_verify_tuning.dev_hash_lds_kb;
+                                     // by default only a lone job sets it, and a lone job hashes in the 3-lane form: hash_one_lane)
     bool acc_first = false;          // forked device-resident job whose accumulator leg shares the hashes' stream: queue it AHEAD of them (mina_verify_tuning.dev_acc_lane = 2)
     uint32_t dev_fork_made = 0;      // the dev_fork value the helper lanes' streams were created under (streams keep their mask / priority for life)
     // SURVEY.md 8e.2 (one exchange step over several GPUs): while set, the folded checks of a job do NOT run their fixed-base MSM and comparison -- they hand out
@@ -189,6 +192,19 @@ static inline bool use_coop8_transcripts(const mina_ctx *c, size_t batch, size_t
     const size_t in_flight = batch * (size_t)(c ? c->nlanes : 1);
     return lim ? in_flight <= lim : ((batch <= per_call_limit && in_flight <= 2048) || in_flight <= 2560);   // a call alone on the GPU: 1536 proofs 29.2 -> 26.8 ms, 2048: 30.2 -> 28.4, 3072: flat, 4096: +3 ms
 }
+
+// The protocol-state hashes of a leg of `leg_states` states run ONE lane per state (api_state.hip pstate_hash1_kernel: the fewest instructions per hash, the
+// longest chain per wave) when the installed tables have the normalised rows, several jobs are in flight and they hold HASH1_MIN_STATES states or more between
+// them (64 per wave: 65 536 are one wave per SIMD of the chip).  A lone job keeps the 3-lane form: its hashes run beside the job's own chain, as one launch
+// behind the LDS reservation tuned for that form (hash_lds_bytes), and a lone 4096-proof call would be one single-lane wave per SIMD.
+static constexpr size_t HASH1_MIN_STATES = 65536;
+static inline int hash_jobs_in_flight(const mina_ctx *c) { return c->pinned >= 0 ? 1 : c->nlanes; }      // a pinned context runs one job at a time
+static inline bool hash_one_lane(const mina_ctx *c, size_t leg_states) {
+    const int jobs = hash_jobs_in_flight(c);
+    return c->pparams_rows1[FIELD_FP] && jobs >= 2 && leg_states * (size_t)jobs >= HASH1_MIN_STATES;
+}
+// states per launch piece of such a leg (0: one launch): `hash_piece_waves` waves of the form that runs -- 64 states each in the single-lane form, 21 in the 3-lane form
+static inline size_t hash_piece_states(const mina_ctx *c, size_t leg_states) { return (size_t)c->hash_piece_waves * (hash_one_lane(c, leg_states) ? 64u : 21u); }
 
 // ---- the Proof-of-State job on the lanes of a context (api_state.hip); every pointer of `j` is a device pointer
 enum : uint32_t { MB_JOB_LEGS = 1, MB_JOB_FINISH = 2, MB_JOB_ALL = 3 };

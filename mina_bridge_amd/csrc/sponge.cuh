@@ -128,6 +128,19 @@ struct PoseidonParams29 { fe29_t mds[3][3]; fe29_t rc[55][3]; fe29_t enter /* 2^
                           uint32_t pad[1]; };     // size: a multiple of 16
 static_assert(sizeof(PoseidonParams29) % 16 == 0, "PoseidonParams29 is read with 16-byte loads");
 __host__ __device__ static inline const PoseidonParams29 *pparams29_of(const PoseidonParams *pp) { return reinterpret_cast<const PoseidonParams29 *>(pp + 1); }
+// The single-lane form's constants (pstate_hash1_kernel), behind PoseidonParams29 in the same buffer.  The S-box is a monomial, so the state of round r can be
+// carried as u_j = d_j s_j: u' = A u^7 + d' rc with A_ij = d'_i M_ij d_j^-7.  Choosing d'_i = d_i^7 / M_ii makes every diagonal entry 1 (rounds 0 .. 53), and the
+// last round takes d' = 1, so a permutation maps the same unscaled state to the same unscaled state (api_sponge.hip poseidon_rows1: derived wherever the
+// Poseidon constants are installed; refused -- `ok` = 0, the 3-lane form runs -- when some M_ii is 0).  Row i of round r < 54 is t_i + a[0] t_{i+1} + a[1] t_{i+2}
+// + rc (indices mod 3; fp29.cuh fe29_row1_sg), in the 29-bit form: a = A 2^261 mod p, rc = d' rc 2^522 mod p.  Every lane of a wave runs the same round of the
+// same row, so these are read with scalar loads and ride the constant bus.
+struct PoseidonRow1 { fe29_t a[2]; fe29_t rc; };
+struct PoseidonRows1 { PoseidonRow1 row[54][3];       // rounds 0 .. 53: diagonal-normalised rows
+                       fe29_t last[3][3]; fe29_t last_rc[3];   // round 54: the full matrix A (d' = 1) and the plain round constant (x 2^522)
+                       uint32_t ok;                    // 1: derived (no M_ii is 0)
+                       uint32_t pad[1]; };
+static_assert(sizeof(PoseidonRows1) % 16 == 0, "PoseidonRows1 is read with 16-byte loads");
+__host__ __device__ static inline const PoseidonRows1 *prows1_of(const PoseidonParams *pp) { return reinterpret_cast<const PoseidonRows1 *>(pparams29_of(pp) + 1); }
 
 template <int F>
 __device__ __forceinline__ void poseidon_permute(fe_t s[3], const PoseidonParams *__restrict__ pp) {
@@ -306,6 +319,39 @@ __device__ __forceinline__ void poseidon_rounds_tri(fe29_t &x, const PoseidonPar
     }
 #else
     (void)x; (void)q; (void)tp;                                      // device-only (the host pass never calls it)
+#endif
+}
+// One lane per sponge (pstate_hash1_kernel): the 55 rounds on a whole state in the 29-bit form (x 2^261, below SPONGE29::LANES1_STATE_MILLI_P / 1000 p, limbs normalised).
+// No cross-lane move: a lane's three S-boxes are independent chains (instruction-level parallelism in place of the 3-lane form's ds_bpermute), and the row
+// constants are wave-uniform.  Per round 3 x 156 multiply-accumulates of S-box and 3 x 234 of row against 3 x (156 + 306) in the 3-lane form (the own term
+// costs 9 by 1 where a product costs 81).  Values in units of p (tools/fe29_bounds.py prove_sponge_rounds, "1-lane"): x^2 < 2.32, x^7 < 2.11, row < 4.14.
+template <int F>
+__device__ __forceinline__ void poseidon_rounds_one(fe29_t x[3], const PoseidonRows1 *__restrict__ q1) {
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll 1
+    for (int r = 0; r < 54; ++r) {
+        const PoseidonRow1 *__restrict__ rw = q1->row[r];
+        fe29_t t[3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            const fe29_t x2 = fe29_sqr_sg<F>(x[i]);
+            const fe29_t x4 = fe29_sqr_sg<F>(x2);
+            t[i] = fe29_mul_sg<F>(fe29_mul_sg<F>(x4, x2), x[i]);
+        }
+#pragma unroll
+        for (int i = 0; i < 3; ++i) x[i] = fe29_row1_sg<F>(t[i], rw[i].a[0], t[i == 2 ? 0 : i + 1], rw[i].a[1], t[i == 0 ? 2 : i - 1], rw[i].rc);
+    }
+    fe29_t t[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        const fe29_t x2 = fe29_sqr_sg<F>(x[i]);
+        const fe29_t x4 = fe29_sqr_sg<F>(x2);
+        t[i] = fe29_mul_sg<F>(fe29_mul_sg<F>(x4, x2), x[i]);
+    }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) x[i] = fe29_dot3rc_sg<F>(q1->last[i][0], t[0], q1->last[i][1], t[1], q1->last[i][2], t[2], q1->last_rc[i]);
+#else
+    (void)x; (void)q1;                                               // device-only (the host pass never calls it)
 #endif
 }
 template <int F>

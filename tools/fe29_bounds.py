@@ -318,7 +318,7 @@ def search_lazy_sets():
 
 # ------------------------------------------------------------------------------------------------ SPEC: the Poseidon rounds' lane forms (sponge.cuh)
 # state bound (units of p / 1000) each lane form keeps between rounds; MDS entries and round constants are canonical (< p)
-SPONGE = {"LANES3_STATE_MILLI_P": 4100, "LANES8_STATE_MILLI_P": 4100, "LANES16_STATE_MILLI_P": 6100}
+SPONGE = {"LANES3_STATE_MILLI_P": 4100, "LANES8_STATE_MILLI_P": 4100, "LANES16_STATE_MILLI_P": 6100, "LANES1_STATE_MILLI_P": 6300}
 
 
 def prove_sponge_rounds(field: int, c=None):
@@ -350,8 +350,22 @@ def prove_sponge_rounds(field: int, c=None):
     one = pr.product("16-lane product + rc", [(mds, x7)], lazy="sg", c=rc)
     need(3 * one.vmax < x.vmax + 1, f"16-lane: a round maps a state below {x.vmax / p:.3f} p to {3 * one.vmax / p:.3f} p")
     out["lanes16"] = {"x7": x7, "one": one}
+    # 1 lane per sponge (round 7, pstate_hash1_kernel): x^2, x^4, x^6, x^7 of each element, then the diagonal-normalised row of rounds 0 .. 53 (fe29_row1_sg):
+    # the own x^7 unmultiplied in columns 9 .. 17, two products by wave-uniform constants, the scaled round constant in the reduction; round 54 is the full row
+    # of the 3-lane form.  Absorbs happen in the 29-bit form as in the 3-lane kernel, so the entry state is a row (or the entered salt) plus an absorbed field.
+    x = norm(c["LANES1_STATE_MILLI_P"] * p // 1000, "state (1-lane)")
+    x2 = pr.sqr("1-lane x^2", x, lazy="sg"); x4 = pr.sqr("1-lane x^4", x2, lazy="sg"); x6 = pr.mul("1-lane x^6", x4, x2, lazy="sg"); x7 = pr.mul("1-lane x^7", x6, x, lazy="sg")
+    row1 = pr.product("1-lane normalised row + rc", [(mds, x7)] * 2, lazy="sg", hi=x7, c=rc)
+    full = pr.product("1-lane last row + rc", [(mds, x7)] * 3, lazy="sg", c=rc)
+    absorbed = pr.mul("1-lane absorb: words x 2^522", norm(1 << 256, "absorbed words"), norm(p, "2^522 mod p"), lazy="sg")
+    entered = pr.mul("1-lane enter: Montgomery-2^256 words x 2^266", norm(p, "salt"), norm(p, "2^266 mod p"))
+    need(row1.vmax < x.vmax + 1, f"1-lane: a normalised round maps a state below {x.vmax / p:.3f} p to {row1.vmax / p:.3f} p")
+    for what, v in (("row + absorbed field", max(row1.vmax, full.vmax) + absorbed.vmax), ("salt + absorbed field", entered.vmax + absorbed.vmax),
+                    ("salt + body hash", entered.vmax + max(row1.vmax, full.vmax))):
+        need(v < x.vmax + 1, f"1-lane: {what} = {v / p:.3f} p does not fit the state bound {x.vmax / p:.3f} p")
+    out["lanes1"] = {"x2": x2, "x7": x7, "row": row1, "last_row": full, "absorbed": absorbed}
     # the way out of every form: one STRICT product by 2^256 mod p must land below 2^256 (fe29_to_words) and below 2 p (one conditional subtraction)
-    for key in ("LANES3_STATE_MILLI_P", "LANES8_STATE_MILLI_P", "LANES16_STATE_MILLI_P"):
+    for key in ("LANES3_STATE_MILLI_P", "LANES8_STATE_MILLI_P", "LANES16_STATE_MILLI_P", "LANES1_STATE_MILLI_P"):
         leave = pr.mul(f"leave ({key})", norm(c[key] * p // 1000), norm(p, "2^256 mod p"))
         need(leave.vmax < 2 * p and leave.vmax < 1 << 256, f"{key}: leaving the permutation needs more than one conditional subtraction")
     return pr, out

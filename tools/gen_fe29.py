@@ -10,7 +10,7 @@ and the LAZY forms the chip-filling 3-lane permutation runs its rounds in (fe29_
 m_k = -col mod 2^32 is NOT masked to 29 bits (its three high bits add a multiple of p 2^(29 k): the value stays the same field element,
 the result is < a b / R + 8.0001 p instead of < a b / R + p), the accumulator starts from the first product (no zeroing), and the dot
 product takes a tenth operand c added before the reduction ((sum + c) / R: the round constant, stored times R).  Bounds: fp29.cuh.
-SIGNED-digit forms (round 5, fe29_mul_sg / fe29_sqr_sg / fe29_mul_hi_sg / fe29_sqr_hi_sg): the quotient digit of column k < 8 is the column's own low word read as an
+SIGNED-digit forms (round 5, fe29_mul_sg / fe29_sqr_sg / fe29_mul_hi_sg / fe29_sqr_hi_sg; fe29_row1_sg, the single-lane form's normalised MDS row with SGPR constants): the quotient digit of column k < 8 is the column's own low word read as an
 int32 -- NO instruction makes it (the lazy forms spend a v_sub per digit, the strict ones a v_sub and a v_and) -- and it is SUBTRACTED by `v_mad_i64_i32` against the
 negated prime limbs; digit 8 is (col & M29) - 2^30 (one v_and_or), always negative, so the quotient is positive without an offset term: the result is
 T / R + (1 p, 2 p], limbs 0..7 normalised (tools/fe29_bounds.py `product_signed`; measured: tools/probes/sg_probe.hip).
@@ -104,6 +104,11 @@ def _pack(units, first_out, var):
     return out
 
 
+def _opnd(e):
+    """an asm input operand: "s:EXPR" -- a wave-uniform value read from an SGPR (at most one per VOP3: the constant bus) -- or a VGPR"""
+    return f'"s"({e[2:]})' if e.startswith("s:") else f'"v"({e})'
+
+
 def body_sg(col_terms, hi=None):
     """the column loop with SIGNED quotient digits.  m_k (k < 8) is the low register of the column itself: the instruction that cancels the low limb writes the new column
     to OTHER registers (early-clobber output), so the old low word stays where it is for the five later uses of the digit -- no copy, no negation, no mask.
@@ -129,9 +134,9 @@ def body_sg(col_terms, hi=None):
         for t, (x, y) in enumerate(terms):
             addend = "0" if k == 0 and t == 0 else "%0"
             if isinstance(y, int):
-                units.append((f"v_mad_u64_u32 %0, %1, @0, {y}, {addend}", [f'"v"({x})']))
+                units.append((f"v_mad_u64_u32 %0, %1, @0, {y}, {addend}", [_opnd(x)]))
             else:
-                units.append((f"v_mad_u64_u32 %0, %1, @0, @1, {addend}", [f'"v"({x})', f'"v"({y})']))
+                units.append((f"v_mad_u64_u32 %0, %1, @0, @1, {addend}", [_opnd(x), _opnd(y)]))
         for x, y in st:
             units.append(("v_mad_i64_i32 %0, %1, @0, @1, %0", [f'"v"({x})', f'"s"({y})']))      # the negated prime limb rides the constant bus: no VGPR
         if cancel:
@@ -186,6 +191,18 @@ def emit_signed():
     out += ["template <int F> __device__ __forceinline__ fe29_t fe29_mulrc_sg(const fe29_t &a, const fe29_t &b, const fe29_t &c) {"] + body_sg(dot_rc(1)) + ["}"]
     out += ["template <int F> __device__ __forceinline__ fe29_t fe29_dot2rc_sg(const fe29_t &a0, const fe29_t &b0, const fe29_t &a1, const fe29_t &b1, const fe29_t &c) {"] + body_sg(dot_rc(2)) + ["}"]
     out += ["template <int F> __device__ __forceinline__ fe29_t fe29_dot3rc_sg(const fe29_t &a0, const fe29_t &b0, const fe29_t &a1, const fe29_t &b1, const fe29_t &a2, const fe29_t &b2, const fe29_t &c) {"] + body_sg(dot_rc(3)) + ["}"]
+    # the single-lane form's diagonal-normalised MDS row (round 7): t + (a0 b0 + a1 b1 + c) / R, with a0, a1, c WAVE-UNIFORM (every lane of the wave runs the same
+    # round of the same row): their limbs ride the constant bus as SGPR operands, one per VOP3.  t -- the row's own x^7, whose matrix entry is 1 -- is added to
+    # columns 9 .. 17 before the carries: t R / R = t exactly, 9 multiply-accumulates by 1 where a product would take 81
+    def row1(k):
+        for t in range(2):
+            for i in range(L):
+                j = k - i
+                if 0 <= j < L:
+                    yield (f"b{t}.v[{j}]", f"s:a{t}.v[{i}]")
+        if k < L:
+            yield (f"s:c.v[{k}]", 1)
+    out += ["template <int F> __device__ __forceinline__ fe29_t fe29_row1_sg(const fe29_t &t, const fe29_t &a0, const fe29_t &b0, const fe29_t &a1, const fe29_t &b1, const fe29_t &c) {"] + body_sg(row1, hi="t") + ["}"]
     return out
 
 
