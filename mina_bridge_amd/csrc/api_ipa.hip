@@ -524,19 +524,10 @@ int mb_ipa_batch_check_dev(mina_ctx *c, int curve, mb::IpaShape sh, const mb::Ip
     if (sh.nshared) { if ((rc = c->L->ipa_shared.ensure(batch * sh.nshared * 32))) return rc; if ((rc = c->L->ipa_shared_off.ensure(sh.nshared * 4))) return rc; }
     HIPC(hipMemsetAsync(d_verdict, 0, 8, c->L->stream));
     const PoseidonParams *pp = c->pparams[FB].as<PoseidonParams>();
-#define IPA_PREP(CV, LN, PH, STREAM)                                                                                          \
-    mb::ipa_prepare_kernel<CV, LN, PH><<<cdiv(coop_threads<LN>(batch), 64), 64, 0, STREAM>>>(                                                      \
-        sh, c->fk[FB], c->fk[FS], pp, in.state, in.pos, in.cip, in.lr, in.delta, in.sg, in.z1, in.z2, in.pts, in.r, \
-        in.xi, in.comms, in.comm_override, in.expand, in.rb, in.sb, s.h.as<affine_t>(), c->L->ipa_points.as<affine_t>(), c->L->ipa_scalars.as<uint32_t>(), \
-        c->L->ipa_chals.as<uint32_t>(), c->L->ipa_sigma.as<uint32_t>(), d_verdict + 1, c->L->ipa_xfer.as<uint32_t>(),          \
-        c->L->ipa_shared.as<uint32_t>(), c->L->ipa_shared_off.as<uint32_t>())
     { ProfScope ps_(c, PS_IPA_TRANSCRIPT);
     {
-        // the transcript splits at its first squeeze: to_group (one lane per proof) runs on a second stream beside the rest.  8 lanes per
-        // transcript up to 1024 proofs per call (shortest dependent chain); above that the 3-lane form: 21 transcripts per wave, 3/8 of the
-        // issue slots -- measured with 16 calls of 8192 proofs in flight (bench.py), where the VALU port is what saturates
+        // the transcript splits at its first squeeze: to_group (one lane per proof) runs on a second stream beside the rest
         const mina_verify_tuning tune = mb_tune();
-        const bool oct = use_coop8_transcripts(c, batch, (size_t)tune.ipa_coop8_max);
         Lane &L = *c->L;
         if ((rc = L.ipa_xfer.ensure(batch * mb::IPA_XFER_WORDS * 4))) return rc;
         // second stream only for a context that runs ONE call at a time: with pipeline lanes in flight the other lanes fill the chip, and a
@@ -547,20 +538,27 @@ int mb_ipa_batch_check_dev(mina_ctx *c, int curve, mb::IpaShape sh, const mb::Ip
             if (!L.aux) { HIPC(hipStreamCreateWithFlags(&L.aux, hipStreamNonBlocking)); HIPC(hipEventCreateWithFlags(&L.ev_fork, hipEventDisableTiming)); HIPC(hipEventCreateWithFlags(&L.ev_join, hipEventDisableTiming)); }
             tg = L.aux;
         }
-        const bool hex = use_coop16(c, batch);
-        if (hex) { if (curve == CURVE_PALLAS) IPA_PREP(CURVE_PALLAS, 16, 1, L.stream); else IPA_PREP(CURVE_VESTA, 16, 1, L.stream); }
-        else if (oct) { if (curve == CURVE_PALLAS) IPA_PREP(CURVE_PALLAS, 8, 1, L.stream); else IPA_PREP(CURVE_VESTA, 8, 1, L.stream); }
-        else { if (curve == CURVE_PALLAS) IPA_PREP(CURVE_PALLAS, 3, 1, L.stream); else IPA_PREP(CURVE_VESTA, 3, 1, L.stream); }
+        const int ln = transcript_lanes(c, batch, (size_t)tune.ipa_coop8_max);
+        auto prepare = [&](auto phase) {                        // phase 1: the transcript up to its first squeeze, phase 2: the rest
+            return with_lanes<16, 8, 3>(ln, [&](auto lanes) {
+                constexpr int LN = decltype(lanes)::value, PH = decltype(phase)::value;
+                DISPATCH_CURVE(curve, {
+                    mb::ipa_prepare_kernel<C_, LN, PH><<<cdiv(coop_threads<LN>(batch), 64), 64, 0, L.stream>>>(
+                        sh, c->fk[FB], c->fk[FS], pp, in.state, in.pos, in.cip, in.lr, in.delta, in.sg, in.z1, in.z2, in.pts, in.r,
+                        in.xi, in.comms, in.comm_override, in.expand, in.rb, in.sb, s.h.as<affine_t>(), L.ipa_points.as<affine_t>(), L.ipa_scalars.as<uint32_t>(),
+                        L.ipa_chals.as<uint32_t>(), L.ipa_sigma.as<uint32_t>(), d_verdict + 1, L.ipa_xfer.as<uint32_t>(), L.ipa_shared.as<uint32_t>(), L.ipa_shared_off.as<uint32_t>());
+                });
+                return MINA_OK;
+            });
+        };
+        if ((rc = prepare(std::integral_constant<int, 1>{}))) return rc;
         if (side) { HIPC(hipEventRecord(L.ev_fork, L.stream)); HIPC(hipStreamWaitEvent(L.aux, L.ev_fork, 0)); }
         DISPATCH_FIELD(FB, { mb::ipa_to_group_kernel<F_><<<cdiv(batch, 64), 64, 0, tg>>>((uint32_t)batch, sh.per, c->fk[F_], L.ipa_xfer.as<uint32_t>(), L.ipa_points.as<affine_t>()); });
         if (side) HIPC(hipEventRecord(L.ev_join, L.aux));
-        if (hex) { if (curve == CURVE_PALLAS) IPA_PREP(CURVE_PALLAS, 16, 2, L.stream); else IPA_PREP(CURVE_VESTA, 16, 2, L.stream); }
-        else if (oct) { if (curve == CURVE_PALLAS) IPA_PREP(CURVE_PALLAS, 8, 2, L.stream); else IPA_PREP(CURVE_VESTA, 8, 2, L.stream); }
-        else { if (curve == CURVE_PALLAS) IPA_PREP(CURVE_PALLAS, 3, 2, L.stream); else IPA_PREP(CURVE_VESTA, 3, 2, L.stream); }
+        if ((rc = prepare(std::integral_constant<int, 2>{}))) return rc;
         if (side) HIPC(hipStreamWaitEvent(L.stream, L.ev_join, 0));
     }
     }
-#undef IPA_PREP
     HIPC(hipGetLastError());
     if (sh.nshared) { DISPATCH_FIELD(FS, { mb::ipa_shared_tail_kernel<F_><<<sh.nshared, 256, 0, c->L->stream>>>(sh.batch, sh.nshared, sh.per, c->L->ipa_shared.as<uint32_t>(), c->L->ipa_scalars.as<uint32_t>()); }); }
     if ((rc = mb_bpoly_fold(c, FS, k, batch, c->L->ipa_chals.as<uint32_t>(), c->L->ipa_sigma.as<uint32_t>(), c->L->ipa_folded.as<uint32_t>()))) return rc;
@@ -703,13 +701,15 @@ extern "C" int mina_fq_sponge_run(mina_ctx *c, int curve, size_t batch, const ui
     if ((rc = L.ipa_chals.ensure(batch * 8))) return rc;
     const PoseidonParams *pp = c->pparams[FB].as<PoseidonParams>();
     const int FS = scalar_field_of(curve);
-#define RUN_TAPE(CV, LN)                                                                                                                   \
-    mb::sponge_tape_kernel<CV, LN><<<cdiv(coop_threads<LN>(batch), 64), 64, 0, L.stream>>>((uint32_t)batch, (uint32_t)tape_len, (uint32_t)in_words, (uint32_t)out_words, \
-        c->fk[FB], c->fk[FS], pp, L.ipa_in_a.as<uint8_t>(), init_state ? L.ipa_in_c.as<uint32_t>() : nullptr, init_state ? L.ipa_sigma.as<uint32_t>() : nullptr, \
-        L.ipa_in_b.as<uint32_t>(), L.ipa_scalars.as<uint32_t>(), L.ipa_points.as<uint32_t>(), L.ipa_chals.as<uint32_t>())
-    if (batch <= COOP8_MAX_GROUPS) { if (curve == CURVE_PALLAS) RUN_TAPE(CURVE_PALLAS, 8); else RUN_TAPE(CURVE_VESTA, 8); }
-    else { if (curve == CURVE_PALLAS) RUN_TAPE(CURVE_PALLAS, 3); else RUN_TAPE(CURVE_VESTA, 3); }
-#undef RUN_TAPE
+    if ((rc = with_lanes<8, 3>(sponge_batch_lanes(batch), [&](auto lanes) {
+            constexpr int LN = decltype(lanes)::value;
+            DISPATCH_CURVE(curve, {
+                mb::sponge_tape_kernel<C_, LN><<<cdiv(coop_threads<LN>(batch), 64), 64, 0, L.stream>>>((uint32_t)batch, (uint32_t)tape_len, (uint32_t)in_words, (uint32_t)out_words,
+                    c->fk[FB], c->fk[FS], pp, L.ipa_in_a.as<uint8_t>(), init_state ? L.ipa_in_c.as<uint32_t>() : nullptr, init_state ? L.ipa_sigma.as<uint32_t>() : nullptr,
+                    L.ipa_in_b.as<uint32_t>(), L.ipa_scalars.as<uint32_t>(), L.ipa_points.as<uint32_t>(), L.ipa_chals.as<uint32_t>());
+            });
+            return MINA_OK;
+        }))) return rc;
     HIPC(hipGetLastError());
     if (final_state) HIPC(hipMemcpyAsync(final_state, L.ipa_points.p, batch * 96, hipMemcpyDeviceToHost, L.stream));
     if (final_pos) HIPC(hipMemcpyAsync(final_pos, L.ipa_chals.p, batch * 8, hipMemcpyDeviceToHost, L.stream));

@@ -371,26 +371,15 @@ int mb_kimchi_to_batch_dev(mina_ctx *c, size_t batch, uint32_t n_prev, uint32_t 
     const uint32_t B = (uint32_t)batch, ncomms = n_prev + 2 + mb::KC_COLS;
     const FieldK &kb = c->fk[FIELD_FP], &ks = c->fk[FIELD_FQ];
     mb::kimchi_rows_kernel<<<cdiv(batch * ncomms * 16, 256), 256, 0, L.stream>>>(B, n_prev, ix, in, out.comms);
-    // 8-lane sponges up to 1024 proofs per call (shortest dependent chain), 3-lane above: measured on bench.py --kimchi, 8192 proofs
-    // per step -- 16 x 512: 165 k/s (8-lane) vs 162 k/s; 4 x 2048: 137 k/s (8-lane) vs 150 k/s (3-lane).  mina_verify_tuning.kimchi_coop8_max overrides
-    const size_t coop8_max = (size_t)mb_tune().kimchi_coop8_max;
     const uint32_t fq_roles = pf_digest ? 1u : 2u;              // role 1 = the digest of the recursion challenges, unless the statement stage supplies it
-    if (use_coop16(c, batch)) {
-        mb::kimchi_fq_kernel<16><<<fq_roles * coop_role_blocks<16>(batch), 64, 0, L.stream>>>(B, n_prev, kb, ks, ppb, pps, ix, in, out, xf, d_bad, coop_role_blocks<16>(batch), (const fe_t *)pf_digest, pf_stride);
-        if (npub > 32 && npub <= 40) mb::kimchi_pub_kernel<10><<<cdiv(batch * 8, 64), 64, 0, L.stream>>>(B, npub, ks, ix, in, xf, d_bad);
-        else mb::kimchi_pub_kernel<8><<<cdiv(batch * 8, 64), 64, 0, L.stream>>>(B, npub, ks, ix, in, xf, d_bad);
-        mb::kimchi_fr_kernel<16><<<cdiv(coop_threads<16>(batch), 64), 64, 0, L.stream>>>(B, ks, pps, in, xf, d_bad);
-    } else if (use_coop8_transcripts(c, batch, coop8_max)) {
-        mb::kimchi_fq_kernel<8><<<fq_roles * coop_role_blocks<8>(batch), 64, 0, L.stream>>>(B, n_prev, kb, ks, ppb, pps, ix, in, out, xf, d_bad, coop_role_blocks<8>(batch), (const fe_t *)pf_digest, pf_stride);
-        if (npub > 32 && npub <= 40) mb::kimchi_pub_kernel<10><<<cdiv(batch * 8, 64), 64, 0, L.stream>>>(B, npub, ks, ix, in, xf, d_bad);
-        else mb::kimchi_pub_kernel<8><<<cdiv(batch * 8, 64), 64, 0, L.stream>>>(B, npub, ks, ix, in, xf, d_bad);
-        mb::kimchi_fr_kernel<8><<<cdiv(coop_threads<8>(batch), 64), 64, 0, L.stream>>>(B, ks, pps, in, xf, d_bad);
-    } else {                        // chip-filling batch: 21 sponges per wave
-        mb::kimchi_fq_kernel<3><<<fq_roles * coop_role_blocks<3>(batch), 64, 0, L.stream>>>(B, n_prev, kb, ks, ppb, pps, ix, in, out, xf, d_bad, coop_role_blocks<3>(batch), (const fe_t *)pf_digest, pf_stride);
-        if (npub > 32 && npub <= 40) mb::kimchi_pub_kernel<10><<<cdiv(batch * 8, 64), 64, 0, L.stream>>>(B, npub, ks, ix, in, xf, d_bad);
-        else mb::kimchi_pub_kernel<8><<<cdiv(batch * 8, 64), 64, 0, L.stream>>>(B, npub, ks, ix, in, xf, d_bad);
-        mb::kimchi_fr_kernel<3><<<cdiv(coop_threads<3>(batch), 64), 64, 0, L.stream>>>(B, ks, pps, in, xf, d_bad);
-    }
+    if ((rc = with_lanes<16, 8, 3>(transcript_lanes(c, batch, (size_t)mb_tune().kimchi_coop8_max), [&](auto lanes) {
+            constexpr int LN = decltype(lanes)::value;
+            mb::kimchi_fq_kernel<LN><<<fq_roles * coop_role_blocks<LN>(batch), 64, 0, L.stream>>>(B, n_prev, kb, ks, ppb, pps, ix, in, out, xf, d_bad, coop_role_blocks<LN>(batch), (const fe_t *)pf_digest, pf_stride);
+            if (npub > 32 && npub <= 40) mb::kimchi_pub_kernel<10><<<cdiv(batch * 8, 64), 64, 0, L.stream>>>(B, npub, ks, ix, in, xf, d_bad);
+            else mb::kimchi_pub_kernel<8><<<cdiv(batch * 8, 64), 64, 0, L.stream>>>(B, npub, ks, ix, in, xf, d_bad);
+            mb::kimchi_fr_kernel<LN><<<cdiv(coop_threads<LN>(batch), 64), 64, 0, L.stream>>>(B, ks, pps, in, xf, d_bad);
+            return MINA_OK;
+        }))) return rc;
     mb::kimchi_scalar_kernel<<<cdiv(batch, 64), 64, 0, L.stream>>>(B, n_prev, ks, ix, c->kimchi_tokens.as<mb::KimchiToken>(), c->kimchi_literals.as<fe_t>(), in, out, xf, d_bad);
     if (expand) { expand->p0 = &ix->sigma6; expand->pts = in.t_comm; expand->sc = xf + mb::XF_FTSC; expand->stride = mb::KC_XF; }
     else mb::kimchi_ftcomm_kernel<<<cdiv(batch * 8, 64), 64, 0, L.stream>>>(B, n_prev, kb, ix, in, out, xf);

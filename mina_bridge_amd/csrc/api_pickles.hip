@@ -504,16 +504,12 @@ int mb_pickles_dev(mina_ctx *c, size_t batch, const mb::PicklesIn &in, uint32_t 
     ProfScope ps_(c, PS_PICKLES);
     HIPC(hipMemsetD32Async((hipDeviceptr_t)d_ok, 1, batch, L.stream));   // a program that names an optional evaluation a proof lacks (outside a skipped region) fails THAT proof (pickles_scalar_kernel)
     mb::pickles_expand_kernel<<<cdiv(batch * (50 + 16 * in.n_old), 256), 256, 0, L.stream>>>(B, kp, kq, in, xe);
-    if (use_coop16(c, batch)) {
-        mb::pickles_digest_kernel<16><<<3 * coop_role_blocks<16>(batch), 64, 0, L.stream>>>(B, kp, kq, ppp, ppq, ix, in, xe, d_ok, coop_role_blocks<16>(batch));
-        mb::pickles_tick_kernel<16><<<cdiv(coop_threads<16>(batch), 64), 64, 0, L.stream>>>(B, kp, ppp, in, xe, d_ok);
-    } else if (use_coop8_transcripts(c, batch, 1024)) {
-        mb::pickles_digest_kernel<8><<<3 * coop_role_blocks<8>(batch), 64, 0, L.stream>>>(B, kp, kq, ppp, ppq, ix, in, xe, d_ok, coop_role_blocks<8>(batch));
-        mb::pickles_tick_kernel<8><<<cdiv(coop_threads<8>(batch), 64), 64, 0, L.stream>>>(B, kp, ppp, in, xe, d_ok);
-    } else {
-        mb::pickles_digest_kernel<3><<<3 * coop_role_blocks<3>(batch), 64, 0, L.stream>>>(B, kp, kq, ppp, ppq, ix, in, xe, d_ok, coop_role_blocks<3>(batch));
-        mb::pickles_tick_kernel<3><<<cdiv(coop_threads<3>(batch), 64), 64, 0, L.stream>>>(B, kp, ppp, in, xe, d_ok);
-    }
+    if ((rc = with_lanes<16, 8, 3>(transcript_lanes(c, batch, 1024), [&](auto lanes) {
+            constexpr int LN = decltype(lanes)::value;
+            mb::pickles_digest_kernel<LN><<<3 * coop_role_blocks<LN>(batch), 64, 0, L.stream>>>(B, kp, kq, ppp, ppq, ix, in, xe, d_ok, coop_role_blocks<LN>(batch));
+            mb::pickles_tick_kernel<LN><<<cdiv(coop_threads<LN>(batch), 64), 64, 0, L.stream>>>(B, kp, ppp, in, xe, d_ok);
+            return MINA_OK;
+        }))) return rc;
     mb::pickles_scalar_kernel<<<cdiv(batch, 64), 64, 0, L.stream>>>(B, kp, kq, ix, c->pickles_tokens.as<mb::KimchiToken>(), c->pickles_literals.as<fe_t>(), in, xe, d_pub, d_ok);
     HIPC(hipGetLastError());
     return MINA_OK;

@@ -221,14 +221,11 @@ extern "C" int mina_poseidon_hash(mina_ctx *c, int field, size_t n, size_t len, 
     int rc;
     if ((rc = h2d(c, c->L->tmp_a, inputs, n * len * 32))) return rc;
     if ((rc = c->L->tmp_c.ensure(n * 32))) return rc;
-    // up to 8192 sponges: 8 lanes per sponge (shortest dependent chain); above: wave-packed triples (21 sponges per wave) -- both run their
-    // rounds on the 29-bit limbs (fp29.cuh), which beats one lane per sponge on the saturated 8 x 32 form at every size (19 k against 25 k
-    // cycles per sponge-round), so the single-lane and 4-lane kernels are no longer dispatched here
-    if (n <= COOP8_MAX_GROUPS) {
-        DISPATCH_FIELD(field, { poseidon_hash_coop_kernel<F_, 8><<<cdiv(n * 8, 256), 256, 0, c->L->stream>>>((uint32_t)n, (uint32_t)len, c->fk[F_], c->pparams[field].as<PoseidonParams>(), c->L->tmp_a.as<uint32_t>(), c->L->tmp_c.as<uint32_t>()); });
-    } else {
-        DISPATCH_FIELD(field, { poseidon_hash_coop_kernel<F_, 3><<<cdiv(coop_threads<3>(n), 256), 256, 0, c->L->stream>>>((uint32_t)n, (uint32_t)len, c->fk[F_], c->pparams[field].as<PoseidonParams>(), c->L->tmp_a.as<uint32_t>(), c->L->tmp_c.as<uint32_t>()); });
-    }
+    if ((rc = with_lanes<8, 3>(sponge_batch_lanes(n), [&](auto lanes) {
+            constexpr int LN = decltype(lanes)::value;
+            DISPATCH_FIELD(field, { poseidon_hash_coop_kernel<F_, LN><<<cdiv(coop_threads<LN>(n), 256), 256, 0, c->L->stream>>>((uint32_t)n, (uint32_t)len, c->fk[F_], c->pparams[field].as<PoseidonParams>(), c->L->tmp_a.as<uint32_t>(), c->L->tmp_c.as<uint32_t>()); });
+            return MINA_OK;
+        }))) return rc;
     return d2h_sync(c, out, c->L->tmp_c, n * 32);
 }
 
@@ -268,24 +265,15 @@ static int merkle_prepare_salts(mina_ctx *c, int field, uint32_t depth) {
 
 // Merkle fold of n paths with everything in HBM, queued on the current lane (salts must have been prepared: merkle_prepare_salts)
 int mb_merkle_fold_dev(mina_ctx *c, int field, size_t n, uint32_t depth, const uint32_t *d_leaves, const uint32_t *d_sib, const uint8_t *d_dirs, uint32_t *d_roots) {
-    if (use_coop16(c, n)) {                                      // a few paths: 16 lanes each (shortest chain)
+    return with_lanes<16, 8, 3>(merkle_lanes(c, n), [&](auto lanes) {
+        constexpr int LN = decltype(lanes)::value;
         DISPATCH_FIELD(field, {
-            merkle_fold_coop_kernel<F_, 16><<<cdiv(n * 16, 256), 256, 0, c->L->stream>>>((uint32_t)n, depth, c->fk[F_], c->pparams[field].as<PoseidonParams>(),
+            merkle_fold_coop_kernel<F_, LN><<<cdiv(coop_threads<LN>(n), 256), 256, 0, c->L->stream>>>((uint32_t)n, depth, c->fk[F_], c->pparams[field].as<PoseidonParams>(),
                 c->merkle_salts[field].as<fe_t>(), d_leaves, d_sib, d_dirs, d_roots);
         });
-    } else if (n <= COOP8_MAX_GROUPS) {                          // latency-bound batch: 8 lanes per path
-        DISPATCH_FIELD(field, {
-            merkle_fold_coop_kernel<F_, 8><<<cdiv(n * 8, 256), 256, 0, c->L->stream>>>((uint32_t)n, depth, c->fk[F_], c->pparams[field].as<PoseidonParams>(),
-                c->merkle_salts[field].as<fe_t>(), d_leaves, d_sib, d_dirs, d_roots);
-        });
-    } else {
-        DISPATCH_FIELD(field, {
-            merkle_fold_coop_kernel<F_, 3><<<cdiv(coop_threads<3>(n), 256), 256, 0, c->L->stream>>>((uint32_t)n, depth, c->fk[F_], c->pparams[field].as<PoseidonParams>(),
-                c->merkle_salts[field].as<fe_t>(), d_leaves, d_sib, d_dirs, d_roots);
-        });
-    }
-    HIPC(hipGetLastError());
-    return MINA_OK;
+        HIPC(hipGetLastError());
+        return MINA_OK;
+    });
 }
 int mb_merkle_prepare_salts(mina_ctx *c, int field, uint32_t depth) { return merkle_prepare_salts(c, field, depth); }
 

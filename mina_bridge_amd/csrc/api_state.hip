@@ -9,6 +9,7 @@
 //        step accumulator check (Vesta, 2^16 bases)                                             -> mb_accumulator_check_dev
 // All of it is queued on ONE lane with no host synchronisation between the stages; one verdict word per proof.
 #include <chrono>
+#include <optional>
 #include "ctx.h"
 #include "msm.cuh"
 #include "sponge.cuh"
@@ -221,33 +222,27 @@ static int pstate_hash_dev(mina_ctx *c, size_t n, size_t leg, const uint32_t *d_
     const fe_t *salts = c->state_salts.as<fe_t>();
     ProfScope ps_(c, PS_STATE_HASH);
     // below ~8 k states the chip is latency-bound: 8 lanes per state (shortest chain); above, wave-packed triples (63 of 64 lanes busy); with several
-    // jobs in flight and HASH1_MIN_STATES between them, one lane per state (ctx.h hash_one_lane)
-    if (hash_one_lane(c, leg)) {
-        ProfScope ps1_(c, PS_STATE_HASH1);
-        const size_t per = c->hash_piece_waves ? hash_piece_states(c, leg) : n;      // `hash_piece_waves` waves of 64 states
-        for (size_t lo = 0; lo < n; lo += per) {
-            const size_t cnt = std::min(per, n - lo);
-            mb::pstate_hash1_kernel<FIELD_FP><<<cdiv(cnt, 256), 256, c->hash_lds_bytes, c->L->stream>>>((uint32_t)cnt, pp, salts, d_records + lo * MINA_PSTATE_SLOTS * 8, d_nfields + lo,
-                                                                                                      d_hashes + lo * 8, d_bodies ? d_bodies + lo * 8 : nullptr);
-        }
-    } else if (use_coop16(c, (n + MINA_STATES_PER_PROOF - 1) / MINA_STATES_PER_PROOF))
-        mb::pstate_hash_kernel<FIELD_FP, 16><<<cdiv(n * 16, 256), 256, 0, c->L->stream>>>((uint32_t)n, c->fk[FIELD_FP], pp, salts, d_records, d_nfields, d_hashes, d_bodies);
-    else if (use_coop8(c, n))
-        mb::pstate_hash_kernel<FIELD_FP, 8><<<cdiv(n * 8, 256), 256, 0, c->L->stream>>>((uint32_t)n, c->fk[FIELD_FP], pp, salts, d_records, d_nfields, d_hashes, d_bodies);
-    else if (c->hash_piece_waves && (n + 20) / 21 > c->hash_piece_waves) {
-        // The whole launch would hold every wave slot its 88 VGPRs allow (5 per SIMD) for most of its 20 ms, and the kernels of the other legs /
-        // chunks of a call (a few hundred waves each, one behind the other) would wait for slots.  In pieces of `hash_piece_waves` waves
+    // jobs in flight and HASH1_MIN_STATES between them, one lane per state (ctx.h pstate_hash_lanes)
+    return with_lanes<1, 16, 8, 3>(pstate_hash_lanes(c, n, leg), [&](auto lanes) {
+        constexpr int LN = decltype(lanes)::value;
+        constexpr bool wide = LN == 1 || LN == 3;             // the chip-filling forms
+        std::optional<ProfScope> ps1_;
+        if (LN == 1) ps1_.emplace(c, PS_STATE_HASH1);
+        // A whole chip-filling launch would hold every wave slot its VGPRs allow (5 per SIMD in the 3-lane form) for most of its 20 ms, and the kernels of
+        // the other legs / chunks of a call (a few hundred waves each, one behind the other) would wait for slots.  In pieces of `hash_piece_waves` waves
         // (~2 per SIMD: the multiplier is still saturated) the rest of the register file stays free for them.
-        const size_t per = (size_t)c->hash_piece_waves * 21;
+        const size_t per = wide && c->hash_piece_waves ? hash_piece_states(c, leg) : n;
+        const uint32_t lds = wide ? c->hash_lds_bytes : 0;
         for (size_t lo = 0; lo < n; lo += per) {
             const size_t cnt = std::min(per, n - lo);
-            mb::pstate_hash_kernel<FIELD_FP, 3><<<cdiv(coop_threads<3>(cnt), 256), 256, c->hash_lds_bytes, c->L->stream>>>((uint32_t)cnt, c->fk[FIELD_FP], pp, salts, d_records + lo * MINA_PSTATE_SLOTS * 8,
-                                                                                                             d_nfields + lo, d_hashes + lo * 8, d_bodies ? d_bodies + lo * 8 : nullptr);
+            const uint32_t *rec = d_records + lo * MINA_PSTATE_SLOTS * 8, *nf = d_nfields + lo;
+            uint32_t *hash = d_hashes + lo * 8, *body = d_bodies ? d_bodies + lo * 8 : nullptr;
+            if constexpr (LN == 1) mb::pstate_hash1_kernel<FIELD_FP><<<cdiv(cnt, 256), 256, lds, c->L->stream>>>((uint32_t)cnt, pp, salts, rec, nf, hash, body);
+            else mb::pstate_hash_kernel<FIELD_FP, LN><<<cdiv(coop_threads<LN>(cnt), 256), 256, lds, c->L->stream>>>((uint32_t)cnt, c->fk[FIELD_FP], pp, salts, rec, nf, hash, body);
         }
-    } else
-        mb::pstate_hash_kernel<FIELD_FP, 3><<<cdiv(coop_threads<3>(n), 256), 256, c->hash_lds_bytes, c->L->stream>>>((uint32_t)n, c->fk[FIELD_FP], pp, salts, d_records, d_nfields, d_hashes, d_bodies);
-    HIPC(hipGetLastError());
-    return MINA_OK;
+        HIPC(hipGetLastError());
+        return MINA_OK;
+    });
 }
 
 extern "C" int mina_protocol_state_hash_batch(mina_ctx *c, size_t n, const uint8_t *records, const uint32_t *n_body_fields, uint8_t *hashes_out,

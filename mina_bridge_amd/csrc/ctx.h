@@ -12,6 +12,8 @@
 #include <thread>
 #include <algorithm>
 #include <string>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/mina_verify.h"
@@ -166,8 +168,8 @@ struct mina_ctx {
 
 // lane-cooperative Poseidon: batches of at most this many sponges use 8 lanes each (shortest dependency chain, 2.6x the issue
 // slots), larger ones the wave-packed 3-lane form (21 sponges per wave); both run their rounds on the 29-bit limbs (fp29.cuh).
-// The per-proof transcripts of a job (kimchi, Pickles statement, opening) switch at 1024 proofs per call instead (api_kimchi.hip,
-// api_pickles.hip, api_ipa.hip: measured with 16 calls in flight).
+// The per-proof transcripts of a job (kimchi, Pickles statement, opening) switch at 1024 proofs per call instead (transcript_lanes:
+// measured with 16 calls in flight).
 static constexpr size_t COOP8_MAX_GROUPS = 8192;   // (the default of mina_verify_tuning.coop8_max)
 // `groups` sponges per call, `nlanes` calls in flight: the choice looks at the work in flight (256 proofs per call on 16 lanes are 69 k state
 // hashes at once -- the 8-lane form then spends 2.1x the issue slots of a saturated chip: 480 proofs per call 66 -> 75 k/s).
@@ -206,6 +208,27 @@ static inline bool hash_one_lane(const mina_ctx *c, size_t leg_states) {
 // states per launch piece of such a leg (0: one launch): `hash_piece_waves` waves of the form that runs -- 64 states each in the single-lane form, 21 in the 3-lane form
 static inline size_t hash_piece_states(const mina_ctx *c, size_t leg_states) { return (size_t)c->hash_piece_waves * (hash_one_lane(c, leg_states) ? 64u : 21u); }
 
+// ---- the lane form of each kind of sponge work: lanes per sponge, launched through with_lanes below.  Each site has exactly one of these rules.
+// Salted hashes (the account hashes; the protocol-state hashes behind their single-lane test): `proofs` decides the 16-lane form, `sponges` the 8-lane one.
+static inline int hash_lanes(const mina_ctx *c, size_t proofs, size_t sponges) { return use_coop16(c, proofs) ? 16 : (use_coop8(c, sponges) ? 8 : 3); }
+// `n` protocol-state hashes of a leg of `leg_states` (api_state.hip pstate_hash_dev); the 16-lane test counts the proofs those `n` states make up
+static inline int pstate_hash_lanes(const mina_ctx *c, size_t n, size_t leg_states) {
+    return hash_one_lane(c, leg_states) ? 1 : hash_lanes(c, (n + MINA_STATES_PER_PROOF - 1) / MINA_STATES_PER_PROOF, n);
+}
+// The per-proof transcripts: the Pickles statement passes 1024 proofs per call, kimchi mina_verify_tuning.kimchi_coop8_max and the opening check .ipa_coop8_max
+// (both 1024 by default).  Kimchi, measured on bench.py --kimchi with 8192 proofs per step: 16 x 512 ran 165 k/s in the 8-lane form against 162 k/s in the 3-lane
+// form, 4 x 2048 137 k/s against 150 k/s.  The opening check with 16 calls of 8192 proofs in flight (bench.py), where the VALU port is what saturates: the 3-lane
+// form runs 21 transcripts per wave at 3/8 of the issue slots.
+static inline int transcript_lanes(const mina_ctx *c, size_t batch, size_t per_call_limit) {
+    return use_coop16(c, batch) ? 16 : (use_coop8_transcripts(c, batch, per_call_limit) ? 8 : 3);
+}
+// mina_poseidon_hash and mina_fq_sponge_run: 8 lanes up to COOP8_MAX_GROUPS sponges per call, whatever the tuning and the calls in flight, the 3-lane form above.
+// Both forms run their rounds on the 29-bit limbs (fp29.cuh), which beats one lane per sponge on the saturated 8 x 32 form at every size (19 k against 25 k
+// cycles per sponge-round).
+static inline int sponge_batch_lanes(size_t n) { return n <= COOP8_MAX_GROUPS ? 8 : 3; }
+// the Merkle fold (api_sponge.hip mb_merkle_fold_dev): a few paths take 16 lanes each (use_coop16), the rest as sponge_batch_lanes
+static inline int merkle_lanes(const mina_ctx *c, size_t paths) { return use_coop16(c, paths) ? 16 : sponge_batch_lanes(paths); }
+
 // ---- the Proof-of-State job on the lanes of a context (api_state.hip); every pointer of `j` is a device pointer
 enum : uint32_t { MB_JOB_LEGS = 1, MB_JOB_FINISH = 2, MB_JOB_ALL = 3 };
 struct StateJobCarry { uint32_t *ipa_v = nullptr, *acc_v = nullptr, *kimchi_bad = nullptr; const uint32_t *stmt_ok = nullptr; };
@@ -236,6 +259,16 @@ static inline bool bad_field(int f) { return f != 0 && f != 1; }
 
 #define DISPATCH_FIELD(field, ...)                           \
     do { if ((field) == FIELD_FP) { constexpr int F_ = FIELD_FP; __VA_ARGS__; } else { constexpr int F_ = FIELD_FQ; __VA_ARGS__; } } while (0)
+#define DISPATCH_CURVE(curve, ...)                           \
+    do { if ((curve) == CURVE_PALLAS) { constexpr int C_ = CURVE_PALLAS; __VA_ARGS__; } else { constexpr int C_ = CURVE_VESTA; __VA_ARGS__; } } while (0)
+
+// Runs `f(std::integral_constant<int, LN>{})` for the lane form LN = `lanes` (one of the rules above) and returns its result.  The template arguments list
+// the forms the site instantiates kernels for; a form outside the list is an error, not a fall-back.
+template <int LN, int... FORMS, class Fn> static inline int with_lanes(int lanes, Fn &&f) {
+    if (lanes == LN) return f(std::integral_constant<int, LN>{});
+    if constexpr (sizeof...(FORMS) > 0) return with_lanes<FORMS...>(lanes, std::forward<Fn>(f));
+    else return fail(MINA_ERR_ARG, "no kernel of the " + std::to_string(lanes) + "-lane form at this site");
+}
 
 static inline uint32_t cdiv(size_t a, size_t b) { return (uint32_t)((a + b - 1) / b); }
 

@@ -172,53 +172,15 @@ poseidon_permute_kernel(uint32_t n, FieldK fk, const PoseidonParams *__restrict_
     for (int j = 0; j < 3; ++j) { fe_t w = fe_from_mont<F>(s[j]); for (int q = 0; q < 8; ++q) states[(size_t)i * 24 + j * 8 + q] = w.v[q]; }
 }
 
-// n independent sponges: absorb len elements, squeeze one (rate 2)
-template <int F>
-__global__ void __launch_bounds__(256)
-poseidon_hash_kernel(uint32_t n, uint32_t len, FieldK fk, const PoseidonParams *__restrict__ pp,
-                     const uint32_t *__restrict__ inputs, uint32_t *__restrict__ out_words) {
-    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    fe_t s[3] = {fe_zero(), fe_zero(), fe_zero()};
-    uint32_t count = 0;
-    for (uint32_t e = 0; e < len; ++e) {
-        fe_t w; for (int q = 0; q < 8; ++q) w.v[q] = inputs[((size_t)i * len + e) * 8 + q];
-        w = fe_to_mont<F>(w, fk.r2);
-        if (count == 2) { poseidon_permute<F>(s, pp); count = 0; }
-        s[count] = fe_add<F>(s[count], w); ++count;
-    }
-    poseidon_permute<F>(s, pp);
-    fe_t w = fe_from_mont<F>(s[0]);
-    for (int q = 0; q < 8; ++q) out_words[(size_t)i * 8 + q] = w.v[q];
-}
-
 // ---------------------------------------------------------------- K3, lane-cooperative form
-// Four lanes (one DPP quad) per sponge: lane q < 3 owns state element s_q (lane 3 idles).  Per round every lane does
-// its own x^7 (4 products), the three results are exchanged with quad_perm DPP moves (no LDS), and lane q computes
-// row q of the MDS product (3 products): 7 dependent products per round instead of 21 -- a 3x shorter critical path
-// for the sequential sponge work (Fiat-Shamir transcripts, Merkle paths) at batch sizes that cannot fill the chip.
+// The sequential sponge work (Fiat-Shamir transcripts, Merkle paths) at batch sizes that cannot fill the chip wants a short critical path: the
+// permutation is split over 16, 8 or 3 lanes per sponge (the host picks the form: ctx.h with_lanes and its rules).
 #if defined(__HIPCC__)
-template <int F>
-__device__ __forceinline__ void poseidon_permute_quad(fe_t &s, const PoseidonParams *__restrict__ pp) {
-    const int q = threadIdx.x & 3, qq = q < 3 ? q : 2;
-    const fe_t m0 = pp->mds[qq][0], m1 = pp->mds[qq][1], m2 = pp->mds[qq][2];
-#pragma unroll 1
-    for (int r = 0; r < 55; ++r) {
-        // lazy round (fp.cuh "lazy forms"): s < 2p in, every product unreduced, one conditional subtraction of 2p out
-        fe_t x2 = fe_mul_nr<F>(s, s);
-        fe_t x4 = fe_mul_nr<F>(x2, x2);
-        fe_t t = fe_mul_nr<F>(fe_mul_nr<F>(x4, x2), s);
-        fe_t t0 = quad_bcast<0>(t), t1 = quad_bcast<1>(t), t2 = quad_bcast<2>(t);
-        s = fe_add_csub2p<F>(fe_dot3_nr<F>(m0, t0, m1, t1, m2, t2), pp->rc[r][qq]);
-    }
-    s = fe_cond_sub_p<F>(s);
-}
-
 // Eight lanes per sponge (half a DPP row): the pair of lanes (2e, 2e+1) owns state element e (lanes 6, 7 mirror e = 2).
 // x^7 takes 3 dependent products instead of 4 (x2; then x4 on the even lane and x3 on the odd lane, swapped inside the
 // pair; then x4 * x3) and an MDS row 1.65 instead of 2.3 (even lane: a two-term dot product, odd lane: the third product,
 // as a dot product with a zero term so that both lanes run the same instructions; the halves are swapped and added):
-// 4.65 product latencies per round against 6.3 for the quad form, bit-identical state.  Costs 1.5x the issue slots per
+// 4.65 product latencies per round against 6.3 with one lane per state element, bit-identical state.  Costs 1.5x the issue slots per
 // permutation, so only for batches that leave the chip latency-bound (host picks the form).
 __device__ __forceinline__ fe_t pair_swap(const fe_t &a) {
     fe_t r = a;
@@ -275,8 +237,8 @@ __device__ __forceinline__ void poseidon_permute_oct(fe_t &s, const PoseidonPara
 #endif
 }
 // Three lanes per sponge: 21 sponges per wave64 (lanes 3g, 3g+1, 3g+2 own state elements 0, 1, 2 of sponge g; lane 63 shadows
-// group 20).  Same 7 dependent products per round as the quad form, but no idle fourth lane: 63 of 64 lanes work, which is
-// what the chip-filling batches want (the quad form caps at 75 % lane use).  The x^7 of the two other lanes arrive by ds_bpermute
+// group 20).  7 dependent products per round (a lane's x^7, then its MDS row), and 63 of 64 lanes work, which is what the
+// chip-filling batches want (a DPP quad per sponge would idle its fourth lane: 75 % lane use).  The x^7 of the two other lanes arrive by ds_bpermute
 // (18 per round; measured on the round alone they cost ~3 %: profiles/r05_clock_power.md).  Bit-identical state.
 struct TriPos { uint32_t base, e; };
 __device__ __forceinline__ TriPos tri_pos() {
@@ -408,13 +370,14 @@ __device__ __forceinline__ void poseidon_permute_hex(fe_t &s, const PoseidonPara
     (void)s; (void)pp;
 #endif
 }
-// LANES-lane cooperative permutation / element ownership, LANES = 3 (wave-packed triples), 4 (quad), 8 (octet) or 16
+// LANES-lane cooperative permutation / element ownership, LANES = 3 (wave-packed triples), 8 (octet) or 16
 template <int F, int LANES> __device__ __forceinline__ void poseidon_permute_coop(fe_t &s, const PoseidonParams *__restrict__ pp) {
-    if (LANES == 16) poseidon_permute_hex<F>(s, pp); else if (LANES == 8) poseidon_permute_oct<F>(s, pp); else if (LANES == 3) poseidon_permute_tri<F>(s, pp); else poseidon_permute_quad<F>(s, pp);
+    static_assert(LANES == 3 || LANES == 8 || LANES == 16, "the cooperative forms are 3, 8 and 16 lanes per sponge");
+    if (LANES == 16) poseidon_permute_hex<F>(s, pp); else if (LANES == 8) poseidon_permute_oct<F>(s, pp); else poseidon_permute_tri<F>(s, pp);
 }
 template <int LANES> __device__ __forceinline__ uint32_t coop_elem() {                 // state element this lane owns
     if (LANES == 3) return tri_pos().e;
-    const uint32_t l = threadIdx.x & (LANES - 1), e = LANES == 16 ? (l >> 2) : (LANES == 8 ? (l >> 1) : l);
+    const uint32_t l = threadIdx.x & (LANES - 1), e = LANES == 16 ? (l >> 2) : (l >> 1);
     return e < 3 ? e : 2;
 }
 template <int LANES> __device__ __forceinline__ fe_t coop_get(const fe_t &s, int pos) { // element `pos` -> all lanes of the group
@@ -423,8 +386,7 @@ template <int LANES> __device__ __forceinline__ fe_t coop_get(const fe_t &s, int
 #pragma unroll
         for (int i = 0; i < 8; ++i) r.v[i] = (uint32_t)__shfl((int)s.v[i], src, 64);
         return r; }
-    if (LANES == 8) return pos == 0 ? oct_bcast<0>(s) : (pos == 1 ? oct_bcast<2>(s) : oct_bcast<4>(s));
-    return pos == 0 ? quad_bcast<0>(s) : (pos == 1 ? quad_bcast<1>(s) : quad_bcast<2>(s));
+    return pos == 0 ? oct_bcast<0>(s) : (pos == 1 ? oct_bcast<2>(s) : oct_bcast<4>(s));
 }
 // which sponge a thread works on and whether it is the group's writer; blockDim.x is a multiple of 64
 template <int LANES> __device__ __forceinline__ uint32_t coop_sponge_index(bool &writer) {
@@ -445,7 +407,7 @@ template <int LANES> __device__ __forceinline__ uint32_t coop_role_item(uint32_t
 }
 
 // mina-poseidon `ArithmeticSponge` state machine (rate 2) over base field F, Montgomery state, lane-cooperative over
-// LANES = 3 (wave-packed triples), 4 or 8 lanes: `s` = the state element this lane owns (coop_elem), the position (squeezed, count)
+// LANES = 3 (wave-packed triples), 8 or 16 lanes: `s` = the state element this lane owns (coop_elem), the position (squeezed, count)
 // is replicated.  Absorbed values and squeezed results are replicated on all lanes of the group.
 template <int F, int LANES> struct DevSponge {
     fe_t s; int squeezed; int count; const PoseidonParams *pp;
@@ -472,7 +434,7 @@ template <int LANES> __device__ __forceinline__ uint32_t coop_lane() { return LA
 // the lanes that hold state elements 0, 1, 2 of a cooperative sponge (one lane each)
 template <int LANES> __device__ __forceinline__ bool coop_state_owner() {
     const uint32_t ln = coop_lane<LANES>();
-    return LANES == 16 ? (ln < 12 && !(ln & 3u)) : (LANES == 8 ? (ln < 6 && !(ln & 1u)) : (LANES == 3 ? (threadIdx.x & 63u) < 63u : ln < 3));
+    return LANES == 16 ? (ln < 12 && !(ln & 3u)) : (LANES == 8 ? (ln < 6 && !(ln & 1u)) : (threadIdx.x & 63u) < 63u);
 }
 template <int LANES> __device__ __forceinline__ void store_fe(uint32_t *p, const fe_t &a) { if (coop_writer<LANES>()) for (int i = 0; i < 8; ++i) p[i] = a.v[i]; }
 template <int LANES> __device__ __forceinline__ void store_pt(affine_t *p, const affine_t &a) { if (coop_writer<LANES>()) *p = a; }
@@ -536,7 +498,7 @@ __global__ void merkle_salt_kernel(uint32_t depth, FieldK fk, const PoseidonPara
     for (int j = 0; j < 3; ++j) salts[(size_t)h * 3 + j] = s[j];
 }
 
-// n independent sponges, lane-cooperative (8 lanes each, or wave-packed triples): absorb len elements, squeeze one (same contract as poseidon_hash_kernel)
+// n independent sponges, lane-cooperative (8 lanes each, or wave-packed triples): absorb len elements (rate 2), squeeze one
 template <int F, int LANES>
 __global__ void __launch_bounds__(256)
 poseidon_hash_coop_kernel(uint32_t n, uint32_t len, FieldK fk, const PoseidonParams *__restrict__ pp,

@@ -155,8 +155,8 @@ def test_accumulator_check_multi_unfolded(ctx_srs, oracle, srs_oracle, curve, k,
 
 @pytest.mark.parametrize("n", [8192, 8193, 199999, 200000])
 def test_poseidon_hash_every_kernel_form(ctx, oracle, n):
-    """the sponge-hash entry point picks its kernel by batch size: 8 lanes per sponge (<= 8192), 4 lanes (< 200 000), one lane;
-    each side of both thresholds against the oracle (sampled sponges; the inputs repeat with period 1009)"""
+    """the sponge-hash entry point picks its kernel by batch size: 8 lanes per sponge (<= 8192), the wave-packed 3-lane form above;
+    each side of the threshold, and 199 999 / 200 000 sponges, against the oracle (sampled sponges; the inputs repeat with period 1009)"""
     import mina_bridge_amd as m
     field, length = 0, 5
     params = m.poseidon_params.default_params_bytes(field)

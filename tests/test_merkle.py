@@ -64,7 +64,7 @@ def test_gpu_merkle_roots(ctx, oracle, field, n, depth):
 @pytest.mark.gpu
 @pytest.mark.parametrize("field", [0, 1])
 def test_gpu_cooperative_and_single_lane_poseidon_agree(ctx, oracle, field):
-    """mina_poseidon_hash uses the 4-lane cooperative kernel below 65 536 sponges and one lane per sponge above:
+    """mina_poseidon_hash runs 8 lanes per sponge up to 8192 sponges and the wave-packed 3-lane form above:
     both must reproduce the oracle"""
     import mina_bridge_amd as m
     params = m.poseidon_params.default_params_bytes(field)

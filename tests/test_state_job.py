@@ -20,7 +20,7 @@ def _le(x):
 
 def test_state_hash_parity_reference_state_and_random(ctx, oracle):
     """MinaHash(ProtocolState) on the GPU == oracle, for the reference's own serialized state (constants.rs:22) and random ones;
-    both lane-cooperative forms (8 lanes for small batches, 4 lanes above 8192 states)"""
+    both lane-cooperative forms of a lone call (16 lanes for a few proofs' worth of states, 3 lanes above 8192 states)"""
     import mina_bridge_amd as m
     from oracle import mina_state_ref as S, state_job_ref as J
     from state_job_helpers import pp_fp, state_records
@@ -45,7 +45,7 @@ def test_state_hash_parity_reference_state_and_random(ctx, oracle):
     h2 = ctx.protocol_state_hash_batch(r2, np.array([0, 1], np.uint32))
     assert oracle.le_to_int(h2[0]) == S.hash_with_kimchi(S.PREFIX_PROTOCOL_STATE, [5, S.hash_with_kimchi(S.PREFIX_PROTOCOL_STATE_BODY, [], pp)], pp)
     assert oracle.le_to_int(h2[1]) == S.hash_with_kimchi(S.PREFIX_PROTOCOL_STATE, [6, S.hash_with_kimchi(S.PREFIX_PROTOCOL_STATE_BODY, [9], pp)], pp)
-    # 4-lane form: 8200 records (the 21 above, tiled)
+    # 3-lane form: 8200 records (the 21 above, tiled)
     reps = 8200 // len(states) + 1
     big = ctx.protocol_state_hash_batch(np.tile(recs, (reps, 1)), np.tile(nf, reps))
     assert (big.reshape(reps, len(states), 32) == got[None]).all()
