@@ -35,6 +35,30 @@ func (c *Ctx) SrsCreate(curve int, depth uint32) error {
 	return nil
 }
 
+// SetStateDedup: the protocol-state leg of the context's Proof-of-State jobs hashes each distinct state of a job once (off by default; no result changes).
+func (c *Ctx) SetStateDedup(on bool) error {
+	v := C.int(0)
+	if on {
+		v = 1
+	}
+	if rc := C.mina_ctx_set_state_dedup(c.p, v); rc != 0 {
+		return lastError()
+	}
+	return nil
+}
+
+// StateDedupStats: states that went through a deduplicated leg, the distinct ones among them, fingerprint collisions (since the mode was last switched on).
+func (c *Ctx) StateDedupStats() (states, distinct, collisions uint64, err error) {
+	var a, b, d C.uint64_t
+	if rc := C.mina_ctx_state_dedup_stats(c.p, &a, &b, &d); rc != 0 {
+		return 0, 0, 0, lastError()
+	}
+	return uint64(a), uint64(b), uint64(d), nil
+}
+
+// ConfigureDedupStates: the process-wide boundary (VerifyMinaState and its batch form) deduplicates the protocol states of each chunk; other flags are kept by the caller.
+func ConfigureDedupStates(otherFlags uint32) { C.mina_verify_configure(C.uint32_t(otherFlags) | C.MINA_VERIFY_DEDUP_STATES) }
+
 // AccumulatorCheckMulti: one deterministic verdict per proof (len(sg)/64 proofs).
 func (c *Ctx) AccumulatorCheckMulti(curve int, k uint32, pre, sg []byte) ([]bool, error) {
 	n := len(sg) / 64

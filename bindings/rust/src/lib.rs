@@ -35,6 +35,10 @@ impl Ctx {
         check(unsafe { mina_accumulator_check_multi(self.0, curve, k, n, prechallenges.as_ptr(), sg.as_ptr(), v.as_mut_ptr()) })?;
         Ok(v.into_iter().map(|b| b != 0).collect())
     }
+    /// The protocol-state leg of this context's Proof-of-State jobs hashes each distinct state of a job once (off by default; no result changes).
+    pub fn set_state_dedup(&mut self, on: bool) -> Result<(), MinaError> {
+        check(unsafe { mina_ctx_set_state_dedup(self.0, on as i32) })
+    }
     /// `SRS::verify` on a batch; the two RNG draws of upstream are explicit arguments.  Any failure is `false`.
     pub fn ipa_batch_check(&mut self, curve: i32, openings: &[mina_ipa_opening], rand_base: &[u8; 32], sg_rand_base: &[u8; 32]) -> bool {
         let mut v = 0u8;

@@ -348,6 +348,30 @@ int mina_protocol_state_pack(const uint8_t *bytes, size_t len, int encoding, uin
 /* n records -> n state hashes (and, if body_hashes_out != NULL, the n body hashes) on the GPU */
 int mina_protocol_state_hash_batch(mina_ctx *ctx, size_t n, const uint8_t *records /* n*MINA_PSTATE_SLOTS*32 */,
                                    const uint32_t *n_body_fields /* n */, uint8_t *hashes_out /* n*32 */, uint8_t *body_hashes_out /* n*32 or NULL */);
+/* ---- deduplicated protocol states (opt-in; changes NO result) -------------------------------------------------------
+ * The proofs an operator submits within minutes share most of their 16 chain states and usually the bridge tip state.  Records i and j are THE SAME iff their
+ * n_body_fields agree (clamped to MINA_PSTATE_SLOTS - 1, as the hash kernels clamp them) and their first 1 + n_body_fields slots are byte-identical; slots past
+ * that are ignored, as the hashes ignore them.  rep[i] is the SMALLEST index whose record is the same as record i.  With the mode on, Poseidon runs once per
+ * distinct record and every record takes its representative's hash: every hash, verdict and flag is bit-identical to the mode off, for every input.  It is not a
+ * probabilistic shortcut: a 128-bit fingerprint only chooses where a record looks in a table, and a record joins a class only after its used slots compared
+ * equal to the class owner's in full, so two different records never share a result whatever the fingerprint does.  Per call / per job, never across calls.
+ *
+ * Building block: device pointers, queued on the next pipeline lane, no host synchronisation.  d_records: n*MINA_PSTATE_SLOTS*32 bytes, 16-byte aligned;
+ * d_nfields: n u32; d_rep: n u32; d_counts: 2 u32 {n_distinct, n_collisions} -- n_collisions counts the fingerprint matches whose records differed.
+ * fingerprint_bits: 0 = the full fingerprint; 1..32 = cut it to that many bits (exists so that the collision path can be tested: rep and n_distinct are the
+ * same for every value); above 32: MINA_ERR_ARG.  n <= 2^22. */
+int mina_protocol_state_dedup_dev(mina_ctx *ctx, size_t n, const void *d_records, const void *d_nfields, void *d_rep, void *d_counts, uint32_t fingerprint_bits);
+/* mina_protocol_state_hash_batch with the distinct records hashed once; *n_distinct (may be NULL) receives their number */
+int mina_protocol_state_hash_batch_dedup(mina_ctx *ctx, size_t n, const uint8_t *records /* n*MINA_PSTATE_SLOTS*32 */, const uint32_t *n_body_fields /* n */,
+                                         uint8_t *hashes_out /* n*32 */, uint8_t *body_hashes_out /* n*32 or NULL */, size_t *n_distinct);
+/* Per context, default 0 (off: every code path, launch and result as without this call).  On: the protocol-state leg of mina_state_job_batch / _batch_dev /
+ * _fold_dev finds the identical records of the job, hashes each distinct one once and copies the hash to the records that share it.  Workspace per lane that
+ * runs such a leg: 8 B per state and a table of 16 B x the next power of two >= 2 x states.  The lane form of the hashes follows the number of
+ * records, not of distinct ones (that number never leaves the device).  Switching the mode on waits for the context and restarts the statistics. */
+int mina_ctx_set_state_dedup(mina_ctx *ctx, int on);
+/* Waits for the context; states that went through a deduplicated leg, the distinct ones among them, and fingerprint collisions, summed since the context was
+ * created or the mode was last switched on.  Any of the three pointers may be NULL. */
+int mina_ctx_state_dedup_stats(mina_ctx *ctx, uint64_t *states, uint64_t *distinct, uint64_t *collisions);
 /* serialized states in, state hashes out */
 int mina_protocol_state_hash_bytes(mina_ctx *ctx, int encoding, size_t n, const uint8_t *const *states, const size_t *lens,
                                    uint8_t *hashes_out /* n*32 */);
@@ -599,6 +623,8 @@ int mina_state_proof_split(const uint8_t *bytes, size_t len, size_t *proof_len, 
 #define MINA_VERIFY_ALLOW_SURROGATE 4u        /* verify although the installed Poseidon tables are the library's surrogate (mina_poseidon_params_name()
                                                   contains "UNPINNED"): hashes then agree with this repo's oracle, not with the Mina network.  Without the
                                                   flag every mina_verify_* verdict is `false` on such a context. */
+#define MINA_VERIFY_DEDUP_STATES 8u          /* the boundary's process-wide contexts run with mina_ctx_set_state_dedup on: a chunk's state hashes are not queued
+                                                  while the chunk is still being parsed; its whole state leg runs deduplicated, per chunk.  Verdicts are unchanged. */
 #include <stdbool.h>
 bool mina_verify_state(const uint8_t *proof, size_t proof_len, const uint8_t *pub_input, size_t pub_len);
 int mina_verify_state_batch(size_t n, const uint8_t *const *proofs, const size_t *proof_lens, const uint8_t *const *pub_inputs,

@@ -15,6 +15,7 @@
 #include "sponge.cuh"
 #include "lagrange.cuh"
 #include "wire_state.h"
+#include "state_dedup.cuh"
 
 namespace mb {
 
@@ -22,19 +23,12 @@ template <int F> __device__ __forceinline__ fe_t ld_fe(const uint32_t *p) { fe_t
 
 // `MinaHash(ProtocolState)`: body = H_{"MinaProtoStateBody"}(fields[1 .. 1+nf)); hash = H_{"MinaProtoState"}(fields[0], body).
 // One lane group (8 lanes, or a wave-packed triple for chip-filling batches) per state; record = MINA_PSTATE_SLOTS field elements, canonical words.
+// The sponge of one state, shared by pstate_hash_kernel (hash `sp` is that of record `sp`) and pstate_hash_uniq_kernel (of record uniq[sp]): `rec` / `nf` = the group's
+// record and its clamped field count; the `live && writer` lanes write hash `sp`.
 template <int F, int LANES>
-// LANES == 3: five waves per SIMD (96 VGPRs) as before the signed-digit forms, whose digits pin the low halves of register pairs (100 VGPRs unasked): the three values
-// the allocator parks in scratch are touched outside the round loops only (pinned from the code object: tests/test_code_object.py::test_dominant_kernel_round_loops)
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LANES == 3 ? 5 : 1, LANES == 3 ? 5 : 8)))
-pstate_hash_kernel(uint32_t n, FieldK fk, const PoseidonParams *__restrict__ pp, const fe_t *__restrict__ salts /* [0..3) body, [3..6) state */,
-                   const uint32_t *__restrict__ records, const uint32_t *__restrict__ nfields, uint32_t *__restrict__ out_hash /* n*8 */,
-                   uint32_t *__restrict__ out_body /* n*8 or null */) {
-    bool writer;
-    const uint32_t sp = coop_sponge_index<LANES>(writer), e = coop_elem<LANES>();
-    const bool live = sp < n;
-    const uint32_t idx = live ? sp : 0;                            // dead groups shadow state 0 (whole waves run the cross-lane moves)
-    const uint32_t *rec = records + (size_t)idx * MINA_PSTATE_SLOTS * 8;
-    uint32_t nf = nfields[idx]; if (nf > MINA_PSTATE_SLOTS - 1) nf = MINA_PSTATE_SLOTS - 1;
+__device__ __forceinline__ void pstate_sponge(const bool live, const bool writer, const uint32_t e, const uint32_t sp, const uint32_t *__restrict__ rec, const uint32_t nf,
+                                              const FieldK &fk, const PoseidonParams *__restrict__ pp, const fe_t *__restrict__ salts, uint32_t *__restrict__ out_hash,
+                                              uint32_t *__restrict__ out_body) {
 #if defined(__HIP_DEVICE_COMPILE__)
     if constexpr (LANES == 3) {
         // The chip-filling form keeps the state in the 29-bit form (x 2^261, lazily reduced) from the first absorb to the last squeeze: a field enters by ONE signed-digit
@@ -92,21 +86,52 @@ pstate_hash_kernel(uint32_t n, FieldK fk, const PoseidonParams *__restrict__ pp,
     }
 }
 
+template <int F, int LANES>
+// LANES == 3: five waves per SIMD (96 VGPRs) as before the signed-digit forms, whose digits pin the low halves of register pairs (100 VGPRs unasked): the three values
+// the allocator parks in scratch are touched outside the round loops only (pinned from the code object: tests/test_code_object.py::test_dominant_kernel_round_loops)
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LANES == 3 ? 5 : 1, LANES == 3 ? 5 : 8)))
+pstate_hash_kernel(uint32_t n, FieldK fk, const PoseidonParams *__restrict__ pp, const fe_t *__restrict__ salts /* [0..3) body, [3..6) state */,
+                   const uint32_t *__restrict__ records, const uint32_t *__restrict__ nfields, uint32_t *__restrict__ out_hash /* n*8 */,
+                   uint32_t *__restrict__ out_body /* n*8 or null */) {
+    bool writer;
+    const uint32_t sp = coop_sponge_index<LANES>(writer), e = coop_elem<LANES>();
+    const bool live = sp < n;
+    const uint32_t idx = live ? sp : 0;                            // dead groups shadow state 0 (whole waves run the cross-lane moves)
+    const uint32_t *rec = records + (size_t)idx * MINA_PSTATE_SLOTS * 8;
+    uint32_t nf = nfields[idx]; if (nf > MINA_PSTATE_SLOTS - 1) nf = MINA_PSTATE_SLOTS - 1;
+    pstate_sponge<F, LANES>(live, writer, e, sp, rec, nf, fk, pp, salts, out_hash, out_body);
+}
+
+// The deduplicated state leg (state_dedup.cuh; pstate_hash_dedup_dev): states [lo, lo + cnt) of the DISTINCT records, hash `sp` = that of record uniq[sp].  The number
+// of distinct records `*m` is known on the device only: the grid covers the upper bound, a workgroup whose first state is past `*m` returns at once.
+template <int F, int LANES>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(LANES == 3 ? 5 : 1, LANES == 3 ? 5 : 8)))
+pstate_hash_uniq_kernel(uint32_t lo, uint32_t cnt, const uint32_t *__restrict__ m, const uint32_t *__restrict__ uniq, FieldK fk, const PoseidonParams *__restrict__ pp,
+                        const fe_t *__restrict__ salts, const uint32_t *__restrict__ records, const uint32_t *__restrict__ nfields, uint32_t *__restrict__ out_hash /* by position in uniq */,
+                        uint32_t *__restrict__ out_body /* likewise, or null */) {
+    const uint32_t end = min(lo + cnt, *m);
+    if (lo + blockIdx.x * (LANES == 3 ? (blockDim.x >> 6) * 21u : blockDim.x / LANES) >= end) return;
+    bool writer;
+    const uint32_t sp = lo + coop_sponge_index<LANES>(writer), e = coop_elem<LANES>();
+    const bool live = sp < end;
+    const uint32_t idx = uniq[live ? sp : lo];                     // dead groups shadow the piece's first state (whole waves run the cross-lane moves)
+    const uint32_t *rec = records + (size_t)idx * MINA_PSTATE_SLOTS * 8;
+    uint32_t nf = nfields[idx]; if (nf > MINA_PSTATE_SLOTS - 1) nf = MINA_PSTATE_SLOTS - 1;
+    asm volatile("" : "+v"(rec));                                  // from here on the compiler knows the address only, not the index it came from
+    const uint32_t at = (uint32_t)((size_t)(rec - records) / (MINA_PSTATE_SLOTS * 8));
+    pstate_sponge<F, LANES>(live, writer, e, at, rec, nf, fk, pp, salts, out_hash, out_body);
+}
+
 // The same hashes, ONE lane per state (64 per wave) -- the largest batches (pstate_hash_dev).  The whole sponge state lives on its lane in the 29-bit form from the first
 // absorb to the last squeeze, as in the 3-lane form; the rounds use the diagonal-normalised rows (sponge.cuh poseidon_rounds_one): no cross-lane move, the row
 // constants in SGPRs: 2103 multiply-accumulates per sponge-round in the build's code object (2106 written: the first product of a column starts its accumulator) against
 // 2322.  Five waves per SIMD (91 VGPRs; amdgpu_waves_per_eu caps them at 96): the three S-box chains of a lane hide each other's latency.
 static constexpr uint32_t PSTATE_HASH1_WAVES = 5;
+// the sponge of one lane's state, shared by pstate_hash1_kernel and pstate_hash1_uniq_kernel: hash `sp` from record `rec` with `nf` (clamped) body fields
 template <int F>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PSTATE_HASH1_WAVES, PSTATE_HASH1_WAVES)))
-pstate_hash1_kernel(uint32_t n, const PoseidonParams *__restrict__ pp, const fe_t *__restrict__ salts /* [0..3) body, [3..6) state */,
-                    const uint32_t *__restrict__ records, const uint32_t *__restrict__ nfields, uint32_t *__restrict__ out_hash /* n*8 */,
-                    uint32_t *__restrict__ out_body /* n*8 or null */) {
+__device__ __forceinline__ void pstate_sponge1(const uint32_t sp, const uint32_t *__restrict__ rec, const uint32_t nf, const PoseidonParams *__restrict__ pp,
+                                               const fe_t *__restrict__ salts, uint32_t *__restrict__ out_hash, uint32_t *__restrict__ out_body) {
 #if defined(__HIP_DEVICE_COMPILE__)
-    const uint32_t sp = blockIdx.x * blockDim.x + threadIdx.x;
-    if (sp >= n) return;                                             // nothing crosses lanes: a dead lane just leaves
-    const uint32_t *rec = records + (size_t)sp * MINA_PSTATE_SLOTS * 8;
-    uint32_t nf = nfields[sp]; if (nf > MINA_PSTATE_SLOTS - 1) nf = MINA_PSTATE_SLOTS - 1;
     const PoseidonParams29 *__restrict__ q = pparams29_of(pp);
     const PoseidonRows1 *__restrict__ q1 = prows1_of(pp);
     auto field29 = [&](const uint32_t *w) { return fe29_mul_sg<F>(fe29_from_words(ld_fe<F>(w)), q->absorb); };   // (words)(2^522) / 2^261 = x 2^261
@@ -130,8 +155,32 @@ pstate_hash1_kernel(uint32_t n, const PoseidonParams *__restrict__ pp, const fe_
     const fe_t w = fe_from_mont<F>(fe_cond_sub_p<F>(fe29_to_words(fe29_mul_asm<F>(y[0], q->leave)))); for (int i = 0; i < 8; ++i) out_hash[(size_t)sp * 8 + i] = w.v[i];
     if (out_body) { const fe_t bw = fe_from_mont<F>(fe_cond_sub_p<F>(fe29_to_words(fe29_mul_asm<F>(x[0], q->leave)))); for (int i = 0; i < 8; ++i) out_body[(size_t)sp * 8 + i] = bw.v[i]; }
 #else
-    (void)n; (void)pp; (void)salts; (void)records; (void)nfields; (void)out_hash; (void)out_body;
+    (void)sp; (void)rec; (void)nf; (void)pp; (void)salts; (void)out_hash; (void)out_body;
 #endif
+}
+template <int F>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PSTATE_HASH1_WAVES, PSTATE_HASH1_WAVES)))
+pstate_hash1_kernel(uint32_t n, const PoseidonParams *__restrict__ pp, const fe_t *__restrict__ salts /* [0..3) body, [3..6) state */,
+                    const uint32_t *__restrict__ records, const uint32_t *__restrict__ nfields, uint32_t *__restrict__ out_hash /* n*8 */,
+                    uint32_t *__restrict__ out_body /* n*8 or null */) {
+    const uint32_t sp = blockIdx.x * blockDim.x + threadIdx.x;
+    if (sp >= n) return;                                             // nothing crosses lanes: a dead lane just leaves
+    const uint32_t *rec = records + (size_t)sp * MINA_PSTATE_SLOTS * 8;
+    uint32_t nf = nfields[sp]; if (nf > MINA_PSTATE_SLOTS - 1) nf = MINA_PSTATE_SLOTS - 1;
+    pstate_sponge1<F>(sp, rec, nf, pp, salts, out_hash, out_body);
+}
+// ... of the distinct records only (see pstate_hash_uniq_kernel): a lane past `*m` leaves, so a workgroup whose first state is past it returns at once
+template <int F>
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PSTATE_HASH1_WAVES, PSTATE_HASH1_WAVES)))
+pstate_hash1_uniq_kernel(uint32_t lo, uint32_t cnt, const uint32_t *__restrict__ m, const uint32_t *__restrict__ uniq, const PoseidonParams *__restrict__ pp,
+                         const fe_t *__restrict__ salts, const uint32_t *__restrict__ records, const uint32_t *__restrict__ nfields, uint32_t *__restrict__ out_hash,
+                         uint32_t *__restrict__ out_body) {
+    const uint32_t sp = lo + blockIdx.x * blockDim.x + threadIdx.x;
+    if (sp >= min(lo + cnt, *m)) return;
+    const uint32_t idx = uniq[sp];
+    const uint32_t *rec = records + (size_t)idx * MINA_PSTATE_SLOTS * 8;
+    uint32_t nf = nfields[idx]; if (nf > MINA_PSTATE_SLOTS - 1) nf = MINA_PSTATE_SLOTS - 1;
+    pstate_sponge1<F>(idx, rec, nf, pp, salts, out_hash, out_body);                          // the hash goes to the record's own place
 }
 
 // salts of the hash prefixes: state after absorbing the prefix element into the zero state and permuting (3 elements each)
@@ -243,6 +292,119 @@ static int pstate_hash_dev(mina_ctx *c, size_t n, size_t leg, const uint32_t *d_
         HIPC(hipGetLastError());
         return MINA_OK;
     });
+}
+
+// ------------------------------------------------------------------------------------------------ the deduplicated state leg (state_dedup.cuh)
+// rep[] and {n_distinct, n_collisions} of `n` records, queued on the current lane with its table; with `d_uniq` the ascending list of the representatives as well.
+// `totals`: the context's running {distinct, collisions}, or null.
+static int pstate_dedup_group_dev(mina_ctx *c, size_t n, const uint32_t *d_records, const uint32_t *d_nfields, uint32_t fingerprint_bits, uint32_t *d_rep, uint32_t *d_counts,
+                                  uint32_t *d_uniq, unsigned long long *totals) {
+    Lane &L = *c->L;
+    if ((uintptr_t)d_records & 15u) return fail(MINA_ERR_ARG, "deduplication reads the records 16 bytes at a time: the pointer must be 16-byte aligned");
+    size_t slots = 64; while (slots < 2 * n) slots <<= 1;              // at most half full
+    const uint32_t ntiles = cdiv(n, mb::DEDUP_SCAN_TILE);
+    int rc;
+    if ((rc = L.dd_table.ensure(slots * sizeof(mb::DedupSlot))) || (rc = L.dd_counts.ensure((4 + (size_t)ntiles) * 4))) return rc;
+    uint32_t *tiles = L.dd_counts.as<uint32_t>() + 4;
+    HIPC(hipMemsetAsync(L.dd_table.p, 0xff, slots * sizeof(mb::DedupSlot), L.stream));     // word = empty, min = 2^32 - 1
+    HIPC(hipMemsetAsync(d_counts, 0, 8, L.stream));
+    mb::pstate_dedup_group_kernel<<<cdiv(n * mb::DEDUP_SUB, 256), 256, 0, L.stream>>>((uint32_t)n, (uint32_t)(slots - 1), fingerprint_bits, d_records, d_nfields,
+                                                                                      L.dd_table.as<mb::DedupSlot>(), d_rep, d_counts);
+    mb::pstate_dedup_rep_kernel<<<ntiles, mb::DEDUP_SCAN_BLOCK, 0, L.stream>>>((uint32_t)n, L.dd_table.as<mb::DedupSlot>(), d_rep, tiles);
+    mb::pstate_dedup_scan_kernel<<<1, mb::DEDUP_SCAN_BLOCK, 0, L.stream>>>(ntiles, tiles, d_counts, totals);
+    if (d_uniq) mb::pstate_dedup_compact_kernel<<<ntiles, mb::DEDUP_SCAN_BLOCK, 0, L.stream>>>((uint32_t)n, d_rep, tiles, d_uniq);
+    HIPC(hipGetLastError());
+    return MINA_OK;
+}
+
+// pstate_hash_dev with every distinct record hashed once: group, hash the representatives through uniq[] in the lane form pstate_hash_dev would take for `n` of `leg`
+// (the distinct count is known on the device only: the grids cover `n`, workgroups past the count return at once) straight into the representatives' places of
+// `d_hashes`, copy every other record's hash from its representative's.  Everything on the current lane's stream, in its dd_* buffers; no host synchronisation.
+// `d_hashes` (and `d_bodies`) must be 16-byte aligned.
+static int pstate_hash_dedup_dev(mina_ctx *c, size_t n, size_t leg, const uint32_t *d_records, const uint32_t *d_nfields, uint32_t *d_hashes, uint32_t *d_bodies, bool count) {
+    const PoseidonParams *pp = c->pparams[FIELD_FP].as<PoseidonParams>();
+    const fe_t *salts = c->state_salts.as<fe_t>();
+    Lane &L = *c->L;
+    ProfScope ps_(c, PS_STATE_HASH);
+    int rc;
+    if ((rc = L.dd_rep.ensure(n * 4)) || (rc = L.dd_uniq.ensure(n * 4)) ||
+        (rc = L.dd_counts.ensure((4 + (size_t)cdiv(n, mb::DEDUP_SCAN_TILE)) * 4))) return rc;      // (its full size here: pstate_dedup_group_dev must not move the counters it is handed)
+    if ((rc = pstate_dedup_group_dev(c, n, d_records, d_nfields, 0, L.dd_rep.as<uint32_t>(), L.dd_counts.as<uint32_t>(), L.dd_uniq.as<uint32_t>(),
+                                     count ? c->dedup_totals.as<unsigned long long>() : nullptr))) return rc;
+    if (count) c->dedup_states += n;
+    const uint32_t *m = L.dd_counts.as<uint32_t>(), *uniq = L.dd_uniq.as<uint32_t>();
+    uint32_t *const uh = d_hashes, *const ub = d_bodies;
+    rc = with_lanes<1, 16, 8, 3>(pstate_hash_lanes(c, n, leg), [&](auto lanes) {
+        constexpr int LN = decltype(lanes)::value;
+        constexpr bool wide = LN == 1 || LN == 3;
+        std::optional<ProfScope> ps1_;
+        if (LN == 1) ps1_.emplace(c, PS_STATE_HASH1);
+        const size_t per = wide && c->hash_piece_waves ? hash_piece_states(c, leg) : n;      // pieces as in pstate_hash_dev; those past the distinct count are empty launches
+        const uint32_t lds = wide ? c->hash_lds_bytes : 0;
+        for (size_t lo = 0; lo < n; lo += per) {
+            const size_t cnt = std::min(per, n - lo);
+            if constexpr (LN == 1) mb::pstate_hash1_uniq_kernel<FIELD_FP><<<cdiv(cnt, 256), 256, lds, L.stream>>>((uint32_t)lo, (uint32_t)cnt, m, uniq, pp, salts, d_records, d_nfields, uh, ub);
+            else mb::pstate_hash_uniq_kernel<FIELD_FP, LN><<<cdiv(coop_threads<LN>(cnt), 256), 256, lds, L.stream>>>((uint32_t)lo, (uint32_t)cnt, m, uniq, c->fk[FIELD_FP], pp, salts, d_records, d_nfields, uh, ub);
+        }
+        HIPC(hipGetLastError());
+        return MINA_OK;
+    });
+    if (rc) return rc;
+    mb::pstate_dedup_scatter_kernel<<<cdiv(2 * n, 256), 256, 0, L.stream>>>((uint32_t)n, L.dd_rep.as<uint32_t>(), d_hashes, d_bodies);
+    HIPC(hipGetLastError());
+    return MINA_OK;
+}
+
+extern "C" int mina_ctx_set_state_dedup(mina_ctx *c, int on) {
+    if (!c) return fail(MINA_ERR_ARG, "null ctx");
+    HIPC(hipSetDevice(c->device));
+    return mb_ctx_state_dedup(c, on != 0);
+}
+extern "C" int mina_ctx_state_dedup_stats(mina_ctx *c, uint64_t *states, uint64_t *distinct, uint64_t *collisions) {
+    if (!c) return fail(MINA_ERR_ARG, "null ctx");
+    int rc = mina_ctx_synchronize(c);
+    if (rc) return rc;
+    unsigned long long t[2] = {0, 0};
+    if (c->dedup_totals.p) HIPC(hipMemcpy(t, c->dedup_totals.p, 16, hipMemcpyDeviceToHost));
+    if (states) *states = c->dedup_states;
+    if (distinct) *distinct = t[0];
+    if (collisions) *collisions = t[1];
+    return MINA_OK;
+}
+
+extern "C" int mina_protocol_state_dedup_dev(mina_ctx *c, size_t n, const void *d_records, const void *d_nfields, void *d_rep, void *d_counts, uint32_t fingerprint_bits) {
+    if (!c || !d_counts || (n && (!d_records || !d_nfields || !d_rep))) return fail(MINA_ERR_ARG, "null argument");
+    if (fingerprint_bits > 32) return fail(MINA_ERR_ARG, "fingerprint_bits must be 0 (the full fingerprint) or 1..32");
+    if (n > ((size_t)1 << mb::DEDUP_OWNER_BITS)) return fail(MINA_ERR_ARG, "n too large");
+    HIPC(hipSetDevice(c->device));
+    c->next_lane();
+    if (n == 0) { HIPC(hipMemsetAsync(d_counts, 0, 8, c->L->stream)); return MINA_OK; }
+    return pstate_dedup_group_dev(c, n, (const uint32_t *)d_records, (const uint32_t *)d_nfields, fingerprint_bits, (uint32_t *)d_rep, (uint32_t *)d_counts, nullptr, nullptr);
+}
+
+extern "C" int mina_protocol_state_hash_batch_dedup(mina_ctx *c, size_t n, const uint8_t *records, const uint32_t *n_body_fields, uint8_t *hashes_out,
+                                                    uint8_t *body_hashes_out, size_t *n_distinct) {
+    if (!c || (n && (!records || !n_body_fields || !hashes_out))) return fail(MINA_ERR_ARG, "null argument");
+    if (n_distinct) *n_distinct = 0;
+    if (n == 0) return MINA_OK;
+    if (n > (1u << 22)) return fail(MINA_ERR_ARG, "n too large");
+    for (size_t i = 0; i < n; ++i) if (n_body_fields[i] > MINA_PSTATE_SLOTS - 1) return fail(MINA_ERR_ARG, "n_body_fields exceeds the record");
+    HIPC(hipSetDevice(c->device));
+    c->use_lane0();
+    int rc;
+    if ((rc = ensure_state_salts(c))) return rc;
+    Lane &L = *c->L;
+    if ((rc = h2d(c, L.tmp_a, records, n * MINA_PSTATE_SLOTS * 32))) return rc;
+    if ((rc = h2d(c, L.tmp_b, n_body_fields, n * 4))) return rc;
+    if ((rc = L.tmp_c.ensure(n * 32))) return rc;
+    if ((rc = L.tmp_d.ensure(n * 32))) return rc;
+    if ((rc = pstate_hash_dedup_dev(c, n, n, L.tmp_a.as<uint32_t>(), L.tmp_b.as<uint32_t>(), L.tmp_c.as<uint32_t>(), body_hashes_out ? L.tmp_d.as<uint32_t>() : nullptr, false))) return rc;
+    if (body_hashes_out) HIPC(hipMemcpyAsync(body_hashes_out, L.tmp_d.p, n * 32, hipMemcpyDeviceToHost, L.stream));
+    uint32_t m = 0;
+    HIPC(hipMemcpyAsync(&m, L.dd_counts.p, 4, hipMemcpyDeviceToHost, L.stream));
+    if ((rc = d2h_sync(c, hashes_out, L.tmp_c, n * 32))) return rc;
+    if (n_distinct) *n_distinct = m;
+    return MINA_OK;
 }
 
 extern "C" int mina_protocol_state_hash_batch(mina_ctx *c, size_t n, const uint8_t *records, const uint32_t *n_body_fields, uint8_t *hashes_out,
@@ -434,6 +596,10 @@ int mb_state_jobs_on_lane(mina_ctx *c, const mina_state_jobs *j, uint32_t *d_ver
         if ((rc = S.st_hashes.ensure(ns * 32))) return rc;
         const size_t early = std::min(c->state_hashes_early, ns);      // already queued on this lane by mb_state_hashes_early
         c->state_hashes_early = 0;
+        // mina_ctx_set_state_dedup: the whole leg at once, each distinct record hashed once (a piece queued early could not know its duplicates in later pieces)
+        if (c->state_dedup && early == 0) {
+            if ((rc = pstate_hash_dedup_dev(c, ns, ns, (const uint32_t *)j->state_records, (const uint32_t *)j->state_nfields, S.st_hashes.as<uint32_t>(), nullptr, true))) return rc;
+        } else
         if (early < ns && (rc = pstate_hash_dev(c, ns - early, ns, (const uint32_t *)j->state_records + early * MINA_PSTATE_SLOTS * 8, (const uint32_t *)j->state_nfields + early,
                                                 S.st_hashes.as<uint32_t>() + early * 8, nullptr))) return rc;
         mb::pstate_chain_check_kernel<<<cdiv(B, 64), 64, 0, S.stream>>>((uint32_t)B, S.st_hashes.as<uint32_t>(), (const uint32_t *)j->expected_hashes,

@@ -788,13 +788,13 @@ int run_device_shape(Device &D, const CallIn &in, const std::vector<size_t> &idx
             const size_t first = piece ? (total % piece ? total % piece : piece) : 0;
             const size_t upto = (r + 1 == ch.nsub || !piece) ? ready : (ready < first ? 0 : first + (ready - first) / piece * piece);
             int rc = MINA_OK;
-            if (upto > ch.hashed)
+            if (upto > ch.hashed && !(flags & MINA_VERIFY_DEDUP_STATES))      // deduplicated: the whole state leg runs in finish() (a piece cannot know its duplicates in later pieces)
                 rc = mb_state_hashes_early(c, ch.LS ? ch.LS : &L, ch.n * MINA_STATES_PER_PROOF, ch.hashed, upto - ch.hashed,
                                            (const uint32_t *)lay.at(dbase, S_REC, 0), (const uint32_t *)lay.at(dbase, S_NF, 0), S.rec_ev[r]);
             c->hash_piece_waves = 0;
             c->use_lane0();
             if (rc) return rc;
-            ch.hashed = std::max(ch.hashed, upto);
+            if (!(flags & MINA_VERIFY_DEDUP_STATES)) ch.hashed = std::max(ch.hashed, upto);
         }
         return MINA_OK;
     };
@@ -814,6 +814,7 @@ int run_device_shape(Device &D, const CallIn &in, const std::vector<size_t> &idx
         JobStructs js; make_jobs(sh, lay, dbase, ch.n, true, true, true, js);
         uint32_t *dv = (uint32_t *)(dbase + lay.out_off()), *df = dv + ch.n, *ds = df + 4;
         c->state_hashes_early = ch.hashed;
+        { const bool want = (flags & MINA_VERIFY_DEDUP_STATES) != 0; int drc; if (want != c->state_dedup && (drc = mb_ctx_state_dedup(c, want))) return drc; }      // MINA_VERIFY_DEDUP_STATES: per chunk, under the device's lock
         int rc = mb_state_jobs_on_lane(c, &js.j, dv, df, ch.LI, ch.LA, ds, ch.LS, MB_JOB_FINISH, &ch.carry);
         c->state_hashes_early = 0;
         c->hash_piece_waves = 0;

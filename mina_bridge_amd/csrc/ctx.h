@@ -112,6 +112,7 @@ struct Lane {
     DevBuf bp_ltab, bp_htab, bp_partial, bp_ldig, bp_hdig, bp_colsum;
     DevBuf ipa_chals, ipa_folded, ipa_xyzz_a, ipa_xyzz_b, ipa_points, ipa_scalars, ipa_sigma, ipa_in_a, ipa_in_b, ipa_in_c, ipa_verdict, ipa_xfer, ipa_shared, ipa_shared_off, acc_rho_scaled /* exchange variant: the caller's acc_rho times the shard's own CSPRNG scalar */;
     DevBuf st_ok, st_hashes, st_pub_xyzz, st_pubcomm, st_flags, st_in, st_verdicts;   // Proof-of-State job (api_state.hip)
+    DevBuf dd_rep, dd_uniq, dd_table, dd_counts;  // its deduplicated state leg (state_dedup.cuh): 4 B x n each, the table 16 B x the power of two >= 2 n, counters + one word per 1024 states
     DevBuf kc_state, kc_pos, kc_cip, kc_pts, kc_v, kc_u, kc_comms, kc_xfer, kc_pch, pk_xe, pk_pub, pk_ok;                  // kimchi to_batch output rows (api_kimchi.hip)
     void release_all() {
         MsmWorkspace &w = ws;
@@ -120,6 +121,7 @@ struct Lane {
                          &bp_ltab, &bp_htab, &bp_partial, &bp_ldig, &bp_hdig, &bp_colsum, &ipa_chals, &ipa_folded, &ipa_xyzz_a, &ipa_xyzz_b, &ipa_points, &ipa_scalars,
                          &ipa_sigma, &ipa_in_a, &ipa_in_b, &ipa_in_c, &ipa_verdict, &ipa_xfer, &ipa_shared, &ipa_shared_off, &acc_rho_scaled,
                          &st_ok, &st_hashes, &st_pub_xyzz, &st_pubcomm, &st_flags, &st_in, &st_verdicts,
+                         &dd_rep, &dd_uniq, &dd_table, &dd_counts,
                          &kc_state, &kc_pos, &kc_cip, &kc_pts, &kc_v, &kc_u, &kc_comms, &kc_xfer, &kc_pch, &pk_xe, &pk_pub, &pk_ok};
         for (DevBuf *b : all) b->release();
         host_stage.release();
@@ -158,6 +160,8 @@ struct mina_ctx {
     uint32_t hash_lds_bytes = 0;     // > 0: dynamic LDS a state-hash workgroup reserves (3-lane or single-lane form), to cap its waves per SIMD beside the other legs of a forked job (mina_verify_tuning.dev_hash_lds_kb;
                                      // by default only a lone job sets it, and a lone job hashes in the 3-lane form: hash_one_lane)
     bool acc_first = false;          // forked device-resident job whose accumulator leg shares the hashes' stream: queue it AHEAD of them (mina_verify_tuning.dev_acc_lane = 2)
+    bool state_dedup = false;        // the protocol-state leg of a job hashes each distinct record once (mina_ctx_set_state_dedup; api_state.hip pstate_hash_dedup_dev)
+    DevBuf dedup_totals; uint64_t dedup_states = 0;   // mina_ctx_state_dedup_stats: {distinct, collisions} summed on the device by the legs' scan kernels, the states counted as they are queued
     uint32_t dev_fork_made = 0;      // the dev_fork value the helper lanes' streams were created under (streams keep their mask / priority for life)
     // SURVEY.md 8e.2 (one exchange step over several GPUs): while set, the folded checks of a job do NOT run their fixed-base MSM and comparison -- they hand out
     // this shard's folded scalar vector and the 17-word record of its variable-base partial sum instead (mina_state_job_fold_dev); device pointers
@@ -165,6 +169,20 @@ struct mina_ctx {
     void use_lane0() { L = &lanes[0]; }
     void next_lane() { L = pinned >= 0 ? &lanes[pinned] : &lanes[rr++ % (unsigned)nlanes]; }
 };
+
+// mina_ctx_set_state_dedup without the argument checks (the boundary switches its contexts under their lock: api_verify.hip finish()).  The statistics start
+// again whenever the mode goes from off to on; that waits for the pipeline lanes.
+static inline int mb_ctx_state_dedup(mina_ctx *c, bool on) {
+    if (on && !c->state_dedup) {
+        for (int i = 0; i < c->nlanes; ++i) if (c->lanes[i].stream && hipStreamSynchronize(c->lanes[i].stream) != hipSuccess) return MINA_ERR_HIP;
+        int rc = c->dedup_totals.ensure(16);
+        if (rc) return rc;
+        if (hipMemsetAsync(c->dedup_totals.p, 0, 16, c->lanes[0].stream) != hipSuccess || hipStreamSynchronize(c->lanes[0].stream) != hipSuccess) return MINA_ERR_HIP;
+        c->dedup_states = 0;
+    }
+    c->state_dedup = on;
+    return MINA_OK;
+}
 
 // lane-cooperative Poseidon: batches of at most this many sponges use 8 lanes each (shortest dependency chain, 2.6x the issue
 // slots), larger ones the wave-packed 3-lane form (21 sponges per wave); both run their rounds on the 29-bit limbs (fp29.cuh).

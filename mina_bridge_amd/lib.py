@@ -35,6 +35,7 @@ EXPORTS = [
     "mina_accumulator_check_batch", "mina_accumulator_check_dev", "mina_accumulator_check_multi_dev", "mina_accumulator_check_multi", "mina_ipa_batch_check",
     "mina_consensus_project_window", "mina_consensus_relative_min_window_density", "mina_consensus_is_short_range",
     "mina_protocol_state_pack", "mina_protocol_state_hash_batch", "mina_protocol_state_hash_bytes",
+    "mina_protocol_state_dedup_dev", "mina_protocol_state_hash_batch_dedup", "mina_ctx_set_state_dedup", "mina_ctx_state_dedup_stats",
     "mina_state_jobs_prepare", "mina_state_job_batch_dev", "mina_state_job_batch", "mina_state_job_fold_dev",
     "mina_challenge_to_field_dev", "mina_field_sum_rows_dev", "mina_msm_srs_range_dev", "mina_msm_dev", "mina_points_sum_dev", "mina_point_records_equal_dev",
     "mina_step_index_install", "mina_step_index_load_json", "mina_polish_tokens_from_json", "mina_verifier_index_load_json", "mina_pickles_public_input",
@@ -234,6 +235,7 @@ class KimchiBatchOut(ctypes.Structure):
 
 CHECK_FORMAT, CHECK_LEDGER, CHECK_CHAIN, CHECK_CONSENSUS, CHECK_ACCUMULATOR, CHECK_KIMCHI, CHECK_ACCOUNT_ABI, CHECK_MERKLE = 1, 2, 4, 8, 16, 32, 64, 128
 VERIFY_ALLOW_MISSING_KIMCHI, VERIFY_ALLOW_UNBOUND_STATEMENT, VERIFY_ALLOW_SURROGATE = 1, 2, 4
+VERIFY_DEDUP_STATES = 8   # the boundary hashes each distinct protocol state of a chunk once (MinaContext.set_state_dedup on its contexts); verdicts unchanged
 
 
 def _bytes_arg(b):
@@ -953,6 +955,34 @@ class MinaContext:
         self._ck(self._lib.mina_protocol_state_hash_batch(self._h, ctypes.c_size_t(n), _p(rec), nf.ctypes.data_as(ctypes.c_void_p), _p(out), _p(body)),
                  "mina_protocol_state_hash_batch")
         return (out, body) if want_body else out
+
+    def protocol_state_hash_batch_dedup(self, records, nfields, want_body: bool = False):
+        """`protocol_state_hash_batch` with every distinct record hashed once: (hashes[, body hashes], n_distinct); bit-identical hashes"""
+        rec = _u8(records); nf = np.ascontiguousarray(nfields, dtype=np.uint32)
+        n = nf.size
+        assert rec.size == n * PSTATE_SLOTS * 32
+        out = np.empty((n, 32), np.uint8); body = np.empty((n, 32), np.uint8) if want_body else None
+        m = ctypes.c_size_t(0)
+        self._ck(self._lib.mina_protocol_state_hash_batch_dedup(self._h, ctypes.c_size_t(n), _p(rec), nf.ctypes.data_as(ctypes.c_void_p), _p(out), _p(body), ctypes.byref(m)),
+                 "mina_protocol_state_hash_batch_dedup")
+        return (out, body, int(m.value)) if want_body else (out, int(m.value))
+
+    def protocol_state_dedup_dev(self, n: int, d_records: int, d_nfields: int, d_rep: int, d_counts: int, fingerprint_bits: int = 0):
+        """rep[i] = the smallest index whose record is the same as record i (n u32 at d_rep) and {n_distinct, n_collisions} (2 u32 at d_counts); device pointers,
+        queued on the next pipeline lane.  fingerprint_bits 1..32 cuts the fingerprint (the collision path under test): the results do not depend on it"""
+        self._ck(self._lib.mina_protocol_state_dedup_dev(self._h, ctypes.c_size_t(n), ctypes.c_void_p(d_records), ctypes.c_void_p(d_nfields), ctypes.c_void_p(d_rep),
+                                                         ctypes.c_void_p(d_counts), ctypes.c_uint32(fingerprint_bits)), "mina_protocol_state_dedup_dev")
+
+    def set_state_dedup(self, on: bool = True):
+        """the protocol-state leg of state_job_batch / _batch_dev / _fold_dev hashes each distinct record of a job once (default off; no result changes)"""
+        self._ck(self._lib.mina_ctx_set_state_dedup(self._h, 1 if on else 0), "mina_ctx_set_state_dedup")
+
+    def state_dedup_stats(self):
+        """(states, distinct, collisions) of the deduplicated legs since the mode was last switched on; waits for the context"""
+        from collections import namedtuple
+        a, b, c_ = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self._ck(self._lib.mina_ctx_state_dedup_stats(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c_)), "mina_ctx_state_dedup_stats")
+        return namedtuple("StateDedupStats", "states distinct collisions")(int(a.value), int(b.value), int(c_.value))
 
     def protocol_state_hash_bytes(self, states: list, encoding: int = ENC_BINPROT) -> np.ndarray:
         n = len(states)
