@@ -352,14 +352,14 @@ __global__ void scale_words_kernel(uint32_t n, FieldK fk, const uint32_t *__rest
 }
 
 int mb_accumulator_check_dev(mina_ctx *c, int curve, uint32_t k, size_t batch, const uint32_t *d_prechal,
-                                 const uint32_t *d_sg_words, const uint32_t *d_rho, uint32_t *d_verdict) {
+                                 const uint32_t *d_sg_words, const uint32_t *d_rho, uint32_t *d_verdict, const FoldExport *fx) {
     SrsState &s = c->srs[curve];
     if (s.depth == 0) return fail(MINA_ERR_STATE, "SRS not loaded for this curve");
     if (k < 1 || k > 20 || ((size_t)1 << k) > s.depth) return fail(MINA_ERR_ARG, "2^k exceeds the SRS depth");
     const int FS = scalar_field_of(curve), FB = base_field_of(curve);
     const uint32_t n = 1u << k;
     int rc;
-    if (c->fold_export && batch > 1) {
+    if (fx && batch > 1) {
         // The exchange variant ADDS the shards' partial sums, so no proof of any shard may carry a coefficient an adversary can predict: the opening leg draws its
         // own powers (pow_first), and until round 5 this leg trusted the caller's acc_rho (a caller following upstream's rho_0 = 1, or fixed test randomisers,
         // re-opened the +t / -t cancellation between shards).  Now every acc_rho[b] is multiplied by ONE scalar this call draws from the OS CSPRNG:
@@ -383,13 +383,13 @@ int mb_accumulator_check_dev(mina_ctx *c, int curve, uint32_t k, size_t batch, c
         DISPATCH_FIELD(FS, { challenge_to_field_kernel<F_><<<cdiv(batch * k, 64), 64, 0, c->L->stream>>>((uint32_t)(batch * k), c->fk[F_], d_prechal, c->L->ipa_chals.as<uint32_t>()); });
         if ((rc = mb_bpoly_fold(c, FS, k, batch, c->L->ipa_chals.as<uint32_t>(), d_rho, c->L->ipa_folded.as<uint32_t>()))) return rc;
     }
-    if (c->fold_export && batch > 1) {       // the exchange variant over several GPUs: the caller folds the shards' vectors and runs the MSM over its slice of the bases
-        HIPC(hipMemcpyAsync(c->fold_export->acc_scalars, c->L->ipa_folded.p, (size_t)n * 32, hipMemcpyDeviceToDevice, c->L->stream));
+    if (fx && batch > 1) {       // the exchange variant over several GPUs: the caller folds the shards' vectors and runs the MSM over its slice of the bases
+        HIPC(hipMemcpyAsync(fx->acc_scalars, c->L->ipa_folded.p, (size_t)n * 32, hipMemcpyDeviceToDevice, c->L->stream));
         if ((rc = c->L->ipa_points.ensure(batch * sizeof(affine_t)))) return rc;
         if ((rc = c->L->ipa_sigma.ensure(4))) return rc;
         HIPC(hipMemsetAsync(c->L->ipa_sigma.p, 0, 4, c->L->stream));
         DISPATCH_FIELD(FB, { points_to_mont_checked_kernel<F_><<<cdiv(batch, 256), 256, 0, c->L->stream>>>((uint32_t)batch, d_sg_words, c->fk[F_], c->L->ipa_points.as<affine_t>(), c->L->ipa_sigma.as<uint32_t>()); });
-        if ((rc = mb_msm_variable(c, curve, (uint32_t)batch, d_rho, c->L->ipa_points.p, c->fold_export->acc_point, nullptr))) return rc;
+        if ((rc = mb_msm_variable(c, curve, (uint32_t)batch, d_rho, c->L->ipa_points.p, fx->acc_point, nullptr))) return rc;
         fold_export_flag_kernel<<<1, 64, 0, c->L->stream>>>(c->L->ipa_sigma.as<uint32_t>(), d_verdict);      // verdict word = "no malformed commitment in this shard"
         HIPC(hipGetLastError());
         return MINA_OK;
@@ -506,12 +506,12 @@ extern "C" int mina_accumulator_check_multi(mina_ctx *c, int curve, uint32_t k, 
 // ------------------------------------------------------------------------------------------------
 // a8: combined opening check, inputs resident in HBM (structure-of-arrays, see IpaDevIn).  Queued on the current lane, no host
 // synchronisation: d_verdict[0] = 1 iff the folded check holds, d_verdict[1] = malformed-input flag.
-int mb_ipa_batch_check_dev(mina_ctx *c, int curve, mb::IpaShape sh, const mb::IpaDevIn &in, uint32_t *d_verdict) {
+int mb_ipa_batch_check_dev(mina_ctx *c, int curve, mb::IpaShape sh, const mb::IpaDevIn &in, uint32_t *d_verdict, const FoldExport *fx) {
     SrsState &s = c->srs[curve];
     const int FB = base_field_of(curve), FS = scalar_field_of(curve);
     const size_t batch = sh.batch; const uint32_t k = sh.k;
     int rc;
-    if (c->fold_export) sh.pow_first = 1;          // partial sums that the caller adds to other shards': no coefficient-1 proof (ctx.h IpaShape::pow_first)
+    if (fx) sh.pow_first = 1;          // partial sums that the caller adds to other shards': no coefficient-1 proof (ctx.h IpaShape::pow_first)
     if (sh.nshared && (sh.ncomms > 64 || sh.nshared > 64)) return fail(MINA_ERR_ARG, "shared entries need <= 64 commitments");
     const size_t npoints = batch * sh.per + sh.nshared;           // per-proof lists, then the batch-shared points once
     if ((rc = c->L->ipa_points.ensure(npoints * sizeof(affine_t)))) return rc;
@@ -562,9 +562,9 @@ int mb_ipa_batch_check_dev(mina_ctx *c, int curve, mb::IpaShape sh, const mb::Ip
     HIPC(hipGetLastError());
     if (sh.nshared) { DISPATCH_FIELD(FS, { mb::ipa_shared_tail_kernel<F_><<<sh.nshared, 256, 0, c->L->stream>>>(sh.batch, sh.nshared, sh.per, c->L->ipa_shared.as<uint32_t>(), c->L->ipa_scalars.as<uint32_t>()); }); }
     if ((rc = mb_bpoly_fold(c, FS, k, batch, c->L->ipa_chals.as<uint32_t>(), c->L->ipa_sigma.as<uint32_t>(), c->L->ipa_folded.as<uint32_t>()))) return rc;
-    if (c->fold_export) {                        // the exchange variant over several GPUs: scalars and the variable-base partial go to the caller
-        HIPC(hipMemcpyAsync(c->fold_export->ipa_scalars, c->L->ipa_folded.p, ((size_t)1 << k) * 32, hipMemcpyDeviceToDevice, c->L->stream));
-        if ((rc = mb_msm_variable(c, curve, (uint32_t)npoints, c->L->ipa_scalars.as<uint32_t>(), c->L->ipa_points.p, c->fold_export->ipa_point, nullptr))) return rc;
+    if (fx) {                        // the exchange variant over several GPUs: scalars and the variable-base partial go to the caller
+        HIPC(hipMemcpyAsync(fx->ipa_scalars, c->L->ipa_folded.p, ((size_t)1 << k) * 32, hipMemcpyDeviceToDevice, c->L->stream));
+        if ((rc = mb_msm_variable(c, curve, (uint32_t)npoints, c->L->ipa_scalars.as<uint32_t>(), c->L->ipa_points.p, fx->ipa_point, nullptr))) return rc;
         fold_export_flag_kernel<<<1, 64, 0, c->L->stream>>>(d_verdict + 1, d_verdict);     // [1] = malformed flag of the transcripts -> [0] = 1 unless malformed
         HIPC(hipGetLastError());
         return MINA_OK;

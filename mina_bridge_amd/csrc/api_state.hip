@@ -264,12 +264,15 @@ static int ensure_state_salts(mina_ctx *c) {
 
 int mb_ensure_state_salts(mina_ctx *c) { return ensure_state_salts(c); }
 
-// `n` states of a leg of `leg` states (a piece of it, or all of it): the form follows the leg (ctx.h hash_one_lane), so that callers that cut a leg into
-// pieces (hash_piece_states) and this function agree on it
-static int pstate_hash_dev(mina_ctx *c, size_t n, size_t leg, const uint32_t *d_records, const uint32_t *d_nfields, uint32_t *d_hashes, uint32_t *d_bodies) {
+// The launches of `n` state hashes of a leg of `leg` states on the current lane, in the lane form of the leg (ctx.h pstate_hash_lanes) and in the pieces and behind the
+// LDS reservation of `hl`.  Without `u`: records [0, n) -> hashes [0, n).  With it: the distinct records uniq[0 .. *m) of the `n`, each hash to its record's own place;
+// `*m` is known on the device only, so the grids cover `n` and the pieces past the distinct count are empty launches.
+struct UniqList { const uint32_t *m, *uniq; };
+static int pstate_hash_launch(mina_ctx *c, size_t n, size_t leg, HashLaunch hl, const uint32_t *d_records, const uint32_t *d_nfields, uint32_t *d_hashes, uint32_t *d_bodies,
+                              const UniqList *u) {
     const PoseidonParams *pp = c->pparams[FIELD_FP].as<PoseidonParams>();
     const fe_t *salts = c->state_salts.as<fe_t>();
-    ProfScope ps_(c, PS_STATE_HASH);
+    hipStream_t stream = c->L->stream;
     // below ~8 k states the chip is latency-bound: 8 lanes per state (shortest chain); above, wave-packed triples (63 of 64 lanes busy); with several
     // jobs in flight and HASH1_MIN_STATES between them, one lane per state (ctx.h pstate_hash_lanes)
     return with_lanes<1, 16, 8, 3>(pstate_hash_lanes(c, n, leg), [&](auto lanes) {
@@ -278,20 +281,33 @@ static int pstate_hash_dev(mina_ctx *c, size_t n, size_t leg, const uint32_t *d_
         std::optional<ProfScope> ps1_;
         if (LN == 1) ps1_.emplace(c, PS_STATE_HASH1);
         // A whole chip-filling launch would hold every wave slot its VGPRs allow (5 per SIMD in the 3-lane form) for most of its 20 ms, and the kernels of
-        // the other legs / chunks of a call (a few hundred waves each, one behind the other) would wait for slots.  In pieces of `hash_piece_waves` waves
+        // the other legs / chunks of a call (a few hundred waves each, one behind the other) would wait for slots.  In pieces of `hl.piece_waves` waves
         // (~2 per SIMD: the multiplier is still saturated) the rest of the register file stays free for them.
-        const size_t per = wide && c->hash_piece_waves ? hash_piece_states(c, leg) : n;
-        const uint32_t lds = wide ? c->hash_lds_bytes : 0;
+        const size_t per = wide && hl.piece_waves ? hash_piece_states(c, leg, hl.piece_waves) : n;
+        const uint32_t lds = wide ? hl.lds_bytes : 0;
         for (size_t lo = 0; lo < n; lo += per) {
             const size_t cnt = std::min(per, n - lo);
+            const uint32_t grid = cdiv(coop_threads<LN>(cnt), 256);      // (one lane per state: a thread each)
+            if (u) {
+                if constexpr (LN == 1) mb::pstate_hash1_uniq_kernel<FIELD_FP><<<grid, 256, lds, stream>>>((uint32_t)lo, (uint32_t)cnt, u->m, u->uniq, pp, salts, d_records, d_nfields, d_hashes, d_bodies);
+                else mb::pstate_hash_uniq_kernel<FIELD_FP, LN><<<grid, 256, lds, stream>>>((uint32_t)lo, (uint32_t)cnt, u->m, u->uniq, c->fk[FIELD_FP], pp, salts, d_records, d_nfields, d_hashes, d_bodies);
+                continue;
+            }
             const uint32_t *rec = d_records + lo * MINA_PSTATE_SLOTS * 8, *nf = d_nfields + lo;
             uint32_t *hash = d_hashes + lo * 8, *body = d_bodies ? d_bodies + lo * 8 : nullptr;
-            if constexpr (LN == 1) mb::pstate_hash1_kernel<FIELD_FP><<<cdiv(cnt, 256), 256, lds, c->L->stream>>>((uint32_t)cnt, pp, salts, rec, nf, hash, body);
-            else mb::pstate_hash_kernel<FIELD_FP, LN><<<cdiv(coop_threads<LN>(cnt), 256), 256, lds, c->L->stream>>>((uint32_t)cnt, c->fk[FIELD_FP], pp, salts, rec, nf, hash, body);
+            if constexpr (LN == 1) mb::pstate_hash1_kernel<FIELD_FP><<<grid, 256, lds, stream>>>((uint32_t)cnt, pp, salts, rec, nf, hash, body);
+            else mb::pstate_hash_kernel<FIELD_FP, LN><<<grid, 256, lds, stream>>>((uint32_t)cnt, c->fk[FIELD_FP], pp, salts, rec, nf, hash, body);
         }
         HIPC(hipGetLastError());
         return MINA_OK;
     });
+}
+
+// `n` states of a leg of `leg` states (a piece of it, or all of it): the form follows the leg (ctx.h hash_one_lane), so that callers that cut a leg into
+// pieces (hash_piece_states) and this function agree on it
+static int pstate_hash_dev(mina_ctx *c, size_t n, size_t leg, HashLaunch hl, const uint32_t *d_records, const uint32_t *d_nfields, uint32_t *d_hashes, uint32_t *d_bodies) {
+    ProfScope ps_(c, PS_STATE_HASH);
+    return pstate_hash_launch(c, n, leg, hl, d_records, d_nfields, d_hashes, d_bodies, nullptr);
 }
 
 // ------------------------------------------------------------------------------------------------ the deduplicated state leg (state_dedup.cuh)
@@ -321,9 +337,7 @@ static int pstate_dedup_group_dev(mina_ctx *c, size_t n, const uint32_t *d_recor
 // (the distinct count is known on the device only: the grids cover `n`, workgroups past the count return at once) straight into the representatives' places of
 // `d_hashes`, copy every other record's hash from its representative's.  Everything on the current lane's stream, in its dd_* buffers; no host synchronisation.
 // `d_hashes` (and `d_bodies`) must be 16-byte aligned.
-static int pstate_hash_dedup_dev(mina_ctx *c, size_t n, size_t leg, const uint32_t *d_records, const uint32_t *d_nfields, uint32_t *d_hashes, uint32_t *d_bodies, bool count) {
-    const PoseidonParams *pp = c->pparams[FIELD_FP].as<PoseidonParams>();
-    const fe_t *salts = c->state_salts.as<fe_t>();
+static int pstate_hash_dedup_dev(mina_ctx *c, size_t n, size_t leg, HashLaunch hl, const uint32_t *d_records, const uint32_t *d_nfields, uint32_t *d_hashes, uint32_t *d_bodies, bool count) {
     Lane &L = *c->L;
     ProfScope ps_(c, PS_STATE_HASH);
     int rc;
@@ -332,24 +346,8 @@ static int pstate_hash_dedup_dev(mina_ctx *c, size_t n, size_t leg, const uint32
     if ((rc = pstate_dedup_group_dev(c, n, d_records, d_nfields, 0, L.dd_rep.as<uint32_t>(), L.dd_counts.as<uint32_t>(), L.dd_uniq.as<uint32_t>(),
                                      count ? c->dedup_totals.as<unsigned long long>() : nullptr))) return rc;
     if (count) c->dedup_states += n;
-    const uint32_t *m = L.dd_counts.as<uint32_t>(), *uniq = L.dd_uniq.as<uint32_t>();
-    uint32_t *const uh = d_hashes, *const ub = d_bodies;
-    rc = with_lanes<1, 16, 8, 3>(pstate_hash_lanes(c, n, leg), [&](auto lanes) {
-        constexpr int LN = decltype(lanes)::value;
-        constexpr bool wide = LN == 1 || LN == 3;
-        std::optional<ProfScope> ps1_;
-        if (LN == 1) ps1_.emplace(c, PS_STATE_HASH1);
-        const size_t per = wide && c->hash_piece_waves ? hash_piece_states(c, leg) : n;      // pieces as in pstate_hash_dev; those past the distinct count are empty launches
-        const uint32_t lds = wide ? c->hash_lds_bytes : 0;
-        for (size_t lo = 0; lo < n; lo += per) {
-            const size_t cnt = std::min(per, n - lo);
-            if constexpr (LN == 1) mb::pstate_hash1_uniq_kernel<FIELD_FP><<<cdiv(cnt, 256), 256, lds, L.stream>>>((uint32_t)lo, (uint32_t)cnt, m, uniq, pp, salts, d_records, d_nfields, uh, ub);
-            else mb::pstate_hash_uniq_kernel<FIELD_FP, LN><<<cdiv(coop_threads<LN>(cnt), 256), 256, lds, L.stream>>>((uint32_t)lo, (uint32_t)cnt, m, uniq, c->fk[FIELD_FP], pp, salts, d_records, d_nfields, uh, ub);
-        }
-        HIPC(hipGetLastError());
-        return MINA_OK;
-    });
-    if (rc) return rc;
+    const UniqList u{L.dd_counts.as<uint32_t>(), L.dd_uniq.as<uint32_t>()};
+    if ((rc = pstate_hash_launch(c, n, leg, hl, d_records, d_nfields, d_hashes, d_bodies, &u))) return rc;
     mb::pstate_dedup_scatter_kernel<<<cdiv(2 * n, 256), 256, 0, L.stream>>>((uint32_t)n, L.dd_rep.as<uint32_t>(), d_hashes, d_bodies);
     HIPC(hipGetLastError());
     return MINA_OK;
@@ -382,8 +380,8 @@ extern "C" int mina_protocol_state_dedup_dev(mina_ctx *c, size_t n, const void *
     return pstate_dedup_group_dev(c, n, (const uint32_t *)d_records, (const uint32_t *)d_nfields, fingerprint_bits, (uint32_t *)d_rep, (uint32_t *)d_counts, nullptr, nullptr);
 }
 
-extern "C" int mina_protocol_state_hash_batch_dedup(mina_ctx *c, size_t n, const uint8_t *records, const uint32_t *n_body_fields, uint8_t *hashes_out,
-                                                    uint8_t *body_hashes_out, size_t *n_distinct) {
+// host-buffer hashes: upload, hash (with `dedup` each distinct record once; its count -> *n_distinct), download
+static int pstate_hash_batch(mina_ctx *c, size_t n, const uint8_t *records, const uint32_t *n_body_fields, uint8_t *hashes_out, uint8_t *body_hashes_out, bool dedup, size_t *n_distinct) {
     if (!c || (n && (!records || !n_body_fields || !hashes_out))) return fail(MINA_ERR_ARG, "null argument");
     if (n_distinct) *n_distinct = 0;
     if (n == 0) return MINA_OK;
@@ -398,33 +396,23 @@ extern "C" int mina_protocol_state_hash_batch_dedup(mina_ctx *c, size_t n, const
     if ((rc = h2d(c, L.tmp_b, n_body_fields, n * 4))) return rc;
     if ((rc = L.tmp_c.ensure(n * 32))) return rc;
     if ((rc = L.tmp_d.ensure(n * 32))) return rc;
-    if ((rc = pstate_hash_dedup_dev(c, n, n, L.tmp_a.as<uint32_t>(), L.tmp_b.as<uint32_t>(), L.tmp_c.as<uint32_t>(), body_hashes_out ? L.tmp_d.as<uint32_t>() : nullptr, false))) return rc;
+    uint32_t *bodies = body_hashes_out ? L.tmp_d.as<uint32_t>() : nullptr;
+    if ((rc = dedup ? pstate_hash_dedup_dev(c, n, n, HashLaunch{}, L.tmp_a.as<uint32_t>(), L.tmp_b.as<uint32_t>(), L.tmp_c.as<uint32_t>(), bodies, false)
+                    : pstate_hash_dev(c, n, n, HashLaunch{}, L.tmp_a.as<uint32_t>(), L.tmp_b.as<uint32_t>(), L.tmp_c.as<uint32_t>(), bodies))) return rc;
     if (body_hashes_out) HIPC(hipMemcpyAsync(body_hashes_out, L.tmp_d.p, n * 32, hipMemcpyDeviceToHost, L.stream));
     uint32_t m = 0;
-    HIPC(hipMemcpyAsync(&m, L.dd_counts.p, 4, hipMemcpyDeviceToHost, L.stream));
+    if (dedup) HIPC(hipMemcpyAsync(&m, L.dd_counts.p, 4, hipMemcpyDeviceToHost, L.stream));
     if ((rc = d2h_sync(c, hashes_out, L.tmp_c, n * 32))) return rc;
     if (n_distinct) *n_distinct = m;
     return MINA_OK;
 }
-
+extern "C" int mina_protocol_state_hash_batch_dedup(mina_ctx *c, size_t n, const uint8_t *records, const uint32_t *n_body_fields, uint8_t *hashes_out,
+                                                    uint8_t *body_hashes_out, size_t *n_distinct) {
+    return pstate_hash_batch(c, n, records, n_body_fields, hashes_out, body_hashes_out, true, n_distinct);
+}
 extern "C" int mina_protocol_state_hash_batch(mina_ctx *c, size_t n, const uint8_t *records, const uint32_t *n_body_fields, uint8_t *hashes_out,
                                               uint8_t *body_hashes_out) {
-    if (!c || (n && (!records || !n_body_fields || !hashes_out))) return fail(MINA_ERR_ARG, "null argument");
-    if (n == 0) return MINA_OK;
-    if (n > (1u << 22)) return fail(MINA_ERR_ARG, "n too large");
-    for (size_t i = 0; i < n; ++i) if (n_body_fields[i] > MINA_PSTATE_SLOTS - 1) return fail(MINA_ERR_ARG, "n_body_fields exceeds the record");
-    HIPC(hipSetDevice(c->device));
-    c->use_lane0();
-    int rc;
-    if ((rc = ensure_state_salts(c))) return rc;
-    Lane &L = *c->L;
-    if ((rc = h2d(c, L.tmp_a, records, n * MINA_PSTATE_SLOTS * 32))) return rc;
-    if ((rc = h2d(c, L.tmp_b, n_body_fields, n * 4))) return rc;
-    if ((rc = L.tmp_c.ensure(n * 32))) return rc;
-    if ((rc = L.tmp_d.ensure(n * 32))) return rc;
-    if ((rc = pstate_hash_dev(c, n, n, L.tmp_a.as<uint32_t>(), L.tmp_b.as<uint32_t>(), L.tmp_c.as<uint32_t>(), body_hashes_out ? L.tmp_d.as<uint32_t>() : nullptr))) return rc;
-    if (body_hashes_out) HIPC(hipMemcpyAsync(body_hashes_out, L.tmp_d.p, n * 32, hipMemcpyDeviceToHost, L.stream));
-    return d2h_sync(c, hashes_out, L.tmp_c, n * 32);
+    return pstate_hash_batch(c, n, records, n_body_fields, hashes_out, body_hashes_out, false, nullptr);
 }
 
 // convenience: serialized states in, state hashes out (parse on the host, hash on the GPU); malformed state -> MINA_ERR_FORMAT
@@ -512,11 +500,10 @@ extern "C" int mina_state_jobs_prepare(mina_ctx *c, uint32_t log2_domain, uint32
     return MINA_OK;
 }
 
-// all pointers of `j` are device pointers; queued on the current lane
-// `split`: the three independent legs (protocol states / wrap opening / accumulator) go to three lanes of the context -- lane 0 plus
-// two helper lanes -- and are joined by events before the verdict kernel: for small, latency-bound batches the serial chain of
-// dependent Poseidon permutations of one leg hides behind the other legs (host-buffer entry point only).
-static int leg_fork(mina_ctx *c, Lane &from, Lane &to) {
+// Fork / join of a job's legs.  A job may run its three independent legs (protocol states / wrap opening / accumulator) on three lanes -- the current one plus
+// helper lanes -- joined by events before the verdict kernel: for small, latency-bound batches the serial chain of dependent Poseidon permutations of one leg
+// hides behind the other legs (mina_state_job_batch), large ones fill the chip with fewer jobs in flight (dev_fork_lanes, the boundary's setup_legs).
+static int leg_fork(Lane &from, Lane &to) {
     if (!to.stream) HIPC(hipStreamCreateWithFlags(&to.stream, hipStreamNonBlocking));
     if (!from.ev_leg) HIPC(hipEventCreateWithFlags(&from.ev_leg, hipEventDisableTiming));
     HIPC(hipEventRecord(from.ev_leg, from.stream));
@@ -531,8 +518,8 @@ static int leg_join(Lane &leg, Lane &into) {
 }
 // Early start of a job's protocol-state leg: the boundary (api_verify.hip) streams the records of a chunk to the GPU while the rest of the
 // chunk is still being parsed, and queues the hashes of states [lo, lo + cnt) -- of a job of `ns_total` states whose state leg will run on
-// lane LS -- behind `after` (the upload of those records).  mb_state_jobs_on_lane then takes `c->state_hashes_early` states as hashed.
-int mb_state_hashes_early(mina_ctx *c, Lane *LS, size_t ns_total, size_t lo, size_t cnt, const uint32_t *d_records, const uint32_t *d_nfields, hipEvent_t after) {
+// lane LS -- behind `after` (the upload of those records).  The caller keeps count and hands it to mb_state_jobs_on_lane as StateJobPlan::hashed_early.
+int mb_state_hashes_early(mina_ctx *c, Lane *LS, size_t ns_total, size_t lo, size_t cnt, const uint32_t *d_records, const uint32_t *d_nfields, hipEvent_t after, HashLaunch hash) {
     if (!LS || lo + cnt > ns_total) return fail(MINA_ERR_ARG, "bad early state range");
     if (!c->have_state_salts) return fail(MINA_ERR_STATE, "call mina_state_jobs_prepare first");
     if (!LS->stream) HIPC(hipStreamCreateWithFlags(&LS->stream, hipStreamNonBlocking));
@@ -541,146 +528,151 @@ int mb_state_hashes_early(mina_ctx *c, Lane *LS, size_t ns_total, size_t lo, siz
     if (after) HIPC(hipStreamWaitEvent(LS->stream, after, 0));
     Lane *const L0 = c->L;
     c->L = LS;
-    rc = pstate_hash_dev(c, cnt, ns_total, d_records + lo * MINA_PSTATE_SLOTS * 8, d_nfields + lo, LS->st_hashes.as<uint32_t>() + lo * 8, nullptr);
+    rc = pstate_hash_dev(c, cnt, ns_total, hash, d_records + lo * MINA_PSTATE_SLOTS * 8, d_nfields + lo, LS->st_hashes.as<uint32_t>() + lo * 8, nullptr);
     c->L = L0;
     return rc;
 }
 
-// LI / LA: helper lanes of the wrap-proof leg and the accumulator leg (nullptr = everything on the current lane, in order); LS: a lane of
-// its own for the protocol-state leg as well (the boundary gives the chain and the hashes streams with disjoint CU masks, api_verify.hip)
-// `phase`: MB_JOB_ALL queues the whole job.  The boundary queues a job in two steps, because the wrap-proof half of its input is parsed (and
-// uploaded) before the protocol states are: MB_JOB_LEGS = the accumulator and wrap-proof legs (their verdict pointers are kept in `carry`),
-// later MB_JOB_FINISH = the protocol-state leg (minus what mb_state_hashes_early queued already), the joins and the verdict kernel.
-int mb_state_jobs_on_lane(mina_ctx *c, const mina_state_jobs *j, uint32_t *d_verdicts, uint32_t *d_flags, Lane *LI_, Lane *LA_, uint32_t *d_stmt_out, Lane *LS_, uint32_t phase, StateJobCarry *carry) {
-    if (phase != MB_JOB_ALL && !carry) return fail(MINA_ERR_ARG, "a split job needs a carry");
-    Lane &L = *c->L;
-    Lane *const L0 = c->L;
-    Lane *LI = L0, *LA = L0, *LS = L0;
-    if (LI_ && LA_ && LI_ != L0 && LA_ != L0 && LI_ != LA_) {
-        LI = LI_; LA = LA_;
-        if (LS_ && LS_ != L0 && LS_ != LI) LS = LS_;             // LS == LA: the accumulator leg shares the hashes' stream (behind them, or ahead: mina_ctx::acc_first)
-        c->legs_forked = true;
-        int frc;
-        if ((phase & MB_JOB_LEGS) && ((frc = leg_fork(c, *L0, *LI)) || (frc = leg_fork(c, *L0, *LA)))) return frc;
-        if ((phase & MB_JOB_FINISH) && LS != L0 && (frc = leg_fork(c, *L0, *LS))) return frc;
-    }
+// ---- the legs of a job.  Each is told its lane and makes it the current one (c->L: where every mb_*_dev helper queues); mb_state_jobs_on_lane restores the
+// caller's.  Every pointer of `j` is a device pointer; nothing here waits for the GPU.  `v` collects the words the verdict kernel reads.
+
+// protocol-state leg: the hashes of the job's states (those not queued early), then the chain check -> S.st_ok
+static int state_leg(mina_ctx *c, const mina_state_jobs *j, Lane &S, const StateJobPlan &plan) {
+    c->L = &S;
     const size_t B = j->batch;
     int rc;
-    struct Unfork { mina_ctx *c; Lane *l0; ~Unfork() { c->legs_forked = false; c->L = l0; } } unfork{c, L0};
-    const uint32_t *comm_override = nullptr;
-    uint32_t *ipa_v = nullptr, *acc_v = nullptr;
-    uint32_t *kimchi_bad = nullptr; const uint32_t *stmt_ok = nullptr;
-    // ---- accumulator leg.  It shares scratch buffers with the opening check (ipa_chals / ipa_sigma / ipa_points of its lane), and the
-    // culprit search re-checks slices of a failed batch from the rows the opening check LEFT in those buffers (mb_ipa_recheck_rows): on the
-    // wrap leg's own lane the accumulator therefore runs FIRST (run after it, as it did until round 3, it overwrote the rows: every
-    // part of a search then failed and a batch of more than 1024 proofs with one bad opening was rejected whole).
-    auto accumulator_leg = [&]() -> int {
-        c->L = LA;
-        if (j->with_accumulator) {
-            int r;
-            if ((r = LA->st_flags.ensure(16 * 4))) return r;
-            acc_v = LA->st_flags.as<uint32_t>() + 8;
-            if ((r = mb_accumulator_check_dev(c, CURVE_VESTA, j->acc_k, B, (const uint32_t *)j->acc_prechallenges, (const uint32_t *)j->acc_sg,
-                                              B > 1 ? (const uint32_t *)j->acc_rho : nullptr, acc_v))) return r;
-        }
-        return MINA_OK;
-    };
-    const bool acc_ahead = c->acc_first && LA == LS && LS != L0 && phase == MB_JOB_ALL;      // (device-resident jobs only: the boundary queues a job in two phases)
-    if (acc_ahead && (rc = accumulator_leg())) { c->L = L0; return rc; }
-    Lane &S = *LS;                                              // ---- protocol-state leg
-    c->L = LS;
-    if ((rc = S.st_ok.ensure(B * 4))) return rc;
-    if (!(phase & MB_JOB_FINISH)) {}
-    else if (j->with_states) {
+    if (j->with_states) {
         const size_t ns = B * MINA_STATES_PER_PROOF;
         if ((rc = S.st_hashes.ensure(ns * 32))) return rc;
-        const size_t early = std::min(c->state_hashes_early, ns);      // already queued on this lane by mb_state_hashes_early
-        c->state_hashes_early = 0;
+        const size_t early = std::min(plan.hashed_early, ns);          // already queued on this lane by mb_state_hashes_early
+        const uint32_t *rec = (const uint32_t *)j->state_records, *nf = (const uint32_t *)j->state_nfields;
         // mina_ctx_set_state_dedup: the whole leg at once, each distinct record hashed once (a piece queued early could not know its duplicates in later pieces)
         if (c->state_dedup && early == 0) {
-            if ((rc = pstate_hash_dedup_dev(c, ns, ns, (const uint32_t *)j->state_records, (const uint32_t *)j->state_nfields, S.st_hashes.as<uint32_t>(), nullptr, true))) return rc;
-        } else
-        if (early < ns && (rc = pstate_hash_dev(c, ns - early, ns, (const uint32_t *)j->state_records + early * MINA_PSTATE_SLOTS * 8, (const uint32_t *)j->state_nfields + early,
-                                                S.st_hashes.as<uint32_t>() + early * 8, nullptr))) return rc;
-        mb::pstate_chain_check_kernel<<<cdiv(B, 64), 64, 0, S.stream>>>((uint32_t)B, S.st_hashes.as<uint32_t>(), (const uint32_t *)j->expected_hashes,
-                                                                         (const uint32_t *)j->state_records, (const uint8_t *)j->precheck, S.st_ok.as<uint32_t>());
+            if ((rc = pstate_hash_dedup_dev(c, ns, ns, plan.hash, rec, nf, S.st_hashes.as<uint32_t>(), nullptr, true))) return rc;
+        } else if (early < ns && (rc = pstate_hash_dev(c, ns - early, ns, plan.hash, rec + early * MINA_PSTATE_SLOTS * 8, nf + early, S.st_hashes.as<uint32_t>() + early * 8, nullptr))) return rc;
+        mb::pstate_chain_check_kernel<<<cdiv(B, 64), 64, 0, S.stream>>>((uint32_t)B, S.st_hashes.as<uint32_t>(), (const uint32_t *)j->expected_hashes, rec, (const uint8_t *)j->precheck, S.st_ok.as<uint32_t>());
     } else {
         // no state leg: chain_ok = all ones
         if (j->precheck) return fail(MINA_ERR_ARG, "precheck needs the protocol-state section");
         mb::fill_u32_kernel<<<cdiv(B, 256), 256, 0, S.stream>>>((uint32_t)B, 1u, S.st_ok.as<uint32_t>());
     }
     HIPC(hipGetLastError());
-    c->L = L0;
-    if ((phase & MB_JOB_LEGS) && LA == LI && (rc = accumulator_leg())) { c->L = L0; return rc; }
-    c->L = LI;                                                  // ---- wrap-proof leg
-    if (phase & MB_JOB_LEGS) {
-    Lane &L = *LI;
-    if ((rc = L.st_flags.ensure(16 * 4))) { c->L = L0; return rc; }
-    const uint32_t *pub = (const uint32_t *)j->public_inputs;
+    return MINA_OK;
+}
+
+// accumulator leg: the folded check of the step accumulators -> v.acc_v
+static int accumulator_leg(mina_ctx *c, const mina_state_jobs *j, Lane &A, const FoldExport *fx, StateJobCarry &v) {
+    c->L = &A;
+    if (!j->with_accumulator) return MINA_OK;
+    const size_t B = j->batch;
+    int rc;
+    if ((rc = A.st_flags.ensure(16 * 4))) return rc;
+    v.acc_v = A.st_flags.as<uint32_t>() + 8;
+    return mb_accumulator_check_dev(c, CURVE_VESTA, j->acc_k, B, (const uint32_t *)j->acc_prechallenges, (const uint32_t *)j->acc_sg, B > 1 ? (const uint32_t *)j->acc_rho : nullptr, v.acc_v, fx);
+}
+
+// wrap-proof leg: Pickles statement -> public-input commitment -> kimchi to_batch -> combined opening check; -> v.stmt_ok, v.kimchi_bad, v.ipa_v
+static int wrap_leg(mina_ctx *c, const mina_state_jobs *j, Lane &L, const FoldExport *fx, StateJobCarry &v) {
+    c->L = &L;
+    const size_t B = j->batch;
+    int rc;
+    if ((rc = L.st_flags.ensure(16 * 4))) return rc;
+    const uint32_t *pub = (const uint32_t *)j->public_inputs, *comm_override = nullptr;
     if (j->kimchi && j->kimchi->statements) {      // the Pickles statement -> the wrap circuit's public inputs, on this lane ahead of everything that reads them
-        if ((rc = L.pk_pub.ensure(B * 40 * 32)) || (rc = L.pk_ok.ensure(B * 4))) { c->L = L0; return rc; }
-        if ((rc = mb_pickles_statements_dev(c, B, j->kimchi->statements, L.pk_pub.as<uint32_t>(), L.pk_ok.as<uint32_t>()))) { c->L = L0; return rc; }
-        pub = L.pk_pub.as<uint32_t>(); stmt_ok = L.pk_ok.as<uint32_t>();
+        if ((rc = L.pk_pub.ensure(B * 40 * 32)) || (rc = L.pk_ok.ensure(B * 4))) return rc;
+        if ((rc = mb_pickles_statements_dev(c, B, j->kimchi->statements, L.pk_pub.as<uint32_t>(), L.pk_ok.as<uint32_t>()))) return rc;
+        pub = L.pk_pub.as<uint32_t>(); v.stmt_ok = L.pk_ok.as<uint32_t>();
     }
     if (j->npub || j->kimchi) {
-        if ((rc = L.st_pubcomm.ensure(B * 64))) { c->L = L0; return rc; }
-        if ((rc = mb_pubcomm_dev(c, B, j->log2_domain, j->npub, pub, L.st_pubcomm.as<uint32_t>()))) { c->L = L0; return rc; }
+        if ((rc = L.st_pubcomm.ensure(B * 64))) return rc;
+        if ((rc = mb_pubcomm_dev(c, B, j->log2_domain, j->npub, pub, L.st_pubcomm.as<uint32_t>()))) return rc;
         comm_override = L.st_pubcomm.as<uint32_t>();
     }
-    if (j->with_ipa) {
-        mb::IpaShape sh; sh.batch = (uint32_t)B; sh.k = j->k; sh.npts = j->n_evalpoints; sh.ncomms = j->n_comms; sh.per = 2 * j->k + j->n_comms + 4;
-        auto W = [](const void *p) { return (const uint32_t *)p; };
-        ipa_v = L.st_flags.as<uint32_t>() + 4;
-        if (j->kimchi) {
-            // kimchi oracles + to_batch produce the BatchEvaluationProof rows in lane buffers (the public-input commitment is already in the list)
-            const mina_kimchi_proofs &kp = *j->kimchi;
-            if ((rc = L.kc_state.ensure(B * 96)) || (rc = L.kc_pos.ensure(B * 8)) || (rc = L.kc_cip.ensure(B * 32)) || (rc = L.kc_pts.ensure(B * 64)) ||
-                (rc = L.kc_v.ensure(B * 32)) || (rc = L.kc_u.ensure(B * 32)) || (rc = L.kc_comms.ensure(B * (size_t)j->n_comms * 64))) { c->L = L0; return rc; }
-            kimchi_bad = L.st_flags.as<uint32_t>() + 12;
-            HIPC(hipMemsetAsync(kimchi_bad, 0, 4, L.stream));
-            const uint32_t *prev_chals = W(kp.prev_chals);
-            // no recursion challenges given beside a statement: they ARE the statement's messages_for_next_wrap_proof.old_bulletproof_challenges
-            // (2 x 15; the one source a verifier has), and their digest was taken on the way by the statement stage
-            const bool from_statement = !kp.prev_chals && !kp.prev_prechallenges && kp.statements && kp.n_prev == 2 && j->k == 15;
-            const void *pre = from_statement ? kp.statements->wrap_old_challenges : kp.prev_prechallenges;
-            const void *pf_digest = nullptr; uint32_t pf_stride = 0;
-            if (from_statement && mb_tune().kimchi_shared_digest) mb_pickles_kimchi_digest(c, kp.statements, &pf_digest, &pf_stride);
-            if (pre && kp.n_prev) {                             // 128-bit prechallenges -> scalar-field challenges, on this lane ahead of the sponges
-                const size_t cnt = B * kp.n_prev * j->k;
-                if ((rc = L.kc_pch.ensure(cnt * 32))) { c->L = L0; return rc; }
-                challenge_to_field_kernel<FIELD_FQ><<<cdiv(cnt, 64), 64, 0, L.stream>>>((uint32_t)cnt, c->fk[FIELD_FQ], W(pre), L.kc_pch.as<uint32_t>());
-                prev_chals = L.kc_pch.as<uint32_t>();
-            }
-            mb::KimchiIn in{pub, prev_chals, W(kp.prev_comms), W(kp.w_comm), W(kp.z_comm), W(kp.t_comm), W(kp.evals), W(kp.ft_eval1), comm_override};
-            mb::KimchiOut out{L.kc_state.as<uint32_t>(), L.kc_pos.as<uint32_t>(), L.kc_cip.as<uint32_t>(), L.kc_pts.as<uint32_t>(), L.kc_v.as<uint32_t>(), L.kc_u.as<uint32_t>(),
-                              L.kc_comms.as<uint32_t>(), nullptr};
-            mb::IpaExpand ex;
-            if ((rc = mb_kimchi_to_batch_dev(c, B, kp.n_prev, kp.npub, in, out, kimchi_bad, &ex, pf_digest, pf_stride))) { c->L = L0; return rc; }
-            sh.expand_slot = kp.n_prev + 1; sh.per += mb::IPA_EXPAND - 1;          // the ft commitment enters the MSM as its 8 terms
-            if (mb_tune().ipa_shared_points && kp.n_prev + 45 <= 64) {   // h, the 27 index columns and the index point of the ft combination are the same
-                uint64_t m = 0;                                                       // points for every proof: their scalars are summed first (29 of 88 entries per proof)
-                for (uint32_t i = kp.n_prev + 3; i < kp.n_prev + 9; ++i) m |= (uint64_t)1 << i;        // 6 selectors
-                for (uint32_t i = kp.n_prev + 24; i < kp.n_prev + 45; ++i) m |= (uint64_t)1 << i;      // 15 coefficients + 6 sigma
-                sh.shared_lo = (uint32_t)m; sh.shared_hi = (uint32_t)(m >> 32); sh.shared_h = 1; sh.shared_expand0 = 1; sh.nshared = 29;
-            }
-            mb::IpaDevIn iin{out.sponge_state, out.sponge_pos, out.cip, W(j->lr), W(j->delta), W(j->sg), W(j->z1), W(j->z2), out.evalpoints, out.evalscale, out.polyscale,
-                             out.comms, nullptr, W(j->rand_base), W(j->sg_rand_base)};
-            iin.expand = ex;
-            if ((rc = mb_ipa_batch_check_dev(c, CURVE_PALLAS, sh, iin, ipa_v))) { c->L = L0; return rc; }
-        } else {
-            sh.override_slot = j->npub ? j->pub_comm_slot : 0xffffffffu;
-            mb::IpaDevIn in{W(j->sponge_state), W(j->sponge_pos), W(j->cip), W(j->lr), W(j->delta), W(j->sg), W(j->z1), W(j->z2), W(j->evalpoints), W(j->evalscale),
-                            W(j->polyscale), W(j->comms), comm_override, W(j->rand_base), W(j->sg_rand_base)};
-            if ((rc = mb_ipa_batch_check_dev(c, CURVE_PALLAS, sh, in, ipa_v))) { c->L = L0; return rc; }
-        }
+    if (!j->with_ipa) return MINA_OK;
+    mb::IpaShape sh; sh.batch = (uint32_t)B; sh.k = j->k; sh.npts = j->n_evalpoints; sh.ncomms = j->n_comms; sh.per = 2 * j->k + j->n_comms + 4;
+    auto W = [](const void *p) { return (const uint32_t *)p; };
+    v.ipa_v = L.st_flags.as<uint32_t>() + 4;
+    if (!j->kimchi) {
+        sh.override_slot = j->npub ? j->pub_comm_slot : 0xffffffffu;
+        mb::IpaDevIn in{W(j->sponge_state), W(j->sponge_pos), W(j->cip), W(j->lr), W(j->delta), W(j->sg), W(j->z1), W(j->z2), W(j->evalpoints), W(j->evalscale),
+                        W(j->polyscale), W(j->comms), comm_override, W(j->rand_base), W(j->sg_rand_base)};
+        return mb_ipa_batch_check_dev(c, CURVE_PALLAS, sh, in, v.ipa_v, fx);
     }
+    // kimchi oracles + to_batch produce the BatchEvaluationProof rows in lane buffers (the public-input commitment is already in the list)
+    const mina_kimchi_proofs &kp = *j->kimchi;
+    if ((rc = L.kc_state.ensure(B * 96)) || (rc = L.kc_pos.ensure(B * 8)) || (rc = L.kc_cip.ensure(B * 32)) || (rc = L.kc_pts.ensure(B * 64)) ||
+        (rc = L.kc_v.ensure(B * 32)) || (rc = L.kc_u.ensure(B * 32)) || (rc = L.kc_comms.ensure(B * (size_t)j->n_comms * 64))) return rc;
+    v.kimchi_bad = L.st_flags.as<uint32_t>() + 12;
+    HIPC(hipMemsetAsync(v.kimchi_bad, 0, 4, L.stream));
+    const uint32_t *prev_chals = W(kp.prev_chals);
+    // no recursion challenges given beside a statement: they ARE the statement's messages_for_next_wrap_proof.old_bulletproof_challenges
+    // (2 x 15; the one source a verifier has), and their digest was taken on the way by the statement stage
+    const bool from_statement = !kp.prev_chals && !kp.prev_prechallenges && kp.statements && kp.n_prev == 2 && j->k == 15;
+    const void *pre = from_statement ? kp.statements->wrap_old_challenges : kp.prev_prechallenges;
+    const void *pf_digest = nullptr; uint32_t pf_stride = 0;
+    if (from_statement && mb_tune().kimchi_shared_digest) mb_pickles_kimchi_digest(c, kp.statements, &pf_digest, &pf_stride);
+    if (pre && kp.n_prev) {                             // 128-bit prechallenges -> scalar-field challenges, on this lane ahead of the sponges
+        const size_t cnt = B * kp.n_prev * j->k;
+        if ((rc = L.kc_pch.ensure(cnt * 32))) return rc;
+        challenge_to_field_kernel<FIELD_FQ><<<cdiv(cnt, 64), 64, 0, L.stream>>>((uint32_t)cnt, c->fk[FIELD_FQ], W(pre), L.kc_pch.as<uint32_t>());
+        prev_chals = L.kc_pch.as<uint32_t>();
     }
-    if ((phase & MB_JOB_LEGS) && LA != LI && !acc_ahead && (rc = accumulator_leg())) { c->L = L0; return rc; }
-    c->L = L0;
-    if (phase == MB_JOB_LEGS) { carry->ipa_v = ipa_v; carry->acc_v = acc_v; carry->kimchi_bad = kimchi_bad; carry->stmt_ok = stmt_ok; return MINA_OK; }
-    if (phase == MB_JOB_FINISH) { ipa_v = carry->ipa_v; acc_v = carry->acc_v; kimchi_bad = carry->kimchi_bad; stmt_ok = carry->stmt_ok; }
-    if (LI != L0) { int jrc; if ((jrc = leg_join(*LI, *L0)) || (jrc = leg_join(*LA, *L0)) || (LS != L0 && (jrc = leg_join(*LS, *L0)))) return jrc; }
-    mb::state_job_verdict_kernel<<<cdiv(B, 64), 64, 0, L.stream>>>((uint32_t)B, S.st_ok.as<uint32_t>(), ipa_v, acc_v, kimchi_bad, stmt_ok, d_verdicts, d_flags, d_stmt_out);
+    mb::KimchiIn in{pub, prev_chals, W(kp.prev_comms), W(kp.w_comm), W(kp.z_comm), W(kp.t_comm), W(kp.evals), W(kp.ft_eval1), comm_override};
+    mb::KimchiOut out{L.kc_state.as<uint32_t>(), L.kc_pos.as<uint32_t>(), L.kc_cip.as<uint32_t>(), L.kc_pts.as<uint32_t>(), L.kc_v.as<uint32_t>(), L.kc_u.as<uint32_t>(),
+                      L.kc_comms.as<uint32_t>(), nullptr};
+    mb::IpaExpand ex;
+    if ((rc = mb_kimchi_to_batch_dev(c, B, kp.n_prev, kp.npub, in, out, v.kimchi_bad, &ex, pf_digest, pf_stride))) return rc;
+    sh.expand_slot = kp.n_prev + 1; sh.per += mb::IPA_EXPAND - 1;          // the ft commitment enters the MSM as its 8 terms
+    if (mb_tune().ipa_shared_points && kp.n_prev + 45 <= 64) {   // h, the 27 index columns and the index point of the ft combination are the same
+        uint64_t m = 0;                                                       // points for every proof: their scalars are summed first (29 of 88 entries per proof)
+        for (uint32_t i = kp.n_prev + 3; i < kp.n_prev + 9; ++i) m |= (uint64_t)1 << i;        // 6 selectors
+        for (uint32_t i = kp.n_prev + 24; i < kp.n_prev + 45; ++i) m |= (uint64_t)1 << i;      // 15 coefficients + 6 sigma
+        sh.shared_lo = (uint32_t)m; sh.shared_hi = (uint32_t)(m >> 32); sh.shared_h = 1; sh.shared_expand0 = 1; sh.nshared = 29;
+    }
+    mb::IpaDevIn iin{out.sponge_state, out.sponge_pos, out.cip, W(j->lr), W(j->delta), W(j->sg), W(j->z1), W(j->z2), out.evalpoints, out.evalscale, out.polyscale,
+                     out.comms, nullptr, W(j->rand_base), W(j->sg_rand_base)};
+    iin.expand = ex;
+    return mb_ipa_batch_check_dev(c, CURVE_PALLAS, sh, iin, v.ipa_v, fx);
+}
+
+// One job, queued as `plan` says (ctx.h StateJobPlan) from the current lane, which keeps the fork, the joins and the verdict kernel.
+// plan.wrap / .acc: helper lanes of the wrap-proof leg and the accumulator leg (null = everything on the current lane, in order); plan.states: a lane of
+// its own for the protocol-state leg as well (the boundary gives the chain and the hashes streams with disjoint CU masks, api_verify.hip)
+// plan.phase: MB_JOB_ALL queues the whole job.  The boundary queues a job in two steps, because the wrap-proof half of its input is parsed (and
+// uploaded) before the protocol states are: MB_JOB_LEGS = the accumulator and wrap-proof legs (their verdict pointers are kept in plan.carry),
+// later MB_JOB_FINISH = the protocol-state leg (minus the plan.hashed_early states mb_state_hashes_early queued already), the joins and the verdict kernel.
+int mb_state_jobs_on_lane(mina_ctx *c, const mina_state_jobs *j, uint32_t *d_verdicts, uint32_t *d_flags, const StateJobPlan &plan) {
+    const uint32_t phase = plan.phase;
+    if (phase != MB_JOB_ALL && !plan.carry) return fail(MINA_ERR_ARG, "a split job needs a carry");
+    Lane *const L0 = c->L;
+    struct Restore { mina_ctx *c; Lane *l0; ~Restore() { c->L = l0; } } restore{c, L0};      // the legs switch the current lane: back to the caller's on every return
+    Lane *LI = L0, *LA = L0, *LS = L0;
+    int rc;
+    if (plan.wrap && plan.acc && plan.wrap != L0 && plan.acc != L0 && plan.wrap != plan.acc) {
+        LI = plan.wrap; LA = plan.acc;
+        if (plan.states && plan.states != L0 && plan.states != LI) LS = plan.states;      // LS == LA: the accumulator leg shares the hashes' stream (behind them, or ahead: plan.acc_first)
+        if ((phase & MB_JOB_LEGS) && ((rc = leg_fork(*L0, *LI)) || (rc = leg_fork(*L0, *LA)))) return rc;
+        if ((phase & MB_JOB_FINISH) && LS != L0 && (rc = leg_fork(*L0, *LS))) return rc;
+    }
+    const size_t B = j->batch;
+    StateJobCarry v;                                            // what the legs leave for the verdict kernel
+    const bool acc_ahead = plan.acc_first && LA == LS && LS != L0 && phase == MB_JOB_ALL;      // (device-resident jobs only: the boundary queues a job in two phases)
+    if (acc_ahead && (rc = accumulator_leg(c, j, *LA, plan.fold_export, v))) return rc;
+    if ((rc = LS->st_ok.ensure(B * 4))) return rc;              // the chain_ok words, in either phase
+    if ((phase & MB_JOB_FINISH) && (rc = state_leg(c, j, *LS, plan))) return rc;
+    if (phase & MB_JOB_LEGS) {
+        // The accumulator leg shares scratch buffers with the opening check (ipa_chals / ipa_sigma / ipa_points of its lane), and the
+        // culprit search re-checks slices of a failed batch from the rows the opening check LEFT in those buffers (mb_ipa_recheck_rows): on the
+        // wrap leg's own lane the accumulator therefore runs FIRST (run after it, as it did until round 3, it overwrote the rows: every
+        // part of a search then failed and a batch of more than 1024 proofs with one bad opening was rejected whole).
+        if (LA == LI && (rc = accumulator_leg(c, j, *LA, plan.fold_export, v))) return rc;
+        if ((rc = wrap_leg(c, j, *LI, plan.fold_export, v))) return rc;
+        if (LA != LI && !acc_ahead && (rc = accumulator_leg(c, j, *LA, plan.fold_export, v))) return rc;
+    }
+    if (phase == MB_JOB_LEGS) { *plan.carry = v; return MINA_OK; }
+    if (phase == MB_JOB_FINISH) v = *plan.carry;
+    if (LI != L0 && ((rc = leg_join(*LI, *L0)) || (rc = leg_join(*LA, *L0)) || (LS != L0 && (rc = leg_join(*LS, *L0))))) return rc;
+    mb::state_job_verdict_kernel<<<cdiv(B, 64), 64, 0, L0->stream>>>((uint32_t)B, LS->st_ok.as<uint32_t>(), v.ipa_v, v.acc_v, v.kimchi_bad, v.stmt_ok, d_verdicts, d_flags, plan.d_stmt_out);
     HIPC(hipGetLastError());
     return MINA_OK;
 }
@@ -693,7 +685,8 @@ int mb_state_jobs_on_lane(mina_ctx *c, const mina_state_jobs *j, uint32_t *d_ver
 // then in force (a stream keeps its CU mask / priority for life).  A pinned lane (mina_ctx_pin_lane: the caller queues its own work on that lane's stream) forks as well: the legs
 // start behind an event recorded on the lane and the lane waits for them before its verdict kernel, so everything the caller queued before the call is seen by every leg and
 // everything it queues after the call sees every leg's output -- the exchange variant (mina_state_job_fold_dev under sharded.py's `ordered()` scope) keeps its ONE ordering stream.
-static int dev_fork_lanes(mina_ctx *c, size_t leg_states, Lane **LI, Lane **LA, Lane **LS) {
+// Fills in the lanes, the hash launch and `acc_first` of `plan`; a job that does not fork keeps the plan as it came (everything on the current lane, one launch).
+static int dev_fork_lanes(mina_ctx *c, size_t leg_states, StateJobPlan &plan) {
     const mina_verify_tuning tu = mb_tune();
     const int li = (int)(c->L - c->lanes);
     if (!(tu.dev_fork & 1u) || c->nlanes > MB_DEV_FORK_MAX || li < 0 || li >= MB_DEV_FORK_MAX) return MINA_OK;
@@ -720,8 +713,8 @@ static int dev_fork_lanes(mina_ctx *c, size_t leg_states, Lane **LI, Lane **LA, 
         int rc;
         if ((rc = make(h[0], true, (mode & 2u) != 0, prio_hi)) || (rc = make(h[1], true, false, (prio_lo + prio_hi) / 2)) || (rc = make(h[2], false, (mode & 2u) != 0, prio_lo))) return rc;
     }
-    *LI = &h[0]; *LA = tu.dev_acc_lane ? &h[2] : &h[1]; *LS = &h[2];      // dev_acc_lane: the accumulator leg on the hashes' stream (1: behind them, 2: ahead)
-    c->acc_first = tu.dev_acc_lane == 2;
+    plan.wrap = &h[0]; plan.acc = tu.dev_acc_lane ? &h[2] : &h[1]; plan.states = &h[2];      // dev_acc_lane: the accumulator leg on the hashes' stream (1: behind them, 2: ahead)
+    plan.acc_first = tu.dev_acc_lane == 2;
     // The hashes of a forked job go out in pieces, so that the jobs in flight together ask for ~6 state-hash waves per SIMD (five fit beside nothing else, 96 VGPRs):
     // measured with the wave priorities on (lanes x piece grid at 4096 / 8192 / 16 384 proofs per call, profiles/r06_dev_fork.md) the best piece is ~6144 / lanes waves
     // whatever the call size -- 2 lanes 3072, 3: 2048, 4: 1536, 6: 1024 -- and a lone call is best left whole.  The single-lane form (ctx.h hash_one_lane) wants twice
@@ -730,7 +723,7 @@ static int dev_fork_lanes(mina_ctx *c, size_t leg_states, Lane **LI, Lane **LA, 
     uint32_t piece = tu.dev_piece_waves;
     if (piece == 0 && in_flight >= 2) piece = (hash_one_lane(c, leg_states) ? 12288u : 6144u) / (uint32_t)in_flight;
     if (piece == 0xffffffffu) piece = 0;
-    c->hash_piece_waves = piece;
+    plan.hash.piece_waves = piece;
     // A lone forked job: its hashes would hold every wave slot their 96 VGPRs allow (5 per SIMD) and the chain's waves would wait for one to retire (~13 ms): the
     // hash workgroups reserve 41 KiB of LDS each -- three per CU = 3 waves per SIMD, 224 VGPRs left: room for a wave of every chain kernel but the two PolishToken
     // interpreters (244 / 194 VGPRs + 64 KiB of LDS: they wait for a CU to drain either way).  Lone calls
@@ -738,7 +731,7 @@ static int dev_fork_lanes(mina_ctx *c, size_t leg_states, Lane **LI, Lane **LA, 
     uint32_t lds_kb = tu.dev_hash_lds_kb;
     if (lds_kb == 0 && in_flight == 1) lds_kb = 41;
     if (lds_kb == 0xffffffffu || lds_kb > 160) lds_kb = 0;
-    c->hash_lds_bytes = lds_kb * 1024u;
+    plan.hash.lds_bytes = lds_kb * 1024u;
     return MINA_OK;
 }
 
@@ -749,11 +742,9 @@ extern "C" int mina_state_job_batch_dev(mina_ctx *c, const mina_state_jobs *jobs
     if (!c->have_state_salts && jobs->with_states) return fail(MINA_ERR_STATE, "call mina_state_jobs_prepare first");
     HIPC(hipSetDevice(c->device));
     c->next_lane();
-    Lane *LI = nullptr, *LA = nullptr, *LS = nullptr;
-    if ((rc = dev_fork_lanes(c, jobs->with_states ? jobs->batch * MINA_STATES_PER_PROOF : 0, &LI, &LA, &LS))) return rc;
-    rc = mb_state_jobs_on_lane(c, jobs, (uint32_t *)d_verdicts, (uint32_t *)d_flags, LI, LA, nullptr, LS);
-    c->hash_piece_waves = 0; c->hash_lds_bytes = 0; c->acc_first = false;
-    return rc;
+    StateJobPlan plan;
+    if ((rc = dev_fork_lanes(c, jobs->with_states ? jobs->batch * MINA_STATES_PER_PROOF : 0, plan))) return rc;
+    return mb_state_jobs_on_lane(c, jobs, (uint32_t *)d_verdicts, (uint32_t *)d_flags, plan);
 }
 
 // SURVEY.md 8e.2 for the WHOLE job (the `north_star` variant: "a single reduce of partial sums over xGMI"): this shard's proofs go through every stage of the
@@ -775,13 +766,10 @@ extern "C" int mina_state_job_fold_dev(mina_ctx *c, const mina_state_jobs *jobs,
     if (!c->have_state_salts && jobs->with_states) return fail(MINA_ERR_STATE, "call mina_state_jobs_prepare first");
     HIPC(hipSetDevice(c->device));
     c->next_lane();
-    mina_ctx::FoldExport fe; fe.ipa_scalars = (uint32_t *)d_ipa_scalars; fe.ipa_point = (uint32_t *)d_ipa_point; fe.acc_scalars = (uint32_t *)d_acc_scalars; fe.acc_point = (uint32_t *)d_acc_point;
-    c->fold_export = &fe;
-    Lane *LI = nullptr, *LA = nullptr, *LS = nullptr;
-    if (!(rc = dev_fork_lanes(c, jobs->with_states ? jobs->batch * MINA_STATES_PER_PROOF : 0, &LI, &LA, &LS))) rc = mb_state_jobs_on_lane(c, jobs, (uint32_t *)d_verdicts, (uint32_t *)d_flags, LI, LA, nullptr, LS);
-    c->hash_piece_waves = 0; c->hash_lds_bytes = 0; c->acc_first = false;
-    c->fold_export = nullptr;
-    return rc;
+    const FoldExport fe{(uint32_t *)d_ipa_scalars, (uint32_t *)d_ipa_point, (uint32_t *)d_acc_scalars, (uint32_t *)d_acc_point};
+    StateJobPlan plan; plan.fold_export = &fe;
+    if ((rc = dev_fork_lanes(c, jobs->with_states ? jobs->batch * MINA_STATES_PER_PROOF : 0, plan))) return rc;
+    return mb_state_jobs_on_lane(c, jobs, (uint32_t *)d_verdicts, (uint32_t *)d_flags, plan);
 }
 
 // host-buffer form: one upload of every section, the pipeline, one download; when a folded check fails the proofs are
@@ -837,8 +825,9 @@ extern "C" int mina_state_job_batch(mina_ctx *c, const mina_state_jobs *jobs, ui
     if ((rc = L.st_verdicts.ensure(2 * B * 4 + 16))) return rc;
     uint32_t *dv = L.st_verdicts.as<uint32_t>(), *df = dv + B, *ds = df + 4;
     // small, latency-bound batches: the three independent legs go to three lanes (lane 0 plus two helpers), joined by events
-    const bool split = B <= 1024 && c->nlanes == 1;
-    if ((rc = mb_state_jobs_on_lane(c, &d, dv, df, split ? &c->lanes[1] : nullptr, split ? &c->lanes[2] : nullptr, ds, nullptr))) return rc;
+    StateJobPlan plan; plan.d_stmt_out = ds;
+    if (B <= 1024 && c->nlanes == 1) { plan.wrap = &c->lanes[1]; plan.acc = &c->lanes[2]; }
+    if ((rc = mb_state_jobs_on_lane(c, &d, dv, df, plan))) return rc;
     std::vector<uint32_t> hv(2 * B + 4);
     if ((rc = d2h_sync(c, hv.data(), L.st_verdicts, (2 * B + 4) * 4))) return rc;
     std::vector<uint8_t> stmt_each(B); for (size_t b = 0; b < B; ++b) stmt_each[b] = hv[B + 4 + b] ? 1 : 0;
@@ -849,7 +838,7 @@ extern "C" int mina_state_job_batch(mina_ctx *c, const mina_state_jobs *jobs, ui
     {
         mina_state_jobs only = d; only.with_ipa = 0; only.with_accumulator = 0; only.npub = 0; only.kimchi = nullptr;
         if (only.with_states) {
-            if ((rc = mb_state_jobs_on_lane(c, &only, dv, df, nullptr, nullptr, nullptr, nullptr))) return rc;
+            if ((rc = mb_state_jobs_on_lane(c, &only, dv, df))) return rc;
             if ((rc = d2h_sync(c, hv.data(), L.st_verdicts, B * 4))) return rc;
             for (size_t b = 0; b < B; ++b) chain_each[b] = hv[b] ? 1 : 0;
         }
@@ -917,7 +906,7 @@ extern "C" int mina_state_job_batch(mina_ctx *c, const mina_state_jobs *jobs, ui
                     if (ipa_leg && rows_ok) { if ((r = mb_ipa_recheck_rows(c, lo, cnt, flags_at[q]))) return r; continue; }
                     mina_state_jobs sj = slice(d, lo, cnt);
                     if (ipa_leg) sj.with_accumulator = 0; else { sj.with_ipa = 0; sj.npub = 0; sj.kimchi = nullptr; }
-                    if ((r = mb_state_jobs_on_lane(c, &sj, v, flags_at[q], nullptr, nullptr, nullptr, nullptr))) return r;
+                    if ((r = mb_state_jobs_on_lane(c, &sj, v, flags_at[q]))) return r;
                 }
                 for (size_t q = 0; q < w; ++q) {
                     uint32_t f[4];

@@ -719,7 +719,12 @@ int run_device_shape(Device &D, const CallIn &in, const std::vector<size_t> &idx
     const bool own_up = tu.up_stream != 0;
     auto lane_forms = [&]() {       // the lane forms of the sponge kernels follow the work in flight on the device (ctx.h use_coop*)
         c->nlanes = (int)std::max(1u, std::min<unsigned>(D.inflight.load(), NSLOT));
-        c->hash_piece_waves = tu.hash_piece_waves;
+    };
+    const HashLaunch hash_launch{tu.hash_piece_waves, 0};      // a chunk's state hashes go out in pieces, early ones and the rest alike
+    auto chunk_plan = [&](Chunk &ch, uint32_t phase, uint32_t *d_stmt_out) {
+        StateJobPlan p; p.wrap = ch.LI; p.acc = ch.LA; p.states = ch.LS; p.phase = phase; p.carry = &ch.carry; p.d_stmt_out = d_stmt_out;
+        p.hashed_early = ch.hashed; p.hash = hash_launch;
+        return p;
     };
 
     // A chunk goes to the GPU in three steps, each as soon as its input is parsed (8192 full-size proofs per call: the job's wrap-proof chain
@@ -755,8 +760,7 @@ int run_device_shape(Device &D, const CallIn &in, const std::vector<size_t> &idx
         if (own_up) { HIPC(hipEventRecord(S.ev_up, up)); HIPC(hipStreamWaitEvent(L.stream, S.ev_up, 0)); }
         JobStructs js; make_jobs(sh, lay, dbase, ch.n, true, true, true, js);
         uint32_t *dv = (uint32_t *)(dbase + lay.out_off()), *df = dv + ch.n, *ds = df + 4;
-        rc = mb_state_jobs_on_lane(c, &js.j, dv, df, ch.LI, ch.LA, ds, ch.LS, MB_JOB_LEGS, &ch.carry);
-        c->hash_piece_waves = 0;
+        rc = mb_state_jobs_on_lane(c, &js.j, dv, df, chunk_plan(ch, MB_JOB_LEGS, ds));
         c->use_lane0();
         return rc;
     };
@@ -784,14 +788,13 @@ int run_device_shape(Device &D, const CallIn &in, const std::vector<size_t> &idx
             // hash_piece_states) -- = two waves on every SIMD of the state leg's 128 CUs): a run of
             // 1024 entries is 829 waves -- launched run by run, a fifth of the leg's SIMDs would hold one wave where the others hold two, for as long
             // The odd piece goes FIRST: it is complete after fewer runs, so the leg starts earlier, and it ends with a full piece instead of a half-empty one.
-            const size_t total = ch.n * MINA_STATES_PER_PROOF, piece = hash_piece_states(c, total), ready = hi * MINA_STATES_PER_PROOF;
+            const size_t total = ch.n * MINA_STATES_PER_PROOF, piece = hash_piece_states(c, total, hash_launch.piece_waves), ready = hi * MINA_STATES_PER_PROOF;
             const size_t first = piece ? (total % piece ? total % piece : piece) : 0;
             const size_t upto = (r + 1 == ch.nsub || !piece) ? ready : (ready < first ? 0 : first + (ready - first) / piece * piece);
             int rc = MINA_OK;
             if (upto > ch.hashed && !(flags & MINA_VERIFY_DEDUP_STATES))      // deduplicated: the whole state leg runs in finish() (a piece cannot know its duplicates in later pieces)
                 rc = mb_state_hashes_early(c, ch.LS ? ch.LS : &L, ch.n * MINA_STATES_PER_PROOF, ch.hashed, upto - ch.hashed,
-                                           (const uint32_t *)lay.at(dbase, S_REC, 0), (const uint32_t *)lay.at(dbase, S_NF, 0), S.rec_ev[r]);
-            c->hash_piece_waves = 0;
+                                           (const uint32_t *)lay.at(dbase, S_REC, 0), (const uint32_t *)lay.at(dbase, S_NF, 0), S.rec_ev[r], hash_launch);
             c->use_lane0();
             if (rc) return rc;
             if (!(flags & MINA_VERIFY_DEDUP_STATES)) ch.hashed = std::max(ch.hashed, upto);
@@ -813,11 +816,8 @@ int run_device_shape(Device &D, const CallIn &in, const std::vector<size_t> &idx
         if (own_up) { HIPC(hipEventRecord(S.ev_up, up)); HIPC(hipStreamWaitEvent(L.stream, S.ev_up, 0)); }
         JobStructs js; make_jobs(sh, lay, dbase, ch.n, true, true, true, js);
         uint32_t *dv = (uint32_t *)(dbase + lay.out_off()), *df = dv + ch.n, *ds = df + 4;
-        c->state_hashes_early = ch.hashed;
         { const bool want = (flags & MINA_VERIFY_DEDUP_STATES) != 0; int drc; if (want != c->state_dedup && (drc = mb_ctx_state_dedup(c, want))) return drc; }      // MINA_VERIFY_DEDUP_STATES: per chunk, under the device's lock
-        int rc = mb_state_jobs_on_lane(c, &js.j, dv, df, ch.LI, ch.LA, ds, ch.LS, MB_JOB_FINISH, &ch.carry);
-        c->state_hashes_early = 0;
-        c->hash_piece_waves = 0;
+        int rc = mb_state_jobs_on_lane(c, &js.j, dv, df, chunk_plan(ch, MB_JOB_FINISH, ds));
         c->use_lane0();
         if (rc) return rc;
         if (g_timing) HIPC(hipEventRecord(S.tev[2], L.stream));

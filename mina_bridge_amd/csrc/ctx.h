@@ -153,19 +153,10 @@ struct mina_ctx {
     bool pparams_surrogate[2] = {false, false};                  // the installed Poseidon tables are the library's UNPINNED surrogate set
     bool pparams_rows1[2] = {false, false};                      // the installed tables have the single-lane form's normalised rows (sponge.cuh PoseidonRows1: no zero on the MDS diagonal)
     DevBuf state_salts; bool have_state_salts = false;           // salted initial states of the named hash prefixes (Fp): MB_SALT_*
-    bool legs_forked = false;        // the job being queued runs its legs on separate streams (api_state.hip)
     bool is_view = false;            // a view of another context (mb_ctx_create_view: the culprit search's): creates no stream beyond its lane 0 -- its lanes 1 .. 3 borrow the failed chunk's, and the opening check's side stream is off
-    size_t state_hashes_early = 0;   // states of the next job's protocol-state leg already queued on its lane (mb_state_hashes_early), consumed by mb_state_jobs_on_lane
-    uint32_t hash_piece_waves = 0;   // > 0: the protocol-state hashes of a job are launched in pieces of this many waves (api_state.hip pstate_hash_dev)
-    uint32_t hash_lds_bytes = 0;     // > 0: dynamic LDS a state-hash workgroup reserves (3-lane or single-lane form), to cap its waves per SIMD beside the other legs of a forked job (mina_verify_tuning.dev_hash_lds_kb;
-                                     // by default only a lone job sets it, and a lone job hashes in the 3-lane form: hash_one_lane)
-    bool acc_first = false;          // forked device-resident job whose accumulator leg shares the hashes' stream: queue it AHEAD of them (mina_verify_tuning.dev_acc_lane = 2)
     bool state_dedup = false;        // the protocol-state leg of a job hashes each distinct record once (mina_ctx_set_state_dedup; api_state.hip pstate_hash_dedup_dev)
     DevBuf dedup_totals; uint64_t dedup_states = 0;   // mina_ctx_state_dedup_stats: {distinct, collisions} summed on the device by the legs' scan kernels, the states counted as they are queued
     uint32_t dev_fork_made = 0;      // the dev_fork value the helper lanes' streams were created under (streams keep their mask / priority for life)
-    // SURVEY.md 8e.2 (one exchange step over several GPUs): while set, the folded checks of a job do NOT run their fixed-base MSM and comparison -- they hand out
-    // this shard's folded scalar vector and the 17-word record of its variable-base partial sum instead (mina_state_job_fold_dev); device pointers
-    struct FoldExport { uint32_t *ipa_scalars = nullptr, *ipa_point = nullptr, *acc_scalars = nullptr, *acc_point = nullptr; } *fold_export = nullptr;
     void use_lane0() { L = &lanes[0]; }
     void next_lane() { L = pinned >= 0 ? &lanes[pinned] : &lanes[rr++ % (unsigned)nlanes]; }
 };
@@ -216,15 +207,15 @@ static inline bool use_coop8_transcripts(const mina_ctx *c, size_t batch, size_t
 // The protocol-state hashes of a leg of `leg_states` states run ONE lane per state (api_state.hip pstate_hash1_kernel: the fewest instructions per hash, the
 // longest chain per wave) when the installed tables have the normalised rows, several jobs are in flight and they hold HASH1_MIN_STATES states or more between
 // them (64 per wave: 65 536 are one wave per SIMD of the chip).  A lone job keeps the 3-lane form: its hashes run beside the job's own chain, as one launch
-// behind the LDS reservation tuned for that form (hash_lds_bytes), and a lone 4096-proof call would be one single-lane wave per SIMD.
+// behind the LDS reservation tuned for that form (HashLaunch::lds_bytes), and a lone 4096-proof call would be one single-lane wave per SIMD.
 static constexpr size_t HASH1_MIN_STATES = 65536;
 static inline int hash_jobs_in_flight(const mina_ctx *c) { return c->pinned >= 0 ? 1 : c->nlanes; }      // a pinned context runs one job at a time
 static inline bool hash_one_lane(const mina_ctx *c, size_t leg_states) {
     const int jobs = hash_jobs_in_flight(c);
     return c->pparams_rows1[FIELD_FP] && jobs >= 2 && leg_states * (size_t)jobs >= HASH1_MIN_STATES;
 }
-// states per launch piece of such a leg (0: one launch): `hash_piece_waves` waves of the form that runs -- 64 states each in the single-lane form, 21 in the 3-lane form
-static inline size_t hash_piece_states(const mina_ctx *c, size_t leg_states) { return (size_t)c->hash_piece_waves * (hash_one_lane(c, leg_states) ? 64u : 21u); }
+// states per launch piece of such a leg (0: one launch): `piece_waves` waves of the form that runs -- 64 states each in the single-lane form, 21 in the 3-lane form
+static inline size_t hash_piece_states(const mina_ctx *c, size_t leg_states, uint32_t piece_waves) { return (size_t)piece_waves * (hash_one_lane(c, leg_states) ? 64u : 21u); }
 
 // ---- the lane form of each kind of sponge work: lanes per sponge, launched through with_lanes below.  Each site has exactly one of these rules.
 // Salted hashes (the account hashes; the protocol-state hashes behind their single-lane test): `proofs` decides the 16-lane form, `sponges` the 8-lane one.
@@ -250,11 +241,27 @@ static inline int merkle_lanes(const mina_ctx *c, size_t paths) { return use_coo
 // ---- the Proof-of-State job on the lanes of a context (api_state.hip); every pointer of `j` is a device pointer
 enum : uint32_t { MB_JOB_LEGS = 1, MB_JOB_FINISH = 2, MB_JOB_ALL = 3 };
 struct StateJobCarry { uint32_t *ipa_v = nullptr, *acc_v = nullptr, *kimchi_bad = nullptr; const uint32_t *stmt_ok = nullptr; };
-int mb_state_jobs_on_lane(mina_ctx *c, const mina_state_jobs *j, uint32_t *d_verdicts, uint32_t *d_flags, Lane *LI, Lane *LA, uint32_t *d_stmt_out, Lane *LS,
-                          uint32_t phase = MB_JOB_ALL, StateJobCarry *carry = nullptr);
+// How the protocol-state hashes of a leg are launched (api_state.hip pstate_hash_launch).  piece_waves > 0: in pieces of this many waves of the form that runs
+// (hash_piece_states).  lds_bytes > 0: dynamic LDS a state-hash workgroup reserves (3-lane or single-lane form), to cap its waves per SIMD beside the other legs of
+// a forked job (mina_verify_tuning.dev_hash_lds_kb; by default only a lone job reserves, and a lone job hashes in the 3-lane form: hash_one_lane).
+struct HashLaunch { uint32_t piece_waves = 0, lds_bytes = 0; };
+// SURVEY.md 8e.2 (one exchange step over several GPUs): given one, the folded checks of a job do NOT run their fixed-base MSM and comparison -- they hand out
+// this shard's folded scalar vector and the 17-word record of its variable-base partial sum instead (mina_state_job_fold_dev); device pointers
+struct FoldExport { uint32_t *ipa_scalars = nullptr, *ipa_point = nullptr, *acc_scalars = nullptr, *acc_point = nullptr; };
+// How ONE job is queued: decided by the caller (api_state.hip dev_fork_lanes, the boundary's chunks in api_verify.hip), read by mb_state_jobs_on_lane and its legs.
+struct StateJobPlan {
+    Lane *wrap = nullptr, *acc = nullptr, *states = nullptr;   // helper lanes of the wrap-proof / accumulator / protocol-state legs; null = the current lane
+    uint32_t phase = MB_JOB_ALL; StateJobCarry *carry = nullptr;
+    uint32_t *d_stmt_out = nullptr;                             // [batch] or null: the per-proof "Pickles statement well-formed" words
+    size_t hashed_early = 0;                                    // states of the protocol-state leg already queued on its lane by mb_state_hashes_early
+    HashLaunch hash;
+    bool acc_first = false;                                     // the accumulator leg shares the hashes' lane: queue it AHEAD of them (mina_verify_tuning.dev_acc_lane = 2)
+    const FoldExport *fold_export = nullptr;
+};
+int mb_state_jobs_on_lane(mina_ctx *c, const mina_state_jobs *j, uint32_t *d_verdicts, uint32_t *d_flags, const StateJobPlan &plan = {});
 int mb_verify_account_on(mina_ctx *c, size_t n, const uint8_t *const *proofs, const size_t *proof_lens, const uint8_t *const *pubs, const size_t *pub_lens,
                          uint32_t *passed, uint32_t *ran, Lane *lane, std::mutex *enq_mu);   // api_account.hip: Proof-of-Account on a lane of the caller's choice
-int mb_state_hashes_early(mina_ctx *c, Lane *LS, size_t ns_total, size_t lo, size_t cnt, const uint32_t *d_records, const uint32_t *d_nfields, hipEvent_t after);
+int mb_state_hashes_early(mina_ctx *c, Lane *LS, size_t ns_total, size_t lo, size_t cnt, const uint32_t *d_records, const uint32_t *d_nfields, hipEvent_t after, HashLaunch hash);
 
 // ---- host-side worker pool (api_core.hip): persistent threads, created on first use -- min(hardware threads / 2, 64), $MINA_HOST_THREADS
 // overrides.  A job is `n` independent items handed out in index order; `mb_pool_submit` returns at once (the boundary's pipeline parses
@@ -342,9 +349,9 @@ struct IpaDevIn {     // structure-of-arrays over the batch, canonical little-en
     IpaExpand expand;
 };
 }
-int mb_ipa_batch_check_dev(mina_ctx *c, int curve, mb::IpaShape sh, const mb::IpaDevIn &in, uint32_t *d_verdict /* [0] verdict, [1] malformed flag */);
+int mb_ipa_batch_check_dev(mina_ctx *c, int curve, mb::IpaShape sh, const mb::IpaDevIn &in, uint32_t *d_verdict /* [0] verdict, [1] malformed flag */, const FoldExport *fx = nullptr);
 int mb_ipa_recheck_rows(mina_ctx *c, size_t lo, size_t cnt, uint32_t *d_verdict /* [0] verdict */);   // folded check of proofs [lo, lo + cnt) of the batch prepared last, from its rows; on the current lane
-int mb_accumulator_check_dev(mina_ctx *c, int curve, uint32_t k, size_t batch, const uint32_t *d_prechal, const uint32_t *d_sg_words, const uint32_t *d_rho, uint32_t *d_verdict);
+int mb_accumulator_check_dev(mina_ctx *c, int curve, uint32_t k, size_t batch, const uint32_t *d_prechal, const uint32_t *d_sg_words, const uint32_t *d_rho, uint32_t *d_verdict, const FoldExport *fx = nullptr);
 
 // cross-file entry points (C++ linkage)
 struct xyzz_dev;   // opaque: mb::xyzz_t in HBM

@@ -57,13 +57,14 @@ int mb_step_index_feature_aware(mina_ctx *) { return 0; }
 int mb_kimchi_available(mina_ctx *c) { return c->have_kimchi ? 1 : 0; }
 extern "C" int mina_merkle_verify_batch(mina_ctx *, int, size_t n, uint32_t, const uint8_t *, const uint8_t *, const uint8_t *, const uint8_t *, uint8_t *ok) { for (size_t i = 0; i < n; ++i) ok[i] = 1; return MINA_OK; }
 
-int mb_state_hashes_early(mina_ctx *c, Lane *LS, size_t ns_total, size_t lo, size_t cnt, const uint32_t *, const uint32_t *, hipEvent_t) {
+int mb_state_hashes_early(mina_ctx *c, Lane *LS, size_t ns_total, size_t lo, size_t cnt, const uint32_t *, const uint32_t *, hipEvent_t, HashLaunch) {
     if (!LS || lo + cnt > ns_total) return mb_fail(MINA_ERR_ARG, "bad early state range");
-    c->state_hashes_early = lo + cnt;       // (what the real one leaves for mb_state_jobs_on_lane: written under the device's lock, like the real field)
+    Lane *const keep = c->L; c->L = LS; c->L = keep;       // (the real one hashes with LS as the current lane: a write to the context, under the device's lock)
     return MINA_OK;
 }
 // the job on a lane: verdict words as the verdict kernel writes them -- d_verdicts[b] = precheck[b] AND no folded failure; flags = {opening fold ok, 0, accumulator fold ok, 0}
-int mb_state_jobs_on_lane(mina_ctx *c, const mina_state_jobs *j, uint32_t *d_verdicts, uint32_t *d_flags, Lane *, Lane *, uint32_t *d_stmt_out, Lane *, uint32_t phase, StateJobCarry *carry) {
+int mb_state_jobs_on_lane(mina_ctx *c, const mina_state_jobs *j, uint32_t *d_verdicts, uint32_t *d_flags, const StateJobPlan &plan) {
+    const uint32_t phase = plan.phase; StateJobCarry *const carry = plan.carry; uint32_t *const d_stmt_out = plan.d_stmt_out;
     if (phase != MB_JOB_ALL && !carry) return mb_fail(MINA_ERR_ARG, "a split job needs a carry");
     const size_t B = j->batch;
     Lane &L = *c->L;
@@ -77,7 +78,7 @@ int mb_state_jobs_on_lane(mina_ctx *c, const mina_state_jobs *j, uint32_t *d_ver
         if (phase == MB_JOB_LEGS) { carry->ipa_v = w + 4; carry->acc_v = w + 8; return MINA_OK; }
     }
     const uint32_t ipa_ok = j->with_ipa ? (phase == MB_JOB_FINISH ? carry->ipa_v[0] : w[4]) : 1u, acc_ok = 1u;
-    c->state_hashes_early = 0;
+    c->L = plan.states ? plan.states : &L; c->L = &L;         // (the real legs switch the current lane and the driver restores it: the context field the device's lock protects)
     for (size_t b = 0; b < B; ++b) {
         const uint32_t pre = j->precheck ? ((const uint8_t *)j->precheck)[b] : 1u;
         d_verdicts[b] = (pre && ipa_ok && acc_ok) ? 1u : 0u;
