@@ -59,6 +59,10 @@ func (c *Ctx) StateDedupStats() (states, distinct, collisions uint64, err error)
 // ConfigureDedupStates: the process-wide boundary (VerifyMinaState and its batch form) deduplicates the protocol states of each chunk; other flags are kept by the caller.
 func ConfigureDedupStates(otherFlags uint32) { C.mina_verify_configure(C.uint32_t(otherFlags) | C.MINA_VERIFY_DEDUP_STATES) }
 
+// ConfigurePackOnDevice: the process-wide boundary uploads each chunk's protocol-state bytes as they are and packs / pre-checks them on the GPU
+// (mina_state_frontend_dev; bincode only); off by default, verdicts unchanged; other flags are kept by the caller.
+func ConfigurePackOnDevice(otherFlags uint32) { C.mina_verify_configure(C.uint32_t(otherFlags) | C.MINA_VERIFY_PACK_ON_DEVICE) }
+
 // AccumulatorCheckMulti: one deterministic verdict per proof (len(sg)/64 proofs).
 func (c *Ctx) AccumulatorCheckMulti(curve int, k uint32, pre, sg []byte) ([]bool, error) {
 	n := len(sg) / 64

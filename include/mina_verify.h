@@ -372,6 +372,28 @@ int mina_ctx_set_state_dedup(mina_ctx *ctx, int on);
 /* Waits for the context; states that went through a deduplicated leg, the distinct ones among them, and fingerprint collisions, summed since the context was
  * created or the mode was last switched on.  Any of the three pointers may be NULL. */
 int mina_ctx_state_dedup_stats(mina_ctx *ctx, uint64_t *states, uint64_t *distinct, uint64_t *collisions);
+/* ---- protocol states packed on the device (opt-in; changes NO result) -----------------------------------------------
+ * mina_protocol_state_pack for states whose bytes already sit in HBM, and the rest of what the boundary's host pool does per proof before a job starts: find where
+ * each of a proof's 17 consecutive states ends, compare the 16 ledger hashes, run chain selection between the candidate tip (state 15) and the bridge tip
+ * (state 16).  Records, field counts, info structs, status bytes, `precheck` bytes and masks are bit-identical to the host path (mina_protocol_state_pack,
+ * mina_consensus_select_secure_chain, the checks behind mina_verify_state_checks) for every input, malformed ones included: same length checks, four 32-byte
+ * strings, at most 64 sub-windows, variant tags and booleans in range, 40 canonical field elements, at most MINA_PSTATE_SLOTS - 1 elements, the slice consumed
+ * exactly.  No encoding argument: the device reads the bincode form (MINA_ENC_BINCODE) only -- the form inside `MinaStateProof`, the only one a verifier is handed;
+ * bin_prot stays with the host reader.
+ * Device pointers, queued on the next pipeline lane (the pinned one under mina_ctx_pin_lane), no host synchronisation.  d_records: MINA_PSTATE_SLOTS*32 bytes per
+ * state, 16-byte aligned; d_nfields: u32 per state.  A null or misaligned argument: MINA_ERR_ARG.
+ * State i is bytes [d_off[i], d_off[i] + d_len[i]) of the blob and must fill them exactly.  d_status[i] = 1: accepted; 0: rejected -- the record is then zero and
+ * the field count 0 (d_info[i] undefined); a slice that reaches past blob_len is rejected, not a fault. */
+int mina_protocol_state_pack_dev(mina_ctx *ctx, size_t n, const void *d_blob, size_t blob_len, const void *d_off /* n u64 */, const void *d_len /* n u32 */,
+                                 void *d_records, void *d_nfields, void *d_info /* n mina_protocol_state_info, or NULL */, void *d_status /* n u8 */);
+/* Proof b's 17 states are bytes [d_begin[b], d_end[b]) of the blob, one behind the other.  d_precheck[b] = LEDGER and CONSENSUS and (d_and ? d_and[b] != 0 : 1),
+ * as mina_state_jobs.precheck takes it; d_masks[b] = the MINA_CHECK_FORMAT / _LEDGER / _CONSENSUS bits that passed.  A proof that fails FORMAT (a state rejected,
+ * or the last one not ending at d_end[b], or a range past blob_len) gets zero records, zero field counts, precheck 0 and mask 0.  d_ledger_hashes: 8-byte aligned. */
+int mina_state_frontend_dev(mina_ctx *ctx, size_t batch, const void *d_blob, size_t blob_len,
+                            const void *d_begin, const void *d_end /* batch u64 each: the 17 states of proof b */,
+                            const void *d_expected_hashes /* batch*17*32, as mina_state_jobs.expected_hashes */,
+                            const void *d_ledger_hashes /* batch*16*32 */, const void *d_and /* batch u8 or NULL: host-side bits to AND in */,
+                            void *d_records, void *d_nfields, void *d_precheck /* batch u8 */, void *d_masks /* batch u32 MINA_CHECK_{FORMAT,LEDGER,CONSENSUS}, or NULL */);
 /* serialized states in, state hashes out */
 int mina_protocol_state_hash_bytes(mina_ctx *ctx, int encoding, size_t n, const uint8_t *const *states, const size_t *lens,
                                    uint8_t *hashes_out /* n*32 */);
@@ -625,6 +647,9 @@ int mina_state_proof_split(const uint8_t *bytes, size_t len, size_t *proof_len, 
                                                   flag every mina_verify_* verdict is `false` on such a context. */
 #define MINA_VERIFY_DEDUP_STATES 8u          /* the boundary's process-wide contexts run with mina_ctx_set_state_dedup on: a chunk's state hashes are not queued
                                                   while the chunk is still being parsed; its whole state leg runs deduplicated, per chunk.  Verdicts are unchanged. */
+#define MINA_VERIFY_PACK_ON_DEVICE 16u       /* the boundary's host pool does not read the protocol states: a chunk's state bytes are uploaded as they are and
+                                                  mina_state_frontend_dev writes the records, field counts and `precheck` on the GPU; the state leg follows per chunk.
+                                                  Off by default; verdicts and masks are unchanged.  Works together with MINA_VERIFY_DEDUP_STATES. */
 #include <stdbool.h>
 bool mina_verify_state(const uint8_t *proof, size_t proof_len, const uint8_t *pub_input, size_t pub_len);
 int mina_verify_state_batch(size_t n, const uint8_t *const *proofs, const size_t *proof_lens, const uint8_t *const *pub_inputs,

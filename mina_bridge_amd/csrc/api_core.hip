@@ -65,6 +65,7 @@ extern "C" int mina_ctx_create(int device_id, mina_ctx **out) {
     c->use_lane0();
     c->fk[FIELD_FP] = make_field_consts<FIELD_FP>();
     c->fk[FIELD_FQ] = make_field_consts<FIELD_FQ>();
+    c->state_frontend = mb_state_frontend_on_lane;
     *out = c;
     return MINA_OK;
 }

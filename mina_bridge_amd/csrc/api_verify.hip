@@ -56,7 +56,7 @@ constexpr int NSLOT = 16;                  // most chunks in flight per device (
 // `up`: the slot's upload stream.  No copy of the pipeline waits for a kernel: the copy engines take their commands in order, and one that waits for a
 // kernel of its stream holds up the uploads of every other chunk queued behind it (calls of 65 536 proofs: the jobs of the 8 chunks started up to 300 ms
 // apart, rocprofv3 timeline).  So uploads have a stream of their own, and the verdict words go back through a kernel that writes the page-locked buffer.
-struct Slot { PinnedBuf host, out; DevBuf dev; hipStream_t up = nullptr; hipEvent_t ev = nullptr, ev_up = nullptr; hipEvent_t tev[3] = {nullptr, nullptr, nullptr}; std::vector<hipEvent_t> rec_ev; bool busy = false; };
+struct Slot { PinnedBuf host, out, pk_host /* MINA_VERIFY_PACK_ON_DEVICE: the front end's inputs (PackStage) */; DevBuf dev, pk_dev; hipStream_t up = nullptr; hipEvent_t ev = nullptr, ev_up = nullptr; hipEvent_t tev[3] = {nullptr, nullptr, nullptr}; std::vector<hipEvent_t> rec_ev; bool busy = false; };
 struct Device {
     mina_ctx *c = nullptr; int ordinal = 0;
     std::mutex mu;                         // serialises every call into `c` (a context has ONE current-lane cursor)
@@ -489,7 +489,19 @@ Config read_config(Device &D, uint32_t flags, int network) {
 
 struct CallIn { const uint8_t *const *proofs; const size_t *proof_lens; const uint8_t *const *pubs; const size_t *pub_lens; };
 
+// MINA_VERIFY_PACK_ON_DEVICE: what mina_state_frontend_dev reads for a chunk of n entries, one block in the slot's page-locked pk_host and its twin in pk_dev:
+// begin[n] u64 | end[n] u64 | ledger hashes n x 512 | and[n] u8 | (to 16 bytes) the entries' protocol-state bytes, one behind the other, as the callers sent them
+struct PackStage {
+    size_t n = 0, blob = 0, total = 0;
+    void build(size_t n_, size_t blob_bytes) { n = n_; blob = (529 * n + 15) & ~(size_t)15; total = blob + blob_bytes; }
+    template <class B> uint64_t *begin(B *base) const { return (uint64_t *)base; }
+    template <class B> uint64_t *end(B *base) const { return (uint64_t *)base + n; }
+    template <class B> uint8_t *ledger(B *base) const { return (uint8_t *)base + 16 * n; }
+    template <class B> uint8_t *band(B *base) const { return (uint8_t *)base + 528 * n; }
+    template <class B> uint8_t *bytes(B *base) const { return (uint8_t *)base + blob; }
+};
 struct Chunk {
+    PackStage pk;
     size_t lo = 0, n = 0; Slot *slot = nullptr; int slot_ix = -1; std::vector<HostBits> hb; bool issued = false, skipped = false, harvested = false;
     // two pool jobs per chunk: the wrap-proof halves of its entries (A), then the protocol-state halves (B) in `nsub` runs of `sub` entries -- the
     // records of a run go to the GPU, and their hashes are queued, as soon as the run is parsed
@@ -573,6 +585,10 @@ int run_device_shape(Device &D, const CallIn &in, const std::vector<size_t> &idx
     Layout lay; lay.build(sh, cap);
     mina_ctx *c = D.c;
     int rc_all = MINA_OK;
+    // MINA_VERIFY_PACK_ON_DEVICE: the pool parses the wrap-proof halves only; the protocol-state bytes of a chunk go to the GPU as they are and the front end
+    // (api_pack.hip, through the context's pointer: null in a context that links no kernel = the host path) writes S_REC / S_NF / S_PRE in the device staging.
+    // The state leg then runs whole in finish(), as under MINA_VERIFY_DEDUP_STATES.
+    const bool pack = (flags & MINA_VERIFY_PACK_ON_DEVICE) && c->state_frontend;
 
     auto try_acquire = [&]() -> int {
         std::lock_guard<std::mutex> lk(D.slot_mu);
@@ -582,6 +598,12 @@ int run_device_shape(Device &D, const CallIn &in, const std::vector<size_t> &idx
     auto release = [&](int s) { { std::lock_guard<std::mutex> lk(D.slot_mu); D.slots[s].busy = false; } D.slot_cv.notify_all(); };
 
     auto fallback = [&](Chunk &ch) -> int {     // a folded check of the chunk failed: per-proof verdicts through the culprit search, from the same staging
+        if (pack) {                               // ... whose records, field counts and `precheck` were made on the GPU (the chunk's job is complete: harvest waited for it)
+            uint8_t *hb_ = (uint8_t *)ch.slot->host.p; const uint8_t *db_ = ch.slot->dev.as<uint8_t>();
+            HIPC(hipSetDevice(c->device));
+            HIPC(hipMemcpy(hb_ + lay.off[S_REC], db_ + lay.off[S_REC], lay.off[S_EXP] - lay.off[S_REC], hipMemcpyDeviceToHost));
+            HIPC(hipMemcpy(hb_ + lay.off[S_PRE], db_ + lay.off[S_PRE], ch.n * lay.stride[S_PRE], hipMemcpyDeviceToHost));
+        }
         JobStructs js; make_jobs(sh, lay, (uint8_t *)ch.slot->host.p, ch.n, true, true, true, js);
         std::vector<uint8_t> v(ch.n, 0);
         const auto t = std::chrono::steady_clock::now();
@@ -811,9 +833,16 @@ int run_device_shape(Device &D, const CallIn &in, const std::vector<size_t> &idx
         c->L = &L;
         uint8_t *dbase = S.dev.as<uint8_t>();
         hipStream_t up = own_up ? S.up : L.stream;
-        HIPC(hipMemcpyAsync(lay.at(dbase, S_PRE, 0), lay.at(hbase, S_PRE, 0), ch.n * lay.stride[S_PRE], hipMemcpyHostToDevice, up));
+        if (pack) { int prc; if ((prc = S.pk_dev.ensure(ch.pk.total))) return prc; HIPC(hipMemcpyAsync(S.pk_dev.p, S.pk_host.p, ch.pk.total, hipMemcpyHostToDevice, up)); }
+        else HIPC(hipMemcpyAsync(lay.at(dbase, S_PRE, 0), lay.at(hbase, S_PRE, 0), ch.n * lay.stride[S_PRE], hipMemcpyHostToDevice, up));
         if (g_timing) HIPC(hipEventRecord(S.tev[1], up));
         if (own_up) { HIPC(hipEventRecord(S.ev_up, up)); HIPC(hipStreamWaitEvent(L.stream, S.ev_up, 0)); }
+        if (pack) {       // records, field counts and `precheck` of the chunk, on its lane ahead of the state leg (which forks from this lane)
+            uint8_t *pd = S.pk_dev.as<uint8_t>();
+            int prc = c->state_frontend(c, ch.n, ch.pk.bytes(pd), ch.pk.total - ch.pk.blob, ch.pk.begin(pd), ch.pk.end(pd), lay.at(dbase, S_EXP, 0), ch.pk.ledger(pd), ch.pk.band(pd),
+                                        lay.at(dbase, S_REC, 0), lay.at(dbase, S_NF, 0), lay.at(dbase, S_PRE, 0), nullptr);
+            if (prc) { c->use_lane0(); return prc; }
+        }
         JobStructs js; make_jobs(sh, lay, dbase, ch.n, true, true, true, js);
         uint32_t *dv = (uint32_t *)(dbase + lay.out_off()), *df = dv + ch.n, *ds = df + 4;
         { const bool want = (flags & MINA_VERIFY_DEDUP_STATES) != 0; int drc; if (want != c->state_dedup && (drc = mb_ctx_state_dedup(c, want))) return drc; }      // MINA_VERIFY_DEDUP_STATES: per chunk, under the device's lock
@@ -828,6 +857,35 @@ int run_device_shape(Device &D, const CallIn &in, const std::vector<size_t> &idx
         return MINA_OK;
     };
 
+    // MINA_VERIFY_PACK_ON_DEVICE, once the wrap-proof halves of a chunk are parsed (they say where an entry's states begin): lay out the front end's inputs and let
+    // the pool copy every entry's state bytes and ledger hashes into them -- a copy, no byte of a state is looked at.  An entry whose first half did not parse
+    // gets an empty range: FORMAT fails on the device, its records are zero and its `precheck` 0, as clear_states_half leaves them on the host path.
+    auto gather_states = [&](Chunk &ch) -> int {
+        size_t total = 0;
+        std::vector<uint64_t> at(ch.n + 1, 0);
+        for (size_t b = 0; b < ch.n; ++b) {
+            HostBits &hb = ch.hb[b]; const size_t q = idx[ch.lo + b];
+            hb.parsed = hb.proof_ok;                                  // the rest of FORMAT is the device's: it reaches the verdict through `precheck`
+            at[b] = total; if (hb.proof_ok) total += in.proof_lens[q] - hb.states_at;
+        }
+        at[ch.n] = total;
+        ch.pk.build(ch.n, total);
+        if (ch.slot->pk_host.ensure(ch.pk.total)) return MINA_ERR_HIP;
+        uint8_t *ph = (uint8_t *)ch.slot->pk_host.p;
+        uint64_t *pb = ch.pk.begin(ph), *pe = ch.pk.end(ph);
+        for (size_t b = 0; b < ch.n; ++b) { pb[b] = at[b]; pe[b] = ch.hb[b].proof_ok ? at[b + 1] : at[b]; }
+        memset(ph + 529 * ch.n, 0, ch.pk.blob - 529 * ch.n);
+        Chunk *chp = &ch;
+        ch.jobB = mb_pool_submit(ch.n, [&, chp, ph](size_t b) {
+            const HostBits &hb = chp->hb[b]; const size_t q = idx[chp->lo + b];
+            const uint64_t lo = chp->pk.begin(ph)[b], hi = chp->pk.end(ph)[b];
+            chp->pk.band(ph)[b] = (hb.proof_ok && hb.shape) ? 1 : 0;
+            if (hb.proof_ok) { memcpy(chp->pk.ledger(ph) + 512 * b, in.pubs[q] + 545, 512); memcpy(chp->pk.bytes(ph) + lo, in.proofs[q] + hb.states_at, hi - lo); }      // (proof_ok: the public input has its 1057 bytes)
+            else memset(chp->pk.ledger(ph) + 512 * b, 0, 512);
+        });
+        return MINA_OK;
+    };
+
     size_t next_submit = 0, next_issue = 0, oldest = 0;
     auto t_issued = t_call;
     while (next_issue < nchunks && !rc_all) {
@@ -839,7 +897,7 @@ int run_device_shape(Device &D, const CallIn &in, const std::vector<size_t> &idx
             if (ch.slot->host.ensure(lay.total) || ch.slot->out.ensure(Layout::out_bytes(lay.cap))) { release(s); ch.slot = nullptr; ch.slot_ix = -1; rc_all = MINA_ERR_HIP; break; }
             uint8_t *hbase = (uint8_t *)ch.slot->host.p;
             Chunk *chp = &ch;
-            ch.sub = (early_sub && ch.n >= early_min) ? early_sub : ch.n; ch.nsub = (ch.n + ch.sub - 1) / ch.sub;
+            ch.sub = (early_sub && ch.n >= early_min && !pack) ? early_sub : ch.n; ch.nsub = (ch.n + ch.sub - 1) / ch.sub;
             ch.sub_left.reset(new std::atomic<uint32_t>[ch.nsub]);
             for (size_t r = 0; r < ch.nsub; ++r) ch.sub_left[r].store((uint32_t)(std::min(ch.n, (r + 1) * ch.sub) - r * ch.sub));
             // the pool's order per chunk: the FIRST run whole (both halves: the state leg is the later one of a lone job, its first piece of hashes needs
@@ -858,7 +916,7 @@ int run_device_shape(Device &D, const CallIn &in, const std::vector<size_t> &idx
                 const size_t b = head + i, q = idx[chp->lo + b];
                 parse_proof_half(sh, lay, hbase, b, in.proofs[q], in.proof_lens[q], in.pubs[q], in.pub_lens[q], chp->hb[b], c);
             });
-            ch.jobB = mb_pool_submit(ch.n - head, [&, chp, hbase, head, run_done](size_t i) {
+            ch.jobB = mb_pool_submit(pack ? 0 : ch.n - head, [&, chp, hbase, head, run_done](size_t i) {      // (packed on the device: gather_states below, once job A is through)
                 mb_pool_wait(chp->jobA);                                  // the pool hands jobs out in order, but the last items of A may still be running
                 const size_t b = head + i, q = idx[chp->lo + b];
                 parse_states_half(lay, hbase, b, in.proofs[q], in.proof_lens[q], in.pubs[q], in.pub_lens[q], chp->hb[b]);
@@ -887,9 +945,10 @@ int run_device_shape(Device &D, const CallIn &in, const std::vector<size_t> &idx
         int rc = ch.head ? stream_records(ch, 0, 1) : MINA_OK;          // the first run's records and hashes, ahead of everything else
         mb_pool_wait(ch.jobH); mb_pool_wait(ch.jobA);
         const double t_a = g_timing ? ms_since(t_call) : 0;
+        if (!rc && pack) rc = gather_states(ch);
         if (!rc) rc = issue_legs(ch);
         const double t_legs = g_timing ? ms_since(t_call) : 0;
-        if (!rc && !ch.skipped) rc = stream_records(ch, ch.head ? 1 : 0, ch.nsub);
+        if (!rc && !ch.skipped && !pack) rc = stream_records(ch, ch.head ? 1 : 0, ch.nsub);
         mb_pool_wait(ch.jobB);
         const double t_parsed = g_timing ? ms_since(t_call) : 0;
         if (!rc && !ch.skipped) rc = finish(ch);
@@ -966,7 +1025,35 @@ int state_checks(const uint8_t *proof, size_t proof_len, const uint8_t *pub, siz
     Layout lay; lay.build(sh, 1);
     std::vector<uint8_t> stage(lay.total + 256);
     HostBits hb;
-    parse_into(sh, lay, stage.data(), 0, proof, proof_len, pub, pub_len, hb, D->c);
+    if ((flags & MINA_VERIFY_PACK_ON_DEVICE) && D->c->state_frontend) {
+        // the second half on the GPU: records and field counts come back into the staging, the FORMAT / LEDGER / CONSENSUS bits with them as the front end's mask
+        parse_proof_half(sh, lay, stage.data(), 0, proof, proof_len, pub, pub_len, hb, D->c);
+        if (!hb.proof_ok) return MINA_OK;
+        PackStage pk; pk.build(1, proof_len - hb.states_at);
+        std::vector<uint8_t> hin(pk.total, 0);
+        pk.begin(hin.data())[0] = 0; pk.end(hin.data())[0] = proof_len - hb.states_at;
+        memcpy(pk.ledger(hin.data()), pub + 545, 512); pk.band(hin.data())[0] = 1;
+        memcpy(pk.bytes(hin.data()), proof + hb.states_at, proof_len - hb.states_at);
+        const size_t o_rec = 0, o_nf = lay.stride[S_REC], o_pre = o_nf + 256, o_mask = o_pre + 256, o_exp = o_mask + 256, o_end = o_exp + lay.stride[S_EXP];
+        std::vector<uint8_t> hout(o_exp);
+        {
+            std::lock_guard<std::mutex> lk(D->mu);
+            mina_ctx *c = D->c;
+            HIPC(hipSetDevice(c->device));
+            c->use_lane0();
+            Lane &L = *c->L;
+            int rc;
+            if ((rc = h2d(c, L.tmp_a, hin.data(), hin.size())) || (rc = L.tmp_b.ensure(o_end))) return rc;
+            uint8_t *di = L.tmp_a.as<uint8_t>(), *dout = L.tmp_b.as<uint8_t>();
+            HIPC(hipMemcpyAsync(dout + o_exp, lay.at(stage.data(), S_EXP, 0), lay.stride[S_EXP], hipMemcpyHostToDevice, L.stream));
+            if ((rc = c->state_frontend(c, 1, pk.bytes(di), pk.total - pk.blob, pk.begin(di), pk.end(di), dout + o_exp, pk.ledger(di), pk.band(di), dout + o_rec, dout + o_nf, dout + o_pre, dout + o_mask))) return rc;
+            if ((rc = d2h_sync(c, hout.data(), L.tmp_b, o_exp))) return rc;
+        }
+        uint32_t mask; memcpy(&mask, hout.data() + o_mask, 4);
+        memcpy(lay.at(stage.data(), S_REC, 0), hout.data() + o_rec, lay.stride[S_REC]); memcpy(lay.at(stage.data(), S_NF, 0), hout.data() + o_nf, lay.stride[S_NF]);
+        hb.parsed = (mask & MINA_CHECK_FORMAT) != 0; hb.ledger = (mask & MINA_CHECK_LEDGER) != 0; hb.consensus = (mask & MINA_CHECK_CONSENSUS) != 0;
+    } else
+        parse_into(sh, lay, stage.data(), 0, proof, proof_len, pub, pub_len, hb, D->c);
     if (!hb.parsed) return MINA_OK;
     passed |= MINA_CHECK_FORMAT; ran |= MINA_CHECK_LEDGER | MINA_CHECK_CONSENSUS;
     if (hb.ledger) passed |= MINA_CHECK_LEDGER;

@@ -36,6 +36,7 @@ EXPORTS = [
     "mina_consensus_project_window", "mina_consensus_relative_min_window_density", "mina_consensus_is_short_range",
     "mina_protocol_state_pack", "mina_protocol_state_hash_batch", "mina_protocol_state_hash_bytes",
     "mina_protocol_state_dedup_dev", "mina_protocol_state_hash_batch_dedup", "mina_ctx_set_state_dedup", "mina_ctx_state_dedup_stats",
+    "mina_protocol_state_pack_dev", "mina_state_frontend_dev",
     "mina_state_jobs_prepare", "mina_state_job_batch_dev", "mina_state_job_batch", "mina_state_job_fold_dev",
     "mina_challenge_to_field_dev", "mina_field_sum_rows_dev", "mina_msm_srs_range_dev", "mina_msm_dev", "mina_points_sum_dev", "mina_point_records_equal_dev",
     "mina_step_index_install", "mina_step_index_load_json", "mina_polish_tokens_from_json", "mina_verifier_index_load_json", "mina_pickles_public_input",
@@ -236,6 +237,7 @@ class KimchiBatchOut(ctypes.Structure):
 CHECK_FORMAT, CHECK_LEDGER, CHECK_CHAIN, CHECK_CONSENSUS, CHECK_ACCUMULATOR, CHECK_KIMCHI, CHECK_ACCOUNT_ABI, CHECK_MERKLE = 1, 2, 4, 8, 16, 32, 64, 128
 VERIFY_ALLOW_MISSING_KIMCHI, VERIFY_ALLOW_UNBOUND_STATEMENT, VERIFY_ALLOW_SURROGATE = 1, 2, 4
 VERIFY_DEDUP_STATES = 8   # the boundary hashes each distinct protocol state of a chunk once (MinaContext.set_state_dedup on its contexts); verdicts unchanged
+VERIFY_PACK_ON_DEVICE = 16   # the boundary packs and pre-checks the protocol states of a chunk on the GPU (MinaContext.state_frontend_dev) instead of on its host pool; verdicts unchanged
 
 
 def _bytes_arg(b):
@@ -972,6 +974,21 @@ class MinaContext:
         queued on the next pipeline lane.  fingerprint_bits 1..32 cuts the fingerprint (the collision path under test): the results do not depend on it"""
         self._ck(self._lib.mina_protocol_state_dedup_dev(self._h, ctypes.c_size_t(n), ctypes.c_void_p(d_records), ctypes.c_void_p(d_nfields), ctypes.c_void_p(d_rep),
                                                          ctypes.c_void_p(d_counts), ctypes.c_uint32(fingerprint_bits)), "mina_protocol_state_dedup_dev")
+
+    def protocol_state_pack_dev(self, n: int, d_blob: int, blob_len: int, d_off: int, d_len: int, d_records: int, d_nfields: int, d_info: int, d_status: int):
+        """`protocol_state_pack` (bincode) for n serialized states in HBM: state i = bytes [off[i], off[i] + len[i]) of the blob -> record, field count, info struct
+        (d_info may be 0) and a status byte each; device pointers, queued on the next pipeline lane.  A rejected state has status 0 and a zeroed record"""
+        self._ck(self._lib.mina_protocol_state_pack_dev(self._h, ctypes.c_size_t(n), ctypes.c_void_p(d_blob), ctypes.c_size_t(blob_len), ctypes.c_void_p(d_off), ctypes.c_void_p(d_len),
+                                                        ctypes.c_void_p(d_records), ctypes.c_void_p(d_nfields), ctypes.c_void_p(d_info or None), ctypes.c_void_p(d_status)),
+                 "mina_protocol_state_pack_dev")
+
+    def state_frontend_dev(self, batch: int, d_blob: int, blob_len: int, d_begin: int, d_end: int, d_expected_hashes: int, d_ledger_hashes: int, d_and: int,
+                           d_records: int, d_nfields: int, d_precheck: int, d_masks: int = 0):
+        """the front half of a Proof-of-State job on the GPU: the 17 consecutive serialized states of proof b (bytes [begin[b], end[b]) of the blob) -> the records,
+        field counts and `precheck` bytes `state_job_batch_dev` takes, and the CHECK_FORMAT / _LEDGER / _CONSENSUS masks (d_and, d_masks may be 0)"""
+        self._ck(self._lib.mina_state_frontend_dev(self._h, ctypes.c_size_t(batch), ctypes.c_void_p(d_blob), ctypes.c_size_t(blob_len), ctypes.c_void_p(d_begin), ctypes.c_void_p(d_end),
+                                                   ctypes.c_void_p(d_expected_hashes), ctypes.c_void_p(d_ledger_hashes), ctypes.c_void_p(d_and or None), ctypes.c_void_p(d_records),
+                                                   ctypes.c_void_p(d_nfields), ctypes.c_void_p(d_precheck), ctypes.c_void_p(d_masks or None)), "mina_state_frontend_dev")
 
     def set_state_dedup(self, on: bool = True):
         """the protocol-state leg of state_job_batch / _batch_dev / _fold_dev hashes each distinct record of a job once (default off; no result changes)"""
