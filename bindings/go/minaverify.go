@@ -63,6 +63,10 @@ func ConfigureDedupStates(otherFlags uint32) { C.mina_verify_configure(C.uint32_
 // (mina_state_frontend_dev; bincode only); off by default, verdicts unchanged; other flags are kept by the caller.
 func ConfigurePackOnDevice(otherFlags uint32) { C.mina_verify_configure(C.uint32_t(otherFlags) | C.MINA_VERIFY_PACK_ON_DEVICE) }
 
+// ConfigureAccountOnDevice: VerifyAccountInclusion and its batch form upload a call's bytes as they are and run the whole Proof-of-Account job on the GPU
+// (mina_account_job_dev; bincode only); off by default, verdicts unchanged; other flags are kept by the caller.
+func ConfigureAccountOnDevice(otherFlags uint32) { C.mina_verify_configure(C.uint32_t(otherFlags) | C.MINA_VERIFY_ACCOUNT_ON_DEVICE) }
+
 // AccumulatorCheckMulti: one deterministic verdict per proof (len(sg)/64 proofs).
 func (c *Ctx) AccumulatorCheckMulti(curve int, k uint32, pre, sg []byte) ([]bool, error) {
 	n := len(sg) / 64

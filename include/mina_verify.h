@@ -650,6 +650,9 @@ int mina_state_proof_split(const uint8_t *bytes, size_t len, size_t *proof_len, 
 #define MINA_VERIFY_PACK_ON_DEVICE 16u       /* the boundary's host pool does not read the protocol states: a chunk's state bytes are uploaded as they are and
                                                   mina_state_frontend_dev writes the records, field counts and `precheck` on the GPU; the state leg follows per chunk.
                                                   Off by default; verdicts and masks are unchanged.  Works together with MINA_VERIFY_DEDUP_STATES. */
+#define MINA_VERIFY_ACCOUNT_ON_DEVICE 32u    /* mina_verify_account, _account_batch and _account_checks do not read a call's proofs on the host: the bytes are uploaded
+                                                  as they are and mina_account_job_dev's job parses, cross-checks, hashes, folds and compares on the GPU.  Off by
+                                                  default; verdicts and masks are unchanged.  A context without the device path or without Fp tables keeps the host path. */
 #include <stdbool.h>
 bool mina_verify_state(const uint8_t *proof, size_t proof_len, const uint8_t *pub_input, size_t pub_len);
 int mina_verify_state_batch(size_t n, const uint8_t *const *proofs, const size_t *proof_lens, const uint8_t *const *pub_inputs,
@@ -681,6 +684,32 @@ int mina_verify_account_ctx(mina_ctx *ctx, size_t n, const uint8_t *const *proof
  * MinaAccountProof) -> account hashes on the GPU / the ABI bytes of sol/account.rs:25-314 (host only; out may be NULL to query the length) */
 int mina_account_hash_batch(mina_ctx *ctx, int encoding, size_t n, const uint8_t *const *accounts, const size_t *lens, uint8_t *hashes_out /* n*32 */);
 int mina_account_abi_encode(const uint8_t *account, size_t len, int encoding, uint8_t *out, size_t cap, size_t *out_len);
+/* ---- Proof-of-Account from serialized bytes on the device (opt-in; changes NO result) --------------------------------
+ * What mina_verify_account_ctx does per pair -- mina_parse_merkle_path (depth <= 64), mina_parse_account_pub_inputs, the account reader (tags in range, symbol <= 6 and
+ * URI <= 255 bytes, every field element canonical, nothing behind the account), the byte comparison with mina_account_abi_encode, the four `to_input` records, the
+ * account hash, the Merkle fold and the comparison with the ledger hash -- for pairs whose bytes already sit in HBM, bit-identical to the host path for every
+ * input, malformed ones included.  No encoding argument: the device reads the bincode form (MINA_ENC_BINCODE) only -- the form inside `MinaAccountProof`, the only
+ * one a verifier is handed; bin_prot stays with the host reader.
+ * Pair i: proof = bytes [d_proof_off[i], + d_proof_len[i]) of the blob, public input = [d_pub_off[i], + d_pub_len[i]); u64 each, 8-byte aligned.  A slice that
+ * reaches past blob_len is rejected, not a fault.  Device pointers; both calls queue on the next pipeline lane (the pinned one under mina_ctx_pin_lane) and do not
+ * wait for the GPU (the first job of a context, or the first after mina_poseidon_set_params, prepares its salts and the default sub-hashes and waits for those).
+ * A null, misaligned or inconsistent argument: MINA_ERR_ARG, before any device is touched; no Fp Poseidon tables: MINA_ERR_STATE.
+ *
+ * mina_account_frontend_dev: the reader alone.  d_records / d_nfields / d_salt_idx hold 4 * n entries (a record = MINA_PSTATE_SLOTS*32 bytes, 16-byte aligned; slots
+ * past the field count are not written): stage s (0 zkApp URI, 1 verification key, 2 zkApp, 3 account) of entry k at [s * n + k].  The account stage is indexed by
+ * the pair; the three zkApp stages by the SLOT a pair whose account carries a zkApp takes in a compacted list: d_zk_index[slot] = pair, *d_zk_count = slots taken
+ * (in no particular order), d_zk_marks[i] = 1 for such a pair.  An account without a zkApp has no slot: its three sub-hashes are constants of the Poseidon tables.
+ * d_siblings / d_dirs: 64 entries per pair (32 bytes / 1 byte each), d_depths[i] of them written.  d_bits[i]: MINA_CHECK_FORMAT, MINA_CHECK_ACCOUNT_ABI (only with
+ * FORMAT), and 0x100 / 0x200 / 0x400 = the path / the public input / the account parsed.  A pair that fails FORMAT has field count 0 in every stage. */
+int mina_account_frontend_dev(mina_ctx *ctx, size_t n, const void *d_blob, size_t blob_len, const void *d_proof_off, const void *d_proof_len, const void *d_pub_off,
+                              const void *d_pub_len, void *d_records, void *d_nfields, void *d_salt_idx /* 4*n u32: index of the hash prefix */,
+                              void *d_siblings /* n*64*32, 16-byte aligned */, void *d_dirs /* n*64 */, void *d_depths /* n u32 */, void *d_ledger_hashes /* n*32, 16-byte aligned */,
+                              void *d_zk_marks /* n u32 */, void *d_zk_index /* n u32 */, void *d_zk_count /* 1 u32 */, void *d_bits /* n u32 */);
+/* The whole job: d_passed[i] / d_ran[i] = the masks mina_verify_account_ctx returns for pair i.  d_account_hashes / d_roots (n*32 bytes each, canonical words; may be
+ * NULL): the account hash and the folded root of every pair that passed FORMAT (undefined for the others).  Stream-ordered on its lane like
+ * mina_state_job_batch_dev; the caller synchronises (mina_ctx_sync). */
+int mina_account_job_dev(mina_ctx *ctx, size_t n, const void *d_blob, size_t blob_len, const void *d_proof_off, const void *d_proof_len, const void *d_pub_off,
+                         const void *d_pub_len, void *d_passed /* n u32 */, void *d_ran /* n u32 */, void *d_account_hashes, void *d_roots);
 int mina_verify_configure(uint32_t flags);       /* MINA_VERIFY_* */
 /* Tuning: every knob of the library in ONE struct instead of environment switches (the defaults are the measured optima on one MI355X, DESIGN.md
  * section 5; tests force other shapes to prove the verdicts do not depend on them).  Process-wide; set it before the first verification or between

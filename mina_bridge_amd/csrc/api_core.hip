@@ -66,6 +66,7 @@ extern "C" int mina_ctx_create(int device_id, mina_ctx **out) {
     c->fk[FIELD_FP] = make_field_consts<FIELD_FP>();
     c->fk[FIELD_FQ] = make_field_consts<FIELD_FQ>();
     c->state_frontend = mb_state_frontend_on_lane;
+    c->account_on_device = mb_verify_account_dev_on;
     *out = c;
     return MINA_OK;
 }
@@ -106,7 +107,7 @@ extern "C" void mina_ctx_destroy(mina_ctx *c) {
     (void)hipSetDevice(c->device);
     for (int i = 0; i < MB_MAX_LANES; ++i) if (c->lanes[i].stream) (void)hipStreamSynchronize(c->lanes[i].stream);
     for (int i = 0; i < 2; ++i) { c->srs[i].table.release(); c->srs[i].table29.release(); c->srs[i].table29s.release(); c->srs[i].h.release(); c->srs[i].lagrange_table.release(); c->srs[i].lagrange_digits.release(); c->srs[i].lagrange_digits29.release(); c->pparams[i].release(); c->merkle_salts[i].release(); }
-    c->state_salts.release(); c->dedup_totals.release(); c->kimchi_index.release(); c->kimchi_tokens.release(); c->kimchi_literals.release();
+    c->state_salts.release(); c->acct_defaults.release(); c->dedup_totals.release(); c->kimchi_index.release(); c->kimchi_tokens.release(); c->kimchi_literals.release();
     c->pickles_index.release(); c->pickles_tokens.release(); c->pickles_literals.release();
     if (c->step_host && c->step_host_free) c->step_host_free(c->step_host);
     c->step_host = nullptr;

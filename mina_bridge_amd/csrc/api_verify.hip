@@ -1194,10 +1194,21 @@ extern "C" int mina_state_proof_split(const uint8_t *bytes, size_t len, size_t *
 }
 
 // ------------------------------------------------------------------------------------------------ Proof of Account
+// MINA_VERIFY_ACCOUNT_ON_DEVICE: a call's bytes go to the GPU as they are and the whole job runs there (api_account_dev.hip, reached through the context's pointer:
+// the stand-in contexts of the ThreadSanitizer tier have none).  Without the pointer or without Fp tables the host path runs, with the answer it always gave.
+static bool account_on_device(Device *D, uint32_t flags) {
+    if (!(flags & MINA_VERIFY_ACCOUNT_ON_DEVICE) || !D->c->account_on_device) return false;
+    std::lock_guard<std::mutex> lk(D->mu);
+    return D->c->have_pparams[FIELD_FP];
+}
 extern "C" int mina_verify_account_checks(const uint8_t *proof, size_t proof_len, const uint8_t *pub, size_t pub_len, uint32_t *passed_mask, uint32_t *ran_mask) {
     if (!passed_mask || !ran_mask) return fail(MINA_ERR_ARG, "null argument");
-    Device *D;
-    { std::lock_guard<std::mutex> lk(g_mu); auto &ds = devices(); if (ds.empty()) return MINA_ERR_HIP; D = ds[0]; }
+    Device *D; uint32_t flags;
+    { std::lock_guard<std::mutex> lk(g_mu); auto &ds = devices(); if (ds.empty()) return MINA_ERR_HIP; D = ds[0]; flags = g_flags; }
+    if (account_on_device(D, flags)) {                           // MINA_VERIFY_ACCOUNT_ON_DEVICE: the device job, on the account lane like a batch call
+        std::lock_guard<std::mutex> acct(D->acct_mu);
+        return D->c->account_on_device(D->c, 1, &proof, &proof_len, &pub, &pub_len, passed_mask, ran_mask, &D->c->lanes[MB_PIPE_LANES - 1], &D->mu);
+    }
     std::lock_guard<std::mutex> lk(D->mu);
     return mina_verify_account_ctx(D->c, 1, &proof, &proof_len, &pub, &pub_len, passed_mask, ran_mask);
 }
@@ -1212,8 +1223,10 @@ static int account_batch_direct(size_t n, const uint8_t *const *proofs, const si
           if ((D->c->pparams_surrogate[0] || D->c->pparams_surrogate[1]) && !(flags & MINA_VERIFY_ALLOW_SURROGATE)) return MINA_OK; }   // surrogate Poseidon tables: refuse (see read_config)
         // one account job per device at a time, on a lane of its own (the last pipeline lane: no slot, no culprit search uses it); the device's lock is
         // taken only while its kernels are queued, so the state-proof pipeline of the same process keeps its jobs coming
+        const bool on_device = account_on_device(D, flags);
         std::lock_guard<std::mutex> acct(D->acct_mu);
-        int rc = mb_verify_account_on(D->c, n, proofs, proof_lens, pubs, pub_lens, passed.data(), ran.data(), &D->c->lanes[MB_PIPE_LANES - 1], &D->mu);
+        int rc = on_device ? D->c->account_on_device(D->c, n, proofs, proof_lens, pubs, pub_lens, passed.data(), ran.data(), &D->c->lanes[MB_PIPE_LANES - 1], &D->mu)
+                           : mb_verify_account_on(D->c, n, proofs, proof_lens, pubs, pub_lens, passed.data(), ran.data(), &D->c->lanes[MB_PIPE_LANES - 1], &D->mu);
         if (rc) return rc;
     }
     const uint32_t need = MINA_CHECK_FORMAT | MINA_CHECK_ACCOUNT_ABI | MINA_CHECK_MERKLE;

@@ -114,6 +114,7 @@ struct Lane {
     DevBuf st_ok, st_hashes, st_pub_xyzz, st_pubcomm, st_flags, st_in, st_verdicts;   // Proof-of-State job (api_state.hip)
     DevBuf dd_rep, dd_uniq, dd_table, dd_counts;  // its deduplicated state leg (state_dedup.cuh): 4 B x n each, the table 16 B x the power of two >= 2 n, counters + one word per 1024 states
     DevBuf pk_off, pk_len, pk_status, pk_info, pk_fmt;   // the packed-on-device front end (state_pack.cuh; api_pack.hip): 8 B + 4 B + 1 B per state, two info structs + 1 B per proof
+    DevBuf ac_ws, ac_in;                     // the device path of a Proof-of-Account job (account_pack.cuh; api_account_dev.hip): its workspace (AccountWs), the uploaded bytes + verdict words of a boundary call
     DevBuf kc_state, kc_pos, kc_cip, kc_pts, kc_v, kc_u, kc_comms, kc_xfer, kc_pch, pk_xe, pk_pub, pk_ok;                  // kimchi to_batch output rows (api_kimchi.hip)
     void release_all() {
         MsmWorkspace &w = ws;
@@ -122,7 +123,7 @@ struct Lane {
                          &bp_ltab, &bp_htab, &bp_partial, &bp_ldig, &bp_hdig, &bp_colsum, &ipa_chals, &ipa_folded, &ipa_xyzz_a, &ipa_xyzz_b, &ipa_points, &ipa_scalars,
                          &ipa_sigma, &ipa_in_a, &ipa_in_b, &ipa_in_c, &ipa_verdict, &ipa_xfer, &ipa_shared, &ipa_shared_off, &acc_rho_scaled,
                          &st_ok, &st_hashes, &st_pub_xyzz, &st_pubcomm, &st_flags, &st_in, &st_verdicts,
-                         &dd_rep, &dd_uniq, &dd_table, &dd_counts, &pk_off, &pk_len, &pk_status, &pk_info, &pk_fmt,
+                         &dd_rep, &dd_uniq, &dd_table, &dd_counts, &pk_off, &pk_len, &pk_status, &pk_info, &pk_fmt, &ac_ws, &ac_in,
                          &kc_state, &kc_pos, &kc_cip, &kc_pts, &kc_v, &kc_u, &kc_comms, &kc_xfer, &kc_pch, &pk_xe, &pk_pub, &pk_ok};
         for (DevBuf *b : all) b->release();
         host_stage.release();
@@ -162,6 +163,13 @@ struct mina_ctx {
     // which link no kernel -- keeps the host path.
     int (*state_frontend)(mina_ctx *c, size_t batch, const void *d_blob, size_t blob_len, const void *d_begin, const void *d_end, const void *d_expected_hashes,
                           const void *d_ledger_hashes, const void *d_and, void *d_records, void *d_nfields, void *d_precheck, void *d_masks) = nullptr;
+    // Proof-of-Account on the device (api_account_dev.hip).  acct_defaults: the hashes of the empty URI, the dummy verification key and the default zkApp record under
+    // the installed Fp tables (3 x 8 canonical words + their three records), computed on first use, dropped when the tables change.  account_on_device: the device
+    // twin of mb_verify_account_on (same arguments), filled by mina_ctx_create; the boundary reaches it through the pointer (MINA_VERIFY_ACCOUNT_ON_DEVICE), and a
+    // context without it keeps the host path.
+    DevBuf acct_defaults; bool have_acct_defaults = false;
+    int (*account_on_device)(mina_ctx *c, size_t n, const uint8_t *const *proofs, const size_t *proof_lens, const uint8_t *const *pubs, const size_t *pub_lens,
+                             uint32_t *passed, uint32_t *ran, Lane *lane, std::mutex *enq_mu) = nullptr;
     uint32_t dev_fork_made = 0;      // the dev_fork value the helper lanes' streams were created under (streams keep their mask / priority for life)
     void use_lane0() { L = &lanes[0]; }
     void next_lane() { L = pinned >= 0 ? &lanes[pinned] : &lanes[rr++ % (unsigned)nlanes]; }
@@ -269,6 +277,8 @@ int mb_verify_account_on(mina_ctx *c, size_t n, const uint8_t *const *proofs, co
                          uint32_t *passed, uint32_t *ran, Lane *lane, std::mutex *enq_mu);   // api_account.hip: Proof-of-Account on a lane of the caller's choice
 int mb_state_frontend_on_lane(mina_ctx *c, size_t batch, const void *d_blob, size_t blob_len, const void *d_begin, const void *d_end, const void *d_expected_hashes,
                               const void *d_ledger_hashes, const void *d_and, void *d_records, void *d_nfields, void *d_precheck, void *d_masks);   // api_pack.hip
+int mb_verify_account_dev_on(mina_ctx *c, size_t n, const uint8_t *const *proofs, const size_t *proof_lens, const uint8_t *const *pubs, const size_t *pub_lens,
+                             uint32_t *passed, uint32_t *ran, Lane *lane, std::mutex *enq_mu);   // api_account_dev.hip: the same on the device, from the bytes as they are
 int mb_state_hashes_early(mina_ctx *c, Lane *LS, size_t ns_total, size_t lo, size_t cnt, const uint32_t *d_records, const uint32_t *d_nfields, hipEvent_t after, HashLaunch hash);
 
 // ---- host-side worker pool (api_core.hip): persistent threads, created on first use -- min(hardware threads / 2, 64), $MINA_HOST_THREADS

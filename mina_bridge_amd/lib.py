@@ -36,7 +36,7 @@ EXPORTS = [
     "mina_consensus_project_window", "mina_consensus_relative_min_window_density", "mina_consensus_is_short_range",
     "mina_protocol_state_pack", "mina_protocol_state_hash_batch", "mina_protocol_state_hash_bytes",
     "mina_protocol_state_dedup_dev", "mina_protocol_state_hash_batch_dedup", "mina_ctx_set_state_dedup", "mina_ctx_state_dedup_stats",
-    "mina_protocol_state_pack_dev", "mina_state_frontend_dev",
+    "mina_protocol_state_pack_dev", "mina_state_frontend_dev", "mina_account_frontend_dev", "mina_account_job_dev",
     "mina_state_jobs_prepare", "mina_state_job_batch_dev", "mina_state_job_batch", "mina_state_job_fold_dev",
     "mina_challenge_to_field_dev", "mina_field_sum_rows_dev", "mina_msm_srs_range_dev", "mina_msm_dev", "mina_points_sum_dev", "mina_point_records_equal_dev",
     "mina_step_index_install", "mina_step_index_load_json", "mina_polish_tokens_from_json", "mina_verifier_index_load_json", "mina_pickles_public_input",
@@ -237,6 +237,7 @@ class KimchiBatchOut(ctypes.Structure):
 CHECK_FORMAT, CHECK_LEDGER, CHECK_CHAIN, CHECK_CONSENSUS, CHECK_ACCUMULATOR, CHECK_KIMCHI, CHECK_ACCOUNT_ABI, CHECK_MERKLE = 1, 2, 4, 8, 16, 32, 64, 128
 VERIFY_ALLOW_MISSING_KIMCHI, VERIFY_ALLOW_UNBOUND_STATEMENT, VERIFY_ALLOW_SURROGATE = 1, 2, 4
 VERIFY_DEDUP_STATES = 8   # the boundary hashes each distinct protocol state of a chunk once (MinaContext.set_state_dedup on its contexts); verdicts unchanged
+VERIFY_ACCOUNT_ON_DEVICE = 32   # verify_account / _batch / _checks upload a call's bytes as they are and run the whole Proof-of-Account job on the GPU (MinaContext.account_job_dev); verdicts unchanged
 VERIFY_PACK_ON_DEVICE = 16   # the boundary packs and pre-checks the protocol states of a chunk on the GPU (MinaContext.state_frontend_dev) instead of on its host pool; verdicts unchanged
 
 
@@ -1015,6 +1016,24 @@ class MinaContext:
         out = np.empty((n, 32), np.uint8)
         self._ck(self._lib.mina_account_hash_batch(self._h, int(encoding), ctypes.c_size_t(n), PP, PL, _p(out)), "mina_account_hash_batch")
         return out
+
+    def account_frontend_dev(self, n: int, d_blob: int, blob_len: int, d_proof_off: int, d_proof_len: int, d_pub_off: int, d_pub_len: int, d_records: int, d_nfields: int,
+                             d_salt_idx: int, d_siblings: int, d_dirs: int, d_depths: int, d_ledger_hashes: int, d_zk_marks: int, d_zk_index: int, d_zk_count: int, d_bits: int):
+        """the reader of a Proof-of-Account job on the GPU (bincode): pair i = proof bytes [proof_off[i], + proof_len[i]) and public input [pub_off[i], + pub_len[i]) of
+        the blob (u64 each) -> Merkle path, ledger hash, the four `to_input` records with field counts and salt indices (the three zkApp stages compacted over the
+        accounts that carry one: zk_index / zk_count / zk_marks) and the CHECK_FORMAT / CHECK_ACCOUNT_ABI bits; device pointers, queued on the next pipeline lane"""
+        v = ctypes.c_void_p
+        self._ck(self._lib.mina_account_frontend_dev(self._h, ctypes.c_size_t(n), v(d_blob), ctypes.c_size_t(blob_len), v(d_proof_off), v(d_proof_len), v(d_pub_off), v(d_pub_len),
+                                                     v(d_records), v(d_nfields), v(d_salt_idx), v(d_siblings), v(d_dirs), v(d_depths), v(d_ledger_hashes), v(d_zk_marks), v(d_zk_index),
+                                                     v(d_zk_count), v(d_bits)), "mina_account_frontend_dev")
+
+    def account_job_dev(self, n: int, d_blob: int, blob_len: int, d_proof_off: int, d_proof_len: int, d_pub_off: int, d_pub_len: int, d_passed: int, d_ran: int,
+                        d_account_hashes: int = 0, d_roots: int = 0):
+        """`verify_account_checks` for n serialized pairs in HBM (layout as account_frontend_dev): the `passed` / `ran` masks (u32 each) and, optionally, the account
+        hashes and folded roots (n x 32 bytes); stream-ordered on the next pipeline lane, the caller synchronises"""
+        v = ctypes.c_void_p
+        self._ck(self._lib.mina_account_job_dev(self._h, ctypes.c_size_t(n), v(d_blob), ctypes.c_size_t(blob_len), v(d_proof_off), v(d_proof_len), v(d_pub_off), v(d_pub_len),
+                                                v(d_passed), v(d_ran), v(d_account_hashes or None), v(d_roots or None)), "mina_account_job_dev")
 
     def verify_account_checks(self, proofs: list, pubs: list):
         n = len(proofs)
