@@ -45,6 +45,7 @@ static int srs_alloc(mina_ctx *c, int curve, uint32_t depth) {
     SrsState &s = c->srs[curve];
     s.depth = 0; s.c = 16; s.W = 16;
     s.lagrange_log2 = -1; s.lagrange_host.clear();
+    s.lagrange_table_log2 = -1; s.lagrange_table_n = 0; s.lagrange_digits_n = 0;      // the device tables belong to the old SRS: mb_pubcomm_dev (the job path) checks only these
     static std::atomic<uint64_t> gen{0};
     s.srs_gen = ++gen;
     int rc;

@@ -3,6 +3,7 @@ import numpy as np
 import pytest
 
 from conftest import rand_scalars
+from srs_helpers import srs_blob as _srs_blob
 
 pytestmark = pytest.mark.gpu
 
@@ -275,14 +276,6 @@ def test_msm_srs_multi_randomised_shapes(ctx_srs, oracle, srs_oracle):
             ctx_srs.set_pipeline(1)
         for m in range(nprob):
             assert (got[m] == oracle.msm_pippenger(curve, g[:n], sc[m], threads=8)).all(), (trial, curve, n, nprob, m)
-
-
-def _srs_blob(oracle, curve, g, h):
-    """SRS{g, h} in the reference's file format: fixarray(2)[ array32(n)[bin8(33) ...], bin8(33) ]"""
-    import struct
-    comp = oracle.point_compress(curve, np.concatenate([g, h.reshape(1, 64)]))
-    body = b"".join(b"\xc4\x21" + comp[i].tobytes() for i in range(len(g)))
-    return b"\x92" + b"\xdd" + struct.pack(">I", len(g)) + body + b"\xc4\x21" + comp[len(g)].tobytes()
 
 
 @pytest.mark.parametrize("curve", [1, 0])
