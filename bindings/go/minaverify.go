@@ -67,6 +67,20 @@ func ConfigurePackOnDevice(otherFlags uint32) { C.mina_verify_configure(C.uint32
 // (mina_account_job_dev; bincode only); off by default, verdicts unchanged; other flags are kept by the caller.
 func ConfigureAccountOnDevice(otherFlags uint32) { C.mina_verify_configure(C.uint32_t(otherFlags) | C.MINA_VERIFY_ACCOUNT_ON_DEVICE) }
 
+// SelftestFe29: one routine of the 9 x 29-bit layer (op = C.MINA_FE29_*) on rows of 73 uint32 words, 37 words out per row.  Test-facing: the caller owns the
+// operand bounds, nothing is range-checked on the device.
+func (c *Ctx) SelftestFe29(field, op int, rows []uint32) ([]uint32, error) {
+	n := len(rows) / (C.MINA_FE29_IN_OPERANDS*9 + 1)
+	out := make([]uint32, n*(C.MINA_FE29_OUT_RESULTS*9+1)+1)
+	if n == 0 {
+		return out[:0], nil
+	}
+	if rc := C.mina_selftest_fe29(c.p, C.int(field), C.int(op), C.size_t(n), (*C.uint32_t)(unsafe.Pointer(&rows[0])), (*C.uint32_t)(unsafe.Pointer(&out[0]))); rc != 0 {
+		return nil, lastError()
+	}
+	return out[:len(out)-1], nil
+}
+
 // AccumulatorCheckMulti: one deterministic verdict per proof (len(sg)/64 proofs).
 func (c *Ctx) AccumulatorCheckMulti(curve int, k uint32, pre, sg []byte) ([]bool, error) {
 	n := len(sg) / 64

@@ -211,6 +211,62 @@ int mina_field_sqrt(mina_ctx *ctx, int field, size_t n, const uint8_t *a, uint8_
  * routines; both results as affine points, same[i] = 1 iff the XYZZ coordinates agreed word for word at every step */
 int mina_selftest_group_law(mina_ctx *ctx, int curve, size_t n, const uint8_t *p_affine, const uint8_t *q_affine,
                             uint8_t *out_serial, uint8_t *out_quad, uint8_t *same);
+/* the 9 x 29-bit layer (fp29.cuh, ec29.cuh), one routine per call.  TEST-FACING: the caller owns the operand bounds (tools/fe29_bounds.py states them per call
+ * site) and nothing is range-checked on the device -- an operand beyond them wraps an accumulator or a limb silently, which is what the tests look for.
+ * Rows of fixed size whatever the op, uint32 words: in = MINA_FE29_IN_OPERANDS operands of 9 limbs + 1 flag word (73 words), out = MINA_FE29_OUT_RESULTS results of
+ * 9 limbs + 1 flag word (37 words).  Unused slots are ignored on input and zero on output; a result of eight 32-bit words sits in limbs 0..7 of its slot.
+ *   products: the pairs (a0, b0), (a1, b1), (a2, b2) in slots 0..5 (a square reads slot 0), c -- added before the reduction -- in slot 6, h / t -- added to the
+ *             high half -- in slot 7; result in slot 0.  MINA_FE29_ROW1_SG: a0, a1 and c are wave-uniform by contract; its rows run one per workgroup.
+ *   limb-wise forms: operands in slots 0, 1 (, 2), result in slot 0; _WORDS: slot 0 holds eight words, out slot 0 = fe29_from_words, slot 1 = fe29_to_words of it;
+ *             _IS_MULTIPLE_OF_P: out flag = the bool; _LEAVE: eight canonical Montgomery-2^256 words
+ *   laws:     accumulator (x, y, zz, zzz) in slots 0..3; _ADD_AFFINE: qx, qy in slots 4, 5 (qy normalised or the raw K p - y); _ADD_AFFINE_TWIN: qx, py in slots 4, 5,
+ *             in flag = MINA_FE29_FLAG_NEG | MINA_FE29_FLAG_INF; _XYZZ_ADD: the second accumulator in slots 4..7; _XYZZ_LEAVE: in flag MINA_FE29_FLAG_INF, four
+ *             results of eight words.  Out: the accumulator's raw limbs, out flag = MINA_FE29_FLAG_OK (the returned bool) | MINA_FE29_FLAG_INF (`inf` afterwards). */
+#define MINA_FE29_IN_OPERANDS 8
+#define MINA_FE29_OUT_RESULTS 4
+#define MINA_FE29_FLAG_NEG 1
+#define MINA_FE29_FLAG_OK 1
+#define MINA_FE29_FLAG_INF 2
+#define MINA_FE29_MUL_ASM 0
+#define MINA_FE29_SQR_ASM 1
+#define MINA_FE29_DOT2_ASM 2
+#define MINA_FE29_DOT3_ASM 3
+#define MINA_FE29_SQR_HI_ASM 4
+#define MINA_FE29_MUL_HI_ASM 5
+#define MINA_FE29_MUL_LZ 6
+#define MINA_FE29_SQR_LZ 7
+#define MINA_FE29_MUL_HI_LZ 8
+#define MINA_FE29_MULRC_LZ 9
+#define MINA_FE29_DOT2RC_LZ 10
+#define MINA_FE29_DOT3RC_LZ 11
+#define MINA_FE29_MUL_SG 12
+#define MINA_FE29_SQR_SG 13
+#define MINA_FE29_MUL_HI_SG 14
+#define MINA_FE29_SQR_HI_SG 15
+#define MINA_FE29_MULRC_SG 16
+#define MINA_FE29_DOT2RC_SG 17
+#define MINA_FE29_DOT3RC_SG 18
+#define MINA_FE29_ROW1_SG 19
+#define MINA_FE29_SUB_KP_ONE 32                 /* fe29_sub_kp<F, 1>: the first point of a bucket, negated */
+#define MINA_FE29_KP_MINUS_NEG_Y 33             /* fe29_kp_minus<F, EC29::NEG_Y_MULT> ... */
+#define MINA_FE29_KP_MINUS_SUB_X1 34
+#define MINA_FE29_KP_MINUS_SUB_Y1 35
+#define MINA_FE29_KP_MINUS_G_U1 36
+#define MINA_FE29_KP_MINUS_G_S1 37
+#define MINA_FE29_KP_MINUS_A_2B_X3_SUB 38       /* fe29_kp_minus_a_minus_2b<F, EC29::X3_SUB_MULT> / G_X3_SUB_MULT */
+#define MINA_FE29_KP_MINUS_A_2B_G_X3_SUB 39
+#define MINA_FE29_ADD_KP_MINUS_SUB_X3 40        /* fe29_add_kp_minus<F, EC29::SUB_X3_MULT> / G_SUB_X3_MULT */
+#define MINA_FE29_ADD_KP_MINUS_G_SUB_X3 41
+#define MINA_FE29_ADD 42
+#define MINA_FE29_ADD3 43
+#define MINA_FE29_WORDS 44
+#define MINA_FE29_IS_MULTIPLE_OF_P 45
+#define MINA_FE29_LEAVE 46
+#define MINA_FE29_ADD_AFFINE 64
+#define MINA_FE29_ADD_AFFINE_TWIN 65
+#define MINA_FE29_XYZZ_ADD 66
+#define MINA_FE29_XYZZ_LEAVE 67
+int mina_selftest_fe29(mina_ctx *ctx, int field, int op, size_t n, const uint32_t *rows_in /* n*73 */, uint32_t *rows_out /* n*37 */);
 
 /* ---- a8 / a10: combined IPA check ------------------------------------------------------------ */
 /* Accumulator check (a10) for `batch` proofs on the SRS of `curve`:

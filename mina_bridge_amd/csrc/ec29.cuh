@@ -7,11 +7,11 @@
 // Value discipline (p = 2^254 + c; 2^256 ~ 4 p; a normalised 9-limb value holds up to 2^261) -- PROVEN, not asserted: tools/fe29_bounds.py runs this law on
 // intervals (a maximum per limb and per value), tools/gen_fe29.py refuses to emit fp29.cuh when a rule fails, and the constants below (`EC29::*`, generated into
 // fp29.cuh) are the ones the proof ran with:
-//   * six of the nine products run LAZY (quotient digits unmasked: result < a b / 2^261 + 8.0001 p instead of + p; nine masks less each): pd, r, pp, ppp, zz3, zzz3 --
-//     every one whose result only feeds products or a "K p - b"; q, x3 and the dot product y3 stay strict (with a seventh lazy product the invariants have no fixed point)
+//   * eight of the nine reductions use SIGNED quotient digits (fp29.cuh: no instruction per digit, result within (1 p, 2 p] of a b / 2^261): pd, r, pp, ppp, q, x3, zz3,
+//     zzz3; the dot product y3 keeps the strict unsigned form (its raw operands, limbs up to 2^31, leave a signed column no room)
 //   * a - b is a + K p - b with K p in a redundant limb form whose every limb exceeds any normalised limb of b: limb-wise, NO carry pass -- so the top limb must
 //     hold by itself: K at least one more than b's bound in units of p (the round-4 bug: ONE p under a canonical y)
-//   * accumulator coordinates stay below EC29::INV_X / INV_Y / INV_ZZ / INV_ZZZ times p (26, 6, 10, 9: the least fixed point of the lazy law); table coordinates
+//   * accumulator coordinates stay below EC29::INV_X / INV_Y / INV_ZZ / INV_ZZZ times p (10, 2, 3, 3: the least fixed point of the law with signed digits); table coordinates
 //     are canonical (< p), in the 2^261 domain
 // The exceptional cases of the group law (the two points equal or opposite: P = 0 mod p) are found EXACTLY: a multiple k p = k 2^254 + k c of p below
 // EC29::PD_MAX p has limbs 5..7 and the low 22 bits of limb 8 zero (k c < 2^131) -- four instructions per add -- and only then limbs 0..4 are compared with k c;

@@ -348,10 +348,10 @@ __device__ __forceinline__ void poseidon_permute_hex(fe_t &s, const PoseidonPara
 #undef MB_QUAD29
     const int src = (int)(((threadIdx.x & 63u) & ~15u) | (col << 2));  // lane 0 of quad `col`: x_col^7
     fe29_t x = fe29_mul_asm<F>(fe29_from_words(s), q->enter);        // x 2^256 -> x 2^261
-    // lazy products (fp29.cuh), as the 3-lane form: what counts here is the LENGTH of the dependent chain, and one wave issues an instruction every ~9
+    // signed-digit products (fp29.cuh), as the 3-lane form: what counts here is the LENGTH of the dependent chain, and one wave issues an instruction every ~9
     // cycles whatever their dependencies (microbench --dep) -- fewer instructions is the only lever.  Lane 0 of a quad adds the round constant inside its
-    // product's reduction (the others add zero); the row's three terms are summed in one carry pass.  In units of p: x < 24.3, x^2 < 12.7, x^3 / x^4 < 10.5,
-    // x^7 < 8.9, each term < 8.1
+    // product's reduction (the others add zero); the row's three terms are summed in one carry pass.  Proven (tools/fe29_bounds.py prove_sponge_rounds): the state
+    // stays below SPONGE29::LANES16_STATE_MILLI_P / 1000 = 6.1 p; in units of p: x < 6.1, x^2 < 2.3, x^3 < 2.2, x^4 / x^7 < 2.1, each term < 2.02
     const fe29_t *rcp = c == 0 ? &q->rc2[0][e] : &q->zero;
     const size_t rcs = c == 0 ? 3 : 0;                               // fe29_t elements per round
 #pragma unroll 1

@@ -31,7 +31,7 @@ EXPORTS = [
     "mina_b_poly", "mina_b_poly_coefficients", "mina_b_poly_fold", "mina_b_poly_fold_dev",
     "mina_poseidon_set_params", "mina_poseidon_params_parse", "mina_poseidon_load_params", "mina_poseidon_load_params_file", "mina_poseidon_permute", "mina_poseidon_permute_dev", "mina_poseidon_hash",
     "mina_challenge_to_field", "mina_fq_sponge_run", "mina_to_group", "mina_merkle_roots", "mina_merkle_verify_batch",
-    "mina_field_mul", "mina_field_inv", "mina_field_sqrt", "mina_selftest_group_law",
+    "mina_field_mul", "mina_field_inv", "mina_field_sqrt", "mina_selftest_group_law", "mina_selftest_fe29",
     "mina_accumulator_check_batch", "mina_accumulator_check_dev", "mina_accumulator_check_multi_dev", "mina_accumulator_check_multi", "mina_ipa_batch_check",
     "mina_consensus_project_window", "mina_consensus_relative_min_window_density", "mina_consensus_is_short_range",
     "mina_protocol_state_pack", "mina_protocol_state_hash_batch", "mina_protocol_state_hash_bytes",
@@ -227,6 +227,16 @@ class PicklesStatements(ctypes.Structure):
 
     def strides(self):
         return dict(zip(self.POINTER_FIELDS, (64, 256, self.n_old * 256, self.n_old * 64, 480, 64, 32, self.n_evals * 64, 64, 32, 32, 32)))
+
+# mina_selftest_fe29 (include/mina_verify.h MINA_FE29_*): row sizes, flag bits and op codes
+FE29_IN_OPERANDS, FE29_OUT_RESULTS = 8, 4
+FE29_IN_WORDS, FE29_OUT_WORDS = FE29_IN_OPERANDS * 9 + 1, FE29_OUT_RESULTS * 9 + 1
+FE29_FLAG_NEG, FE29_FLAG_OK, FE29_FLAG_INF = 1, 1, 2
+FE29_OPS = {"MUL_ASM": 0, "SQR_ASM": 1, "DOT2_ASM": 2, "DOT3_ASM": 3, "SQR_HI_ASM": 4, "MUL_HI_ASM": 5, "MUL_LZ": 6, "SQR_LZ": 7, "MUL_HI_LZ": 8, "MULRC_LZ": 9, "DOT2RC_LZ": 10,
+            "DOT3RC_LZ": 11, "MUL_SG": 12, "SQR_SG": 13, "MUL_HI_SG": 14, "SQR_HI_SG": 15, "MULRC_SG": 16, "DOT2RC_SG": 17, "DOT3RC_SG": 18, "ROW1_SG": 19,
+            "SUB_KP_ONE": 32, "KP_MINUS_NEG_Y": 33, "KP_MINUS_SUB_X1": 34, "KP_MINUS_SUB_Y1": 35, "KP_MINUS_G_U1": 36, "KP_MINUS_G_S1": 37, "KP_MINUS_A_2B_X3_SUB": 38,
+            "KP_MINUS_A_2B_G_X3_SUB": 39, "ADD_KP_MINUS_SUB_X3": 40, "ADD_KP_MINUS_G_SUB_X3": 41, "ADD": 42, "ADD3": 43, "WORDS": 44, "IS_MULTIPLE_OF_P": 45, "LEAVE": 46,
+            "ADD_AFFINE": 64, "ADD_AFFINE_TWIN": 65, "XYZZ_ADD": 66, "XYZZ_LEAVE": 67}
 
 
 class KimchiBatchOut(ctypes.Structure):
@@ -881,6 +891,14 @@ class MinaContext:
         a, b, same = np.empty((n, 64), np.uint8), np.empty((n, 64), np.uint8), np.empty(n, np.uint8)
         self._ck(self._lib.mina_selftest_group_law(self._h, curve, ctypes.c_size_t(n), _p(p), _p(q), _p(a), _p(b), _p(same)), "mina_selftest_group_law")
         return a, b, same
+
+    def selftest_fe29(self, field: int, op: int, rows) -> np.ndarray:
+        """one routine of the 9 x 29-bit layer (fp29.cuh / ec29.cuh; op = FE29_OPS[name]) on rows of FE29_IN_WORDS uint32 words -- 8 operands of 9 limbs and a flag
+        word -- -> rows of FE29_OUT_WORDS words: 4 results of 9 limbs and a flag word.  Test-facing: the caller owns the operand bounds (tools/fe29_bounds.py)"""
+        rows = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1, FE29_IN_WORDS)
+        out = np.empty((rows.shape[0], FE29_OUT_WORDS), np.uint32)
+        self._ck(self._lib.mina_selftest_fe29(self._h, int(field), int(op), ctypes.c_size_t(rows.shape[0]), _p(rows), _p(out)), "mina_selftest_fe29")
+        return out
 
     # -- a10 / a8
     def accumulator_check_batch(self, curve: int, k: int, prechallenges, sg, rho=None) -> np.ndarray:

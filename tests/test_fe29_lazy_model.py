@@ -5,11 +5,12 @@ of the routines' callers (the XYZZ mixed add, the Poseidon lane forms); tools/ge
 proofs ran with (`struct EC29`, `struct SPONGE29`) for the C++ to use by name.  This file
   * runs the proofs, checks the committed fp29.cuh IS what the generator writes, and that ec29.cuh takes every multiple of p from `EC29::`;
   * re-introduces the round-4 bug (ONE p under a canonical y) and other broken disciplines: the prover -- and the generator -- must refuse;
-  * restates the generated column loops on Python integers (64-bit accumulator; masked, unmasked or SIGNED quotient digits; the high-half addend, the tenth operand) and
-    runs the group law and the lane forms' rounds on random AND adversarial concrete values (coordinates at their invariants, y = p - 1, 2^254, 2^254 - 2^233 - 1 ...):
+  * runs the generated column loops restated on Python integers (tests/fe29_model.py: 64-bit accumulator; masked, unmasked or SIGNED quotient digits; the high-half addend,
+    the tenth operand), the group law and the lane forms' rounds on random AND adversarial concrete values (coordinates at their invariants, y = p - 1, 2^254, 2^254 - 2^233 - 1 ...):
     every column below 2^64, every limb-wise difference non-negative, every intermediate inside the interval the prover derived, every result the field element
     the textbook formula gives.
-What the GPU parity tests cannot reach -- the worst case of a column, the rare table point -- is reached here, on the CPU tier."""
+What the GPU parity tests cannot reach -- the worst case of a column, the rare table point -- is reached here, on the CPU tier, by the MODEL; the compiled routines meet the
+same corners in tests/test_gpu_fe29.py (rows: tests/test_fe29_rows.py)."""
 import importlib.util
 import os
 import random
@@ -26,101 +27,7 @@ def _load(name):
     return mod
 
 
-B = _load("fe29_bounds")
-L, W, M29, R, P = B.L, B.W, B.M29, B.R, B.P
-
-
-def limbs(x):
-    return B.limbs_of(x)
-
-
-def value(v):
-    return sum(x << (W * i) for i, x in enumerate(v))
-
-
-# ------------------------------------------------------------------------------------------------ the generated column loop on concrete integers
-def model_product_signed(p, pairs, hi=None, c=None):
-    """tools/gen_fe29.py `body_sg` on a 64-bit two's-complement accumulator: the digit of column k < 8 is the column's low word read as an int32 and SUBTRACTED against the
-    prime limbs; digit 8 is (col & M29) - 2^30.  Returns (result limbs, largest |true column value| seen); asserts that the wrapped register and the true value agree
-    whenever the column is shifted."""
-    pl = limbs(p)
-    MASK = (1 << 64) - 1
-    s64 = lambda x: x - (1 << 64) if x >> 63 else x
-    col, true, d, r, peak = 0, 0, [0] * L, [0] * L, 0
-    for k in range(2 * L - 1):
-        for a, b in pairs:
-            for i in range(L):
-                if 0 <= k - i < L:
-                    col = (col + a[i] * b[k - i]) & MASK; true += a[i] * b[k - i]
-        for j in (1, 2, 3, 4, 8):
-            if 0 <= k - j < L and k - j < k:
-                col = (col - d[k - j] * pl[j]) & MASK; true -= d[k - j] * pl[j]
-        if hi is not None and k >= L:
-            col = (col + hi[k - L]) & MASK; true += hi[k - L]
-        if c is not None and k < L:
-            col = (col + c[k]) & MASK; true += c[k]
-        if k < L:
-            lo = col & 0xFFFFFFFF
-            d[k] = (lo - (1 << 32) if lo >> 31 else lo) if k < L - 1 else (lo & M29) - (1 << 30)
-            col = (col - d[k]) & MASK; true -= d[k]
-            assert s64(col) == true and true & M29 == 0, "the signed accumulator wrapped"
-            peak = max(peak, abs(true))
-            true >>= W; col = (s64(col) >> W) & MASK
-        else:
-            assert s64(col) == true, "the signed accumulator wrapped"
-            peak = max(peak, abs(true))
-            r[k - L] = true & M29
-            true >>= W; col = (s64(col) >> W) & MASK
-    assert true >= 0, "negative top limb"
-    r[L - 1] = true + (hi[L - 1] if hi is not None else 0)
-    assert peak < 1 << 63 and r[L - 1] < 1 << 32
-    return r, peak
-
-
-def model_product(p, pairs, lazy=False, hi=None, c=None):
-    """tools/gen_fe29.py `body`: (result limbs, largest accumulator value seen); lazy = "sg": the signed-digit loop"""
-    if lazy == "sg":
-        return model_product_signed(p, pairs, hi=hi, c=c)
-    pl = limbs(p)
-    col, m, r, peak = 0, [0] * L, [0] * L, 0
-    for k in range(2 * L - 1):
-        for a, b in pairs:
-            for i in range(L):
-                if 0 <= k - i < L:
-                    col += a[i] * b[k - i]
-        for j in (1, 2, 3, 4, 8):
-            if 0 <= k - j < L and k - j < k:
-                col += m[k - j] * pl[j]
-        if hi is not None and k >= L:
-            col += hi[k - L]
-        if c is not None and k < L:
-            col += c[k]
-        peak = max(peak, col)
-        if k < L:
-            m[k] = (-col) & (0xFFFFFFFF if lazy else M29)
-            col += m[k]
-            peak = max(peak, col)
-            assert col & M29 == 0
-            col >>= W
-        else:
-            r[k - L] = col & M29
-            col >>= W
-    r[L - 1] = col + (hi[L - 1] if hi is not None else 0)
-    assert peak < 1 << 64, "a column left its 64-bit accumulator"
-    assert r[L - 1] < 1 << 32
-    return r, peak
-
-
-def kp_minus(p, mult, b, lend=30):
-    k = B.kp_redundant(p, mult, lend)
-    out = [k[i] - b[i] for i in range(L)]
-    assert all(0 <= x < 1 << 32 for x in out), "a limb of K p - b went negative"
-    return out
-
-
-def inside(v, iv):
-    """concrete limbs `v` lie inside the interval the prover derived"""
-    return value(v) <= iv["vmax"] and v[8] <= iv["top_limb"]
+from fe29_model import B, L, W, M29, R, P, limbs, value, model_product, model_product_signed, kp_minus, inside, is_multiple_of_p, _law, _general_add  # noqa: E402,F401
 
 
 # ------------------------------------------------------------------------------------------------ the proofs and the generated header
@@ -240,27 +147,6 @@ def test_signed_digit_products_are_the_same_field_element_inside_one_to_two_p_an
             pr.product("four-term row", [(B.norm(pr.p), B.norm(3 * pr.p))] * 4, lazy="sg", c=B.norm(pr.p))                                              # ... a fourth term would not
 
 
-def _law(p, acc, qx, qy, c):
-    """xyzz29_add_affine on concrete limbs (ec29.cuh, statement by statement); returns every intermediate"""
-    md = lambda name: B.mode_of(name, B.EC29_LAZY, B.EC29_SIGNED)
-    pd, _ = model_product(p, [(qx, acc["zz"])], lazy=md("pd"), hi=kp_minus(p, c["SUB_X1_MULT"], acc["x"]))
-    r, _ = model_product(p, [(qy, acc["zzz"])], lazy=md("r"), hi=kp_minus(p, c["SUB_Y1_MULT"], acc["y"]))
-    pp, _ = model_product(p, [(pd, pd)], lazy=md("pp"))
-    ppp, _ = model_product(p, [(pd, pp)], lazy=md("ppp"))
-    q, _ = model_product(p, [(acc["x"], pp)], lazy=md("q"))
-    k = B.kp_redundant(p, c["X3_SUB_MULT"], 31)
-    h = [k[i] - ppp[i] - 2 * q[i] for i in range(L)]
-    assert all(0 <= x < 1 << 32 for x in h), "a limb of K p - ppp - 2 q went negative"
-    x3, _ = model_product(p, [(r, r)], lazy=md("x3"), hi=h)
-    k3 = kp_minus(p, c["SUB_X3_MULT"], x3)
-    a = [q[i] + k3[i] for i in range(L)]
-    assert all(x < 1 << 32 for x in a)
-    y3, peak = model_product(p, [(r, a), (kp_minus(p, c["SUB_Y1_MULT"], acc["y"]), ppp)], lazy=md("y3"))
-    zz, _ = model_product(p, [(acc["zz"], pp)], lazy=md("zz"))
-    zzz, _ = model_product(p, [(acc["zzz"], ppp)], lazy=md("zzz"))
-    return {"pd": pd, "r": r, "pp": pp, "ppp": ppp, "q": q, "x3": x3, "y3": y3, "zz": zz, "zzz": zzz}, peak
-
-
 def test_the_group_law_on_concrete_values_stays_inside_the_proven_intervals_and_is_the_textbook_formula():
     """madd-2008-s on XYZZ coordinates in the Montgomery-2^261 domain: with U2 = X2 ZZ1, S2 = Y2 ZZZ1, P = U2 - X1, R = S2 - Y1: X3 = R^2 - PPP - 2 Q, Y3 = R (Q - X3) - Y1 PPP,
     ZZ3 = ZZ1 PP, ZZZ3 = ZZZ1 PPP (Q = X1 PP) -- each product carrying one factor 1/2^261"""
@@ -303,15 +189,7 @@ def test_the_exact_zero_test_of_the_group_law_covers_every_multiple_of_p_below_i
     """ec29.cuh fe29_is_multiple_of_p: a normalised value below EC29::PD_MAX p is 0 mod p iff limbs 5..7 and the low 22 bits of limb 8 are zero and limbs 0..4 equal k c"""
     for F, p in P.items():
         cpart = p - (1 << 254)
-        pl = limbs(p)
-
-        def is_multiple(a):
-            if a[5] | a[6] | a[7] | (a[8] & 0x3FFFFF): return False
-            k = a[8] >> 22
-            t, carry = [], 0
-            for j in range(5):
-                x = k * pl[j] + carry; t.append(x & M29); carry = x >> W
-            return a[:5] == t and carry == 0
+        is_multiple = lambda a: is_multiple_of_p(p, a)
         rng = random.Random(5)
         for k in list(range(B.EC29["PD_MAX"] + 1)) + [rng.randrange(1 << 19) for _ in range(50)]:
             assert k * cpart < 1 << 145                                   # k c stays inside limbs 0..4
@@ -347,7 +225,6 @@ def test_the_general_add_on_concrete_values_stays_inside_the_proven_intervals_an
     """ec29.cuh xyzz29_add (add-2008-s on XYZZ, both operands accumulators within the invariants): U1 = X1 ZZ2, U2 = X2 ZZ1, S1 = Y1 ZZZ2, S2 = Y2 ZZZ1, P = U2 - U1, R = S2 - S1,
     X3 = R^2 - PPP - 2 Q (Q = U1 PP), Y3 = R (Q - X3) - S1 PPP, ZZ3 = ZZ1 ZZ2 PP, ZZZ3 = ZZZ1 ZZZ2 PPP -- each product carrying one factor 1 / 2^261"""
     c, e = B.EC29_GENERAL, B.EC29
-    md = lambda name: B.mode_of(name, B.EC29_GENERAL_LAZY, B.EC29_GENERAL_SIGNED)
     rng = random.Random(41)
     for F, p in P.items():
         table = B.prove_all()["fields"][F]["group_add"]
@@ -358,25 +235,14 @@ def test_the_general_add_on_concrete_values_stays_inside_the_proven_intervals_an
             av = {k: (b - 1 - rng.randrange(3) if edge else rng.randrange(b)) for k, b in inv.items()}
             bv = {k: (b - 1 - rng.randrange(3) if edge and it % 8 == 0 else rng.randrange(b)) for k, b in inv.items()}
             a = {k: limbs(v) for k, v in av.items()}; b = {k: limbs(v) for k, v in bv.items()}
-            u1, _ = model_product(p, [(a["x"], b["zz"])], lazy=md("u1")); s1, _ = model_product(p, [(a["y"], b["zzz"])], lazy=md("s1"))
-            pd, _ = model_product(p, [(b["x"], a["zz"])], lazy=md("pd"), hi=kp_minus(p, c["G_U1_MULT"], u1))
-            r, _ = model_product(p, [(b["y"], a["zzz"])], lazy=md("r"), hi=kp_minus(p, c["G_S1_MULT"], s1))
-            pp, _ = model_product(p, [(pd, pd)], lazy=md("pp")); ppp, _ = model_product(p, [(pd, pp)], lazy=md("ppp")); q, _ = model_product(p, [(u1, pp)], lazy=md("q"))
-            k4 = B.kp_redundant(p, c["G_X3_SUB_MULT"], 31)
-            h = [k4[i] - ppp[i] - 2 * q[i] for i in range(L)]
-            assert all(0 <= x < 1 << 32 for x in h)
-            x3, _ = model_product(p, [(r, r)], lazy=md("x3"), hi=h)
-            k3 = kp_minus(p, c["G_SUB_X3_MULT"], x3)
-            y3, _ = model_product(p, [(r, [q[i] + k3[i] for i in range(L)]), (kp_minus(p, c["G_S1_MULT"], s1), ppp)], lazy=md("y3"))
-            zz12, _ = model_product(p, [(a["zz"], b["zz"])], lazy=md("zz12")); zz, _ = model_product(p, [(zz12, pp)], lazy=md("zz"))
-            zzz12, _ = model_product(p, [(a["zzz"], b["zzz"])], lazy=md("zzz12")); zzz, _ = model_product(p, [(zzz12, ppp)], lazy=md("zzz"))
+            got = _general_add(p, a, b, c)
+            x3, y3, zz, zzz = got["x3"], got["y3"], got["zz"], got["zzz"]
             U1, U2, S1, S2 = av["x"] * bv["zz"] * rinv % p, bv["x"] * av["zz"] * rinv % p, av["y"] * bv["zzz"] * rinv % p, bv["y"] * av["zzz"] * rinv % p
             Pd, Rr = (U2 - U1) % p, (S2 - S1) % p
             PP = Pd * Pd * rinv % p; PPP = Pd * PP * rinv % p; Q = U1 * PP * rinv % p
             X3 = (Rr * Rr * rinv - PPP - 2 * Q) % p; Y3 = (Rr * (Q - X3) * rinv - S1 * PPP * rinv) % p
             want = {"u1": U1, "s1": S1, "pd": Pd, "r": Rr, "pp": PP, "ppp": PPP, "q": Q, "x3": X3, "y3": Y3,
                     "zz": av["zz"] * bv["zz"] * rinv % p * PP * rinv % p, "zzz": av["zzz"] * bv["zzz"] * rinv % p * PPP * rinv % p}
-            got = {"u1": u1, "s1": s1, "pd": pd, "r": r, "pp": pp, "ppp": ppp, "q": q, "x3": x3, "y3": y3, "zz": zz, "zzz": zzz}
             for name, v in got.items():
                 assert value(v) % p == want[name], (F, it, name)
                 assert inside(v, table[name]), (F, it, name)

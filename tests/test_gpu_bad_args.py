@@ -7,6 +7,8 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
+MINA_ERR_ARG = -1            # include/mina_verify.h
+
 
 def test_bad_arguments_are_errors_not_crashes(ctx_srs):
     import mina_bridge_amd as m
@@ -45,6 +47,16 @@ def test_bad_arguments_are_errors_not_crashes(ctx_srs):
     assert lib.mina_dev_malloc(c._h, ctypes.c_size_t(16), None) < 0
     assert lib.mina_accumulator_check_multi(c._h, 1, ctypes.c_uint32(16), ctypes.c_size_t(1), None, None, None) < 0
     assert b"null" in lib.mina_last_error()
+    # the 29-bit self-test hook: null pointers, a field that is none, an op that is none -- MINA_ERR_ARG each, before anything is launched
+    rows_in, rows_out = np.zeros(m.lib.FE29_IN_WORDS, np.uint32), np.zeros(m.lib.FE29_OUT_WORDS, np.uint32)
+    pin, pout, op = rows_in.ctypes.data_as(ctypes.c_void_p), rows_out.ctypes.data_as(ctypes.c_void_p), m.lib.FE29_OPS["MUL_SG"]
+    for bad in ((None, 0, op, 1, pin, pout), (c._h, 0, op, 1, None, pout), (c._h, 0, op, 1, pin, None), (c._h, 2, op, 1, pin, pout), (c._h, -1, op, 1, pin, pout),
+                (c._h, 0, max(m.lib.FE29_OPS.values()) + 1, 1, pin, pout), (c._h, 0, -1, 1, pin, pout), (c._h, 0, 20, 1, pin, pout)):
+        assert lib.mina_selftest_fe29(bad[0], bad[1], bad[2], ctypes.c_size_t(bad[3]), bad[4], bad[5]) == MINA_ERR_ARG, bad[1:4]
+    assert 20 not in m.lib.FE29_OPS.values() and lib.mina_selftest_fe29(c._h, 0, op, ctypes.c_size_t(0), None, None) == 0      # (a gap between the op groups; no rows: nothing to do)
+    with pytest.raises(m.MinaError, match="bad op"):
+        c.selftest_fe29(0, 31, rows_in)
+    assert lib.mina_selftest_fe29(c._h, 0, op, ctypes.c_size_t(1), pin, pout) == 0 and not rows_out[9:].any()
     # and the context still computes
     one = np.zeros(32, np.uint8); one[0] = 1
     assert (c.msm_srs(1, one) == c.srs_get_g(1, 0, 1)[0]).all()

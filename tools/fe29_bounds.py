@@ -38,10 +38,11 @@ def limbs_of(x: int):
 
 class V:
     """a 9-limb operand: `limb[i]` = largest value limb i can hold (all limbs are >= 0), `vmax` = largest value of the integer sum limb_i 2^(29 i);
-    `normal`: limbs 0..7 are below 2^29 (the value determines the limbs)"""
+    `normal`: limbs 0..7 are below 2^29 (the value determines the limbs); `src`: how a RAW operand is made of normalised ones -- ("kp_minus", mult, lend, b),
+    ("add_kp_minus", mult, a, b), ("kp_minus_a_minus_2b", mult, a, b), ("select", a, b) -- for whoever builds concrete operands from the intervals (tests/fe29_model.py)"""
 
-    def __init__(self, limb, vmax, normal, name=""):
-        self.limb, self.vmax, self.normal, self.name = list(limb), int(vmax), normal, name
+    def __init__(self, limb, vmax, normal, name="", src=None):
+        self.limb, self.vmax, self.normal, self.name, self.src = list(limb), int(vmax), normal, name, src
         need(all(0 <= x < 1 << 32 for x in self.limb), f"{name}: a limb does not fit its 32-bit register: {[hex(x) for x in self.limb]}")
 
     def __repr__(self):
@@ -71,6 +72,11 @@ class Prover:
         self.pl = limbs_of(self.p)
         need(self.pl[0] == 1 and self.pl[5] == self.pl[6] == self.pl[7] == 0 and self.pl[8] == 1 << 22, "Pasta prime shape")
         self.log = []                                           # (routine, what, worst column / 2^64, result bound in p)
+        self.calls = []                                         # every call site WITH its operands: {"site", "kind", "mode" (False strict, True lazy, "sg"), "pairs" / "operands" (V),
+                                                                #  "hi", "c", "mult", "out" (V), "worst" (the largest column, an integer; None for the limb-wise forms)}
+
+    def record(self, site, kind, out, **kw):
+        self.calls.append(dict({"site": site, "kind": kind, "mode": False, "pairs": [], "operands": [], "hi": None, "c": None, "mult": None, "worst": None}, out=out, **kw))
 
     # ---- the generated column loop (tools/gen_fe29.py `body`) on maxima
     def product(self, what, pairs, lazy=False, hi: V | None = None, c: V | None = None) -> V:
@@ -108,6 +114,7 @@ class Prover:
         need(top < 1 << 32, f"{what}: the top limb can reach {top:#x}")
         out = V([M29] * (L - 1) + [top], vmax, True, what)
         self.log.append((what, "product" + (" (lazy)" if lazy else ""), worst / 2**64, vmax / p))
+        self.record(what, "product", out, mode=bool(lazy), pairs=list(pairs), hi=hi, c=c, worst=worst)
         return out
 
     # ---- the SIGNED-digit column loop (tools/gen_fe29.py `body_sg`, round 5): the quotient digit of column k < 8 is the column's own low word read as an int32,
@@ -155,6 +162,7 @@ class Prover:
         out = V([M29] * (L - 1) + [top], vmax, True, what)
         out.vmin = m_lo * p // R                                # > 0.99 p
         self.log.append((what, "product (signed)", worst / 2**64, vmax / p))
+        self.record(what, "product", out, mode="sg", pairs=list(pairs), hi=hi, c=c, worst=worst)
         return out
 
     def mul(self, what, a, b, **kw): return self.product(what, [(a, b)], **kw)
@@ -169,13 +177,17 @@ class Prover:
         k = kp_redundant(self.p, mult, 30)
         for i in range(L):
             need(k[i] - b.limb[i] >= 0, f"{what}: limb {i} of {mult} p - b goes negative (K_{i} = {k[i]:#x}, b_{i} up to {b.limb[i]:#x}): use a larger multiple of p")
-        out = V(k, mult * self.p, False, what)
+        out = V(k, mult * self.p, False, what, src=("kp_minus", mult, 30, b))
         self.log.append((what, f"{mult} p - b, raw", None, mult))
+        self.record(what, "kp_minus", out, operands=[b], mult=mult)
         return out
 
     def add_kp_minus(self, what, mult: int, a: V, b: V) -> V:
         k = self.kp_minus(what, mult, b)
-        return V([a.limb[i] + k.limb[i] for i in range(L)], a.vmax + mult * self.p, False, what)
+        self.calls.pop()                                        # (the inner K p - b is this site's own first half)
+        out = V([a.limb[i] + k.limb[i] for i in range(L)], a.vmax + mult * self.p, False, what, src=("add_kp_minus", mult, a, b))
+        self.record(what, "add_kp_minus", out, operands=[a, b], mult=mult)
+        return out
 
     def kp_minus_a_minus_2b(self, what, mult: int, a: V, b: V) -> V:
         need(a.normal and b.normal, f"{what}: operands must be normalised")
@@ -183,16 +195,20 @@ class Prover:
         for i in range(L):
             need(k[i] - a.limb[i] - 2 * b.limb[i] >= 0, f"{what}: limb {i} of {mult} p - a - 2 b goes negative (a_{i} up to {a.limb[i]:#x}, b_{i} up to {b.limb[i]:#x})")
         self.log.append((what, f"{mult} p - a - 2 b, raw", None, mult))
-        return V(k, mult * self.p, False, what)
+        out = V(k, mult * self.p, False, what, src=("kp_minus_a_minus_2b", mult, a, b))
+        self.record(what, "kp_minus_a_minus_2b", out, operands=[a, b], mult=mult)
+        return out
 
     def sub_kp(self, what, mult: int, a: V, b: V) -> V:
         """a + MULT p - b WITH the carry pass (normalised result): the lower limbs lend, so the condition is on the integers: b <= a + MULT p"""
         need(a.normal and b.normal, f"{what}: operands must be normalised")
         need(b.vmax <= mult * self.p, f"{what}: b can exceed {mult} p")
-        return norm(a.vmax + mult * self.p + 1, what)
+        out = norm(a.vmax + mult * self.p + 1, what)
+        self.record(what, "sub_kp", out, operands=[a, b], mult=mult)
+        return out
 
     def select(self, what, a: V, b: V) -> V:
-        return V([max(x, y) for x, y in zip(a.limb, b.limb)], max(a.vmax, b.vmax), a.normal and b.normal, what)
+        return V([max(x, y) for x, y in zip(a.limb, b.limb)], max(a.vmax, b.vmax), a.normal and b.normal, what, src=None if a.normal and b.normal else ("select", a, b))
 
 
 # ------------------------------------------------------------------------------------------------ SPEC: the XYZZ mixed add of ec29.cuh
