@@ -81,6 +81,20 @@ func (c *Ctx) SelftestFe29(field, op int, rows []uint32) ([]uint32, error) {
 	return out[:len(out)-1], nil
 }
 
+// SelftestFe32: one routine of the 8 x 32 layer (op = C.MINA_FE32_*) on rows of 65 uint32 words, 33 words out per row.  Test-facing: raw words, the caller owns
+// each routine's contract, nothing is range-checked on the device.
+func (c *Ctx) SelftestFe32(field, op int, rows []uint32) ([]uint32, error) {
+	n := len(rows) / (C.MINA_FE32_IN_OPERANDS*8 + 1)
+	out := make([]uint32, n*(C.MINA_FE32_OUT_RESULTS*8+1)+1)
+	if n == 0 {
+		return out[:0], nil
+	}
+	if rc := C.mina_selftest_fe32(c.p, C.int(field), C.int(op), C.size_t(n), (*C.uint32_t)(unsafe.Pointer(&rows[0])), (*C.uint32_t)(unsafe.Pointer(&out[0]))); rc != 0 {
+		return nil, lastError()
+	}
+	return out[:len(out)-1], nil
+}
+
 // AccumulatorCheckMulti: one deterministic verdict per proof (len(sg)/64 proofs).
 func (c *Ctx) AccumulatorCheckMulti(curve int, k uint32, pre, sg []byte) ([]bool, error) {
 	n := len(sg) / 64

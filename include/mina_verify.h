@@ -267,6 +267,41 @@ int mina_selftest_group_law(mina_ctx *ctx, int curve, size_t n, const uint8_t *p
 #define MINA_FE29_XYZZ_ADD 66
 #define MINA_FE29_XYZZ_LEAVE 67
 int mina_selftest_fe29(mina_ctx *ctx, int field, int op, size_t n, const uint32_t *rows_in /* n*73 */, uint32_t *rows_out /* n*37 */);
+/* the 8 x 32 layer (fp.cuh, ec.cuh, fe_inv / fe_sqrt of groupmap.cuh), one routine per call.  TEST-FACING: raw words in, raw words out -- no Montgomery conversion and no
+ * range check on the device; the caller owns each routine's contract (chains: operands below p, or below 2p for _COND_SUB_P; products: sum a_i b_i < p 2^256, canonical
+ * or not; laws: coordinates below p).  Rows of fixed size whatever the op, uint32 words: in = MINA_FE32_IN_OPERANDS operands of 8 words + 1 flag word (65 words, the flag
+ * is reserved and ignored), out = MINA_FE32_OUT_RESULTS results of 8 words + 1 flag word (33 words).  Unused slots are ignored on input and zero on output.
+ *   field:  a, b in slots 0, 1; _DOT2 / _DOT3: the pairs (a0, b0), (a1, b1), (a2, b2) in slots 0..5; result in slot 0.  _TO_MONT multiplies slot 0 by R^2 mod p, _FROM_MONT
+ *           by the plain 1; _INV and _SQRT take and give Montgomery words (_SQRT: out flag MINA_FE32_FLAG_TRUE iff a square, the root -- ark's -- in slot 0, else zero);
+ *           _WORDS_CANONICAL: out flag MINA_FE32_FLAG_TRUE iff the plain integer in slot 0 is below p.
+ *   laws:   Montgomery words.  _DBL_AFFINE: x, y in slots 0, 1; _XYZZ_DBL: (x, y, zz, zzz) in slots 0..3; _ADD_AFFINE: the accumulator in slots 0..3, qx, qy in slots 4, 5;
+ *           _XYZZ_ADD: the second operand in slots 4..7.  Out: the four raw XYZZ words.  The _QUAD forms run four lanes per row on identical operands; the result is
+ *           lane 0's, and the out flag has MINA_FE32_FLAG_LANES_AGREE iff all four lanes ended with identical words. */
+#define MINA_FE32_IN_OPERANDS 8
+#define MINA_FE32_OUT_RESULTS 4
+#define MINA_FE32_FLAG_TRUE 1
+#define MINA_FE32_FLAG_LANES_AGREE 2
+#define MINA_FE32_COND_SUB_P 0
+#define MINA_FE32_ADD 1
+#define MINA_FE32_SUB 2
+#define MINA_FE32_NEG 3
+#define MINA_FE32_DBL 4
+#define MINA_FE32_MUL 5
+#define MINA_FE32_SQR 6
+#define MINA_FE32_DOT2 7
+#define MINA_FE32_DOT3 8
+#define MINA_FE32_TO_MONT 9
+#define MINA_FE32_FROM_MONT 10
+#define MINA_FE32_INV 11
+#define MINA_FE32_SQRT 12
+#define MINA_FE32_WORDS_CANONICAL 13
+#define MINA_FE32_DBL_AFFINE 32
+#define MINA_FE32_XYZZ_DBL 33
+#define MINA_FE32_ADD_AFFINE 34
+#define MINA_FE32_XYZZ_ADD 35
+#define MINA_FE32_XYZZ_DBL_QUAD 36
+#define MINA_FE32_XYZZ_ADD_QUAD 37
+int mina_selftest_fe32(mina_ctx *ctx, int field, int op, size_t n, const uint32_t *rows_in /* n*65 */, uint32_t *rows_out /* n*33 */);
 
 /* ---- a8 / a10: combined IPA check ------------------------------------------------------------ */
 /* Accumulator check (a10) for `batch` proofs on the SRS of `curve`:

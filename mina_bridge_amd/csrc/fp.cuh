@@ -272,7 +272,8 @@ template <int F> MB_HD fe_t fe_mul_portable(const fe_t &a, const fe_t &b) {
             c = (uint64_t)a.v[j] * bi + t[j] + c;
             t[j] = (uint32_t)c; c >>= 32;
         }
-        t[8] += (uint32_t)c;                                 // t < 2^288 here, no further carry
+        const uint64_t top = (uint64_t)t[8] + c;             // t < 2^288 + p here: an operand that is NOT reduced (a >= 2^256 - 2^224 against a digit 0xffffffff of b) carries
+        t[8] = (uint32_t)top;                                 // out of the ninth word -- kept in `top` and added back after the shift (t < 2^257 there)
         const uint32_t m = 0u - t[0];
         uint64_t k = (t[0] != 0) ? 1u : 0u;                  // carry of t0 + m * 1
         k = (uint64_t)m * FieldP<F>::P1 + t[1] + k; t[0] = (uint32_t)k; k >>= 32;
@@ -282,7 +283,7 @@ template <int F> MB_HD fe_t fe_mul_portable(const fe_t &a, const fe_t &b) {
         k = (uint64_t)t[5] + k; t[4] = (uint32_t)k; k >>= 32;
         k = (uint64_t)t[6] + k; t[5] = (uint32_t)k; k >>= 32;
         k = ((uint64_t)m << 30) + t[7] + k; t[6] = (uint32_t)k; k >>= 32;
-        k = (uint64_t)t[8] + k; t[7] = (uint32_t)k; t[8] = (uint32_t)(k >> 32);
+        k = (uint64_t)t[8] + k; t[7] = (uint32_t)k; t[8] = (uint32_t)(k >> 32) + (uint32_t)(top >> 32);
     }
     fe_t r;
 #pragma unroll

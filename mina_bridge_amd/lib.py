@@ -31,7 +31,7 @@ EXPORTS = [
     "mina_b_poly", "mina_b_poly_coefficients", "mina_b_poly_fold", "mina_b_poly_fold_dev",
     "mina_poseidon_set_params", "mina_poseidon_params_parse", "mina_poseidon_load_params", "mina_poseidon_load_params_file", "mina_poseidon_permute", "mina_poseidon_permute_dev", "mina_poseidon_hash",
     "mina_challenge_to_field", "mina_fq_sponge_run", "mina_to_group", "mina_merkle_roots", "mina_merkle_verify_batch",
-    "mina_field_mul", "mina_field_inv", "mina_field_sqrt", "mina_selftest_group_law", "mina_selftest_fe29",
+    "mina_field_mul", "mina_field_inv", "mina_field_sqrt", "mina_selftest_group_law", "mina_selftest_fe29", "mina_selftest_fe32",
     "mina_accumulator_check_batch", "mina_accumulator_check_dev", "mina_accumulator_check_multi_dev", "mina_accumulator_check_multi", "mina_ipa_batch_check",
     "mina_consensus_project_window", "mina_consensus_relative_min_window_density", "mina_consensus_is_short_range",
     "mina_protocol_state_pack", "mina_protocol_state_hash_batch", "mina_protocol_state_hash_bytes",
@@ -237,6 +237,12 @@ FE29_OPS = {"MUL_ASM": 0, "SQR_ASM": 1, "DOT2_ASM": 2, "DOT3_ASM": 3, "SQR_HI_AS
             "SUB_KP_ONE": 32, "KP_MINUS_NEG_Y": 33, "KP_MINUS_SUB_X1": 34, "KP_MINUS_SUB_Y1": 35, "KP_MINUS_G_U1": 36, "KP_MINUS_G_S1": 37, "KP_MINUS_A_2B_X3_SUB": 38,
             "KP_MINUS_A_2B_G_X3_SUB": 39, "ADD_KP_MINUS_SUB_X3": 40, "ADD_KP_MINUS_G_SUB_X3": 41, "ADD": 42, "ADD3": 43, "WORDS": 44, "IS_MULTIPLE_OF_P": 45, "LEAVE": 46,
             "ADD_AFFINE": 64, "ADD_AFFINE_TWIN": 65, "XYZZ_ADD": 66, "XYZZ_LEAVE": 67}
+# mina_selftest_fe32 (include/mina_verify.h MINA_FE32_*)
+FE32_IN_OPERANDS, FE32_OUT_RESULTS = 8, 4
+FE32_IN_WORDS, FE32_OUT_WORDS = FE32_IN_OPERANDS * 8 + 1, FE32_OUT_RESULTS * 8 + 1
+FE32_FLAG_TRUE, FE32_FLAG_LANES_AGREE = 1, 2
+FE32_OPS = {"COND_SUB_P": 0, "ADD": 1, "SUB": 2, "NEG": 3, "DBL": 4, "MUL": 5, "SQR": 6, "DOT2": 7, "DOT3": 8, "TO_MONT": 9, "FROM_MONT": 10, "INV": 11, "SQRT": 12,
+            "WORDS_CANONICAL": 13, "DBL_AFFINE": 32, "XYZZ_DBL": 33, "ADD_AFFINE": 34, "XYZZ_ADD": 35, "XYZZ_DBL_QUAD": 36, "XYZZ_ADD_QUAD": 37}
 
 
 class KimchiBatchOut(ctypes.Structure):
@@ -898,6 +904,14 @@ class MinaContext:
         rows = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1, FE29_IN_WORDS)
         out = np.empty((rows.shape[0], FE29_OUT_WORDS), np.uint32)
         self._ck(self._lib.mina_selftest_fe29(self._h, int(field), int(op), ctypes.c_size_t(rows.shape[0]), _p(rows), _p(out)), "mina_selftest_fe29")
+        return out
+
+    def selftest_fe32(self, field: int, op: int, rows) -> np.ndarray:
+        """one routine of the 8 x 32 layer (fp.cuh / ec.cuh / fe_inv, fe_sqrt; op = FE32_OPS[name]) on rows of FE32_IN_WORDS uint32 words -- 8 operands of 8 words and a
+        flag word -- -> rows of FE32_OUT_WORDS words: 4 results of 8 words and a flag word.  Test-facing: raw words, the caller owns each routine's contract"""
+        rows = np.ascontiguousarray(rows, dtype=np.uint32).reshape(-1, FE32_IN_WORDS)
+        out = np.empty((rows.shape[0], FE32_OUT_WORDS), np.uint32)
+        self._ck(self._lib.mina_selftest_fe32(self._h, int(field), int(op), ctypes.c_size_t(rows.shape[0]), _p(rows), _p(out)), "mina_selftest_fe32")
         return out
 
     # -- a10 / a8

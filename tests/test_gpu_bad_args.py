@@ -57,6 +57,16 @@ def test_bad_arguments_are_errors_not_crashes(ctx_srs):
     with pytest.raises(m.MinaError, match="bad op"):
         c.selftest_fe29(0, 31, rows_in)
     assert lib.mina_selftest_fe29(c._h, 0, op, ctypes.c_size_t(1), pin, pout) == 0 and not rows_out[9:].any()
+    # the 8 x 32 self-test hook, the same way
+    rows_in, rows_out = np.zeros(m.lib.FE32_IN_WORDS, np.uint32), np.full(m.lib.FE32_OUT_WORDS, 7, np.uint32)
+    pin, pout, op = rows_in.ctypes.data_as(ctypes.c_void_p), rows_out.ctypes.data_as(ctypes.c_void_p), m.lib.FE32_OPS["MUL"]
+    for bad in ((None, 0, op, 1, pin, pout), (c._h, 0, op, 1, None, pout), (c._h, 0, op, 1, pin, None), (c._h, 2, op, 1, pin, pout), (c._h, -1, op, 1, pin, pout),
+                (c._h, 0, max(m.lib.FE32_OPS.values()) + 1, 1, pin, pout), (c._h, 0, -1, 1, pin, pout), (c._h, 0, 14, 1, pin, pout), (c._h, 0, op, (1 << 22) + 1, pin, pout)):
+        assert lib.mina_selftest_fe32(bad[0], bad[1], bad[2], ctypes.c_size_t(bad[3]), bad[4], bad[5]) == MINA_ERR_ARG, bad[1:4]
+    assert 14 not in m.lib.FE32_OPS.values() and lib.mina_selftest_fe32(c._h, 0, op, ctypes.c_size_t(0), None, None) == 0      # (a gap between the op groups; no rows: nothing to do)
+    with pytest.raises(m.MinaError, match="bad op"):
+        c.selftest_fe32(0, 31, rows_in)
+    assert lib.mina_selftest_fe32(c._h, 0, op, ctypes.c_size_t(1), pin, pout) == 0 and not rows_out.any()                      # 0 * 0, unused slots and the flag zero
     # and the context still computes
     one = np.zeros(32, np.uint8); one[0] = 1
     assert (c.msm_srs(1, one) == c.srs_get_g(1, 0, 1)[0]).all()

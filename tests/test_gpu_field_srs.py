@@ -13,6 +13,8 @@ MODS = {0: 0x40000000000000000000000000000000224698FC094CF91B992D30ED00000001,
 
 
 def edge_values(oracle, field):
+    """edges of the VALUES (0, 1, p - 1, the halves, 2^254), not of the arithmetic: the hooks convert to Montgomery form first, so the limbs the carry chains and the
+    products see are pseudo-random images and only 0 stays an edge.  The limb-level corners are fed raw by tests/test_gpu_fe32.py"""
     p = MODS[field]
     return oracle.ints_to_le([0, 1, 2, p - 1, p - 2, (p - 1) // 2, (p + 1) // 2, 1 << 254, (1 << 128) - 1, 5])
 
