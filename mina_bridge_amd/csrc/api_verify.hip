@@ -56,7 +56,17 @@ constexpr int NSLOT = 16;                  // most chunks in flight per device (
 // `up`: the slot's upload stream.  No copy of the pipeline waits for a kernel: the copy engines take their commands in order, and one that waits for a
 // kernel of its stream holds up the uploads of every other chunk queued behind it (calls of 65 536 proofs: the jobs of the 8 chunks started up to 300 ms
 // apart, rocprofv3 timeline).  So uploads have a stream of their own, and the verdict words go back through a kernel that writes the page-locked buffer.
-struct Slot { PinnedBuf host, out, pk_host /* MINA_VERIFY_PACK_ON_DEVICE: the front end's inputs (PackStage) */; DevBuf dev, pk_dev; hipStream_t up = nullptr; hipEvent_t ev = nullptr, ev_up = nullptr; hipEvent_t tev[3] = {nullptr, nullptr, nullptr}; std::vector<hipEvent_t> rec_ev; bool busy = false; };
+struct Slot { PinnedBuf host, out, pk_host /* MINA_VERIFY_PACK_ON_DEVICE: the front end's inputs (PackStage) */; DevBuf dev, pk_dev; hipStream_t up = nullptr; hipEvent_t ev = nullptr, ev_up = nullptr; hipEvent_t tev[3] = {nullptr, nullptr, nullptr}; std::vector<hipEvent_t> rec_ev; bool busy = false;
+    void destroy() {                       // everything the slot owns (the last job on it first); caller holds the device's locks, the slot's device is current
+        if (ev) { (void)hipEventSynchronize(ev); (void)hipEventDestroy(ev); }
+        for (auto &e : tev) if (e) (void)hipEventDestroy(e);
+        for (auto &e : rec_ev) if (e) (void)hipEventDestroy(e);
+        if (ev_up) (void)hipEventDestroy(ev_up);
+        if (up) (void)hipStreamDestroy(up);
+        ev = ev_up = tev[0] = tev[1] = tev[2] = nullptr; rec_ev.clear(); up = nullptr;
+        host.release(); out.release(); dev.release(); pk_host.release(); pk_dev.release();
+    }
+};
 struct Device {
     mina_ctx *c = nullptr; int ordinal = 0;
     std::mutex mu;                         // serialises every call into `c` (a context has ONE current-lane cursor)
@@ -70,6 +80,12 @@ struct Device {
     std::mutex slot_mu; std::condition_variable slot_cv; Slot slots[NSLOT];
     uint32_t prepared_npub = 0xffffffffu;
     std::atomic<unsigned> inflight{0};
+    int try_acquire(int nslot) {           // a free slot among the first `nslot`, or -1
+        std::lock_guard<std::mutex> lk(slot_mu);
+        for (int s = 0; s < nslot; ++s) if (!slots[s].busy) { slots[s].busy = true; return s; }
+        return -1;
+    }
+    void release(int s) { { std::lock_guard<std::mutex> lk(slot_mu); slots[s].busy = false; } slot_cv.notify_all(); }
 };
 std::mutex g_mu;                           // guards the device list, the flags and set-up
 std::vector<Device *> g_devs; bool g_init_failed = false;
@@ -108,7 +124,7 @@ void destroy_devices() {                    // caller holds g_mu
         { std::lock_guard<std::mutex> sl(d->search_mu);       // lock order: search_mu before mu (the installers', the fallback's)
           std::lock_guard<std::mutex> lk(d->mu);
           (void)hipSetDevice(d->c->device);
-          for (Slot &s : d->slots) { if (s.ev) { (void)hipEventSynchronize(s.ev); (void)hipEventDestroy(s.ev); } for (auto &e : s.tev) if (e) (void)hipEventDestroy(e); for (auto &e : s.rec_ev) if (e) (void)hipEventDestroy(e); s.rec_ev.clear(); if (s.ev_up) (void)hipEventDestroy(s.ev_up); if (s.up) (void)hipStreamDestroy(s.up); s.ev_up = nullptr; s.up = nullptr; s.host.release(); s.out.release(); s.dev.release(); }
+          for (Slot &s : d->slots) s.destroy();
           mina_ctx_destroy(d->sc);                            // the view first: it borrows c's buffers
           mina_ctx_destroy(d->c); }
         delete d;
@@ -241,7 +257,7 @@ static inline void launch_words_out(hipStream_t st, uint32_t words, const uint32
 // bytes -> bools, pipelined (core/src/aligned.rs:31-58 builds the bytes; core/src/proof/state_proof.rs:10-41 their layout):
 //   a call is cut into chunks of 8192 proofs; the host pool parses a chunk STRAIGHT INTO the page-locked structure-of-arrays staging of its
 //   slot, in two halves -- the wrap proofs, then the 17 protocol states per proof (`to_input` flattening, ledger / consensus checks) -- and each
-//   half goes to the GPU as soon as it exists (issue_legs / stream_records / finish in run_device; mb_state_jobs_on_lane: no host synchronisation
+//   half goes to the GPU as soon as it exists (issue_legs / stream_records / finish of ShapePass; mb_state_jobs_on_lane: no host synchronisation
 //   inside); up to four chunks are on the GPU at a time, verdict words come back through page-locked memory.  No per-call allocation, no gather
 //   copy.  A chunk whose folded check fails goes through the culprit search of mina_state_job_batch from the same staging.
 namespace {
@@ -487,6 +503,10 @@ Config read_config(Device &D, uint32_t flags, int network) {
     return cf;
 }
 
+Shape shape_of_config(const Config &cf) {      // what the installed indexes say of a job's shape (n_old / n_ev: the proofs')
+    Shape sh; sh.kimchi = cf.kimchi; sh.statements = cf.kimchi && cf.statements; sh.k = cf.k; sh.network = cf.network; sh.feature_aware = cf.feature_aware;
+    return sh;
+}
 struct CallIn { const uint8_t *const *proofs; const size_t *proof_lens; const uint8_t *const *pubs; const size_t *pub_lens; };
 
 // MINA_VERIFY_PACK_ON_DEVICE: what mina_state_frontend_dev reads for a chunk of n entries, one block in the slot's page-locked pk_host and its twin in pk_dev:
@@ -517,87 +537,351 @@ double ms_since(std::chrono::steady_clock::time_point t) { return std::chrono::d
 // what a caller of the pipeline copied under g_mu (lock order: g_mu before any D.mu) + the tuning of the call
 struct CallEnv { uint32_t flags = 0; int network = -1; mina_verify_tuning tu; };
 
-// verdict bytes of the proofs idx[0..m) of the call on device D that share ONE evaluation / recursion shape; well-formed proofs of another
-// shape are returned in `deferred` (their verdict bytes stay 0 until the caller runs them as a job of their own)
-int run_device_shape(Device &D, const CallIn &in, const std::vector<size_t> &idx, uint8_t *verdicts, const CallEnv &env, std::vector<size_t> &deferred) {
+// evaluation / recursion shape of the job over the proofs idx[..] of a call (Mina's blockchain proofs all share one): the most frequent shape among up to 9
+// proofs spread over the call -- one odd-shaped proof at the head of a merged job must not send every other caller's proof through a second job --
+// and, when none of the sampled ones parses, the first proof that does.  false: nothing parses
+bool vote_shape(const CallIn &in, const std::vector<size_t> &idx, Shape &sh) {
     const size_t m = idx.size();
-    const uint32_t flags = env.flags; const mina_verify_tuning &tu = env.tu;
-    deferred.clear();
-    for (size_t i = 0; i < m; ++i) verdicts[idx[i]] = 0;
-    if (m == 0) return MINA_OK;
-    const auto t_call = std::chrono::steady_clock::now();
-    const Config cf = read_config(D, flags, env.network);
-    if (!cf.usable) return MINA_OK;
-    if (!cf.kimchi && !(flags & MINA_VERIFY_ALLOW_MISSING_KIMCHI)) return MINA_OK;          // the kimchi step cannot run: nothing can pass
-    Shape sh; sh.kimchi = cf.kimchi; sh.statements = cf.kimchi && cf.statements; sh.k = cf.k; sh.network = cf.network; sh.feature_aware = cf.feature_aware;
-    if (sh.statements) {           // evaluation / recursion shape of the job (Mina's blockchain proofs all share one): the most frequent shape among up to 9
-        // proofs spread over the call -- one odd-shaped proof at the head of a merged job must not send every other caller's proof through a second job --
-        // and, when none of the sampled ones parses, the first proof that does
-        auto shape_of = [&](size_t q, uint32_t &n_old, uint32_t &n_ev) -> bool {
-            if (!in.proofs[q]) return false;
-            mw::StateProofContainer &box = tl_box();
-            mw::Bincode cur(in.proofs[q], in.proof_lens[q]);
-            if (!mw::read_wrap_proof(cur, box.tip_proof)) return false;
-            const size_t a = box.tip_proof.step_old_bulletproof_challenges.size(), b = box.tip_proof.prev_evals.size();
-            if (a > 4 || b < 43 || b > 62) return false;
-            n_old = (uint32_t)a; n_ev = (uint32_t)b; return true;
-        };
-        std::vector<std::pair<uint32_t, uint32_t>> votes;
-        const size_t samples = std::min<size_t>(m, 9);
-        for (size_t i = 0; i < samples; ++i) { uint32_t a, b; if (shape_of(idx[samples > 1 ? i * (m - 1) / (samples - 1) : 0], a, b)) votes.push_back({a, b}); }
-        bool found = false;
-        if (!votes.empty()) {
-            size_t best = 0;
-            for (auto &v : votes) { const size_t cnt = (size_t)std::count(votes.begin(), votes.end(), v); if (cnt > best) { best = cnt; sh.n_old = v.first; sh.n_ev = v.second; } }
-            found = true;
-        }
-        for (size_t i = 0; i < m && !found; ++i) found = shape_of(idx[i], sh.n_old, sh.n_ev);
-        if (!found) return MINA_OK;                                                          // nothing parses
-    }
-    // read per call (tests force tiny chunks / shards to drive the pipeline's slot recycling with a handful of proofs)
-    // Measured on one MI355X (tools/boundary_sweep.sh, bench.py --boundary-only): 8192 full-size proofs as ONE chunk 55 - 58 ms, 2 x 4096: 74 ms,
-    // 8 x 1024: 87 ms, 16 x 512: 92 ms -- a job is a ~30 ms dependent chain of small kernels whatever its size, and jobs that start together do
-    // not fill each other's gaps the way the staggered steps of a long-running pipeline do.  Bigger calls in chunks of 8192 (16 384 proofs: 92 ms
-    // against 121 ms in chunks of 4096; 65 536: 305 against 336 ms = 215 k proofs/s): their parsing and upload overlap the previous chunk's job,
-    // and one bad proof costs a culprit search over 8192, not over everything.
-    const size_t chunk_target = std::max<size_t>(1, tu.chunk);
-    const size_t single_max = std::max<size_t>(1, tu.single_max);
-    const size_t nchunks = m <= single_max ? 1 : (m + chunk_target - 1) / chunk_target;
-    // chunks of ONE call on the GPU at a time (the next ones are parsed meanwhile)
-    // A call of more chunks than the window is a pipeline: jobs that enter the GPU together also leave it together (4 jobs started within 15 ms: all done
-    // at ~185 ms, then the next 4 -- 65 536 proofs: 345 ms), jobs one period apart keep the chip filled while one of them drains (four caller threads
-    // with 8192 proofs each reach 238 k proofs/s that way).  So the first `window` chunks of such a call are issued `pace_ms` apart.
-    const double pace_ms = tu.pace_us * 1e-3;
-    // (no parsing ahead of the window: a slot is a staging buffer AND four streams, and with more streams in use than the runtime's 16 hardware queues the
-    // jobs' legs wait for each other -- 65 536 proofs per call: 342 ms with two chunks parsed ahead, 285 ms with none; the wrap-proof halves of a chunk take 1 ms)
-    // slots of the device in use, over all callers: 4 jobs with their legs forked = 16 streams = the runtime's hardware queues (two callers of 32 768 proofs
-    // with 16 slots: 125 k proofs/s, six callers of 8192: 205 k -- against 235 k for four)
-    const size_t head_min = tu.head_min;      // 0: every streamed chunk; huge: never
-    const int nslot = std::min(NSLOT, std::max(1, (int)tu.slots));
-    const size_t ahead = tu.ahead;
-    const size_t window = std::max<size_t>(1, tu.window);
-    // streamed form of a chunk (stream_records below): from `early_min` entries, in runs of `early_sub` (0 = off)
-    const size_t early_min = std::max<size_t>(1, tu.early_min);
-    const size_t early_sub = tu.early_sub;
-    std::vector<Chunk> chunks(nchunks);
-    for (size_t q = 0; q < nchunks; ++q) { chunks[q].lo = m * q / nchunks; chunks[q].n = m * (q + 1) / nchunks - chunks[q].lo; chunks[q].hb.resize(chunks[q].n); }
-    const size_t cap = (m + nchunks - 1) / nchunks;
-    Layout lay; lay.build(sh, cap);
-    mina_ctx *c = D.c;
-    int rc_all = MINA_OK;
-    // MINA_VERIFY_PACK_ON_DEVICE: the pool parses the wrap-proof halves only; the protocol-state bytes of a chunk go to the GPU as they are and the front end
-    // (api_pack.hip, through the context's pointer: null in a context that links no kernel = the host path) writes S_REC / S_NF / S_PRE in the device staging.
-    // The state leg then runs whole in finish(), as under MINA_VERIFY_DEDUP_STATES.
-    const bool pack = (flags & MINA_VERIFY_PACK_ON_DEVICE) && c->state_frontend;
-
-    auto try_acquire = [&]() -> int {
-        std::lock_guard<std::mutex> lk(D.slot_mu);
-        for (int s = 0; s < nslot; ++s) if (!D.slots[s].busy) { D.slots[s].busy = true; return s; }
-        return -1;
+    auto shape_of = [&](size_t q, uint32_t &n_old, uint32_t &n_ev) -> bool {
+        if (!in.proofs[q]) return false;
+        mw::StateProofContainer &box = tl_box();
+        mw::Bincode cur(in.proofs[q], in.proof_lens[q]);
+        if (!mw::read_wrap_proof(cur, box.tip_proof)) return false;
+        const size_t a = box.tip_proof.step_old_bulletproof_challenges.size(), b = box.tip_proof.prev_evals.size();
+        if (a > 4 || b < 43 || b > 62) return false;
+        n_old = (uint32_t)a; n_ev = (uint32_t)b; return true;
     };
-    auto release = [&](int s) { { std::lock_guard<std::mutex> lk(D.slot_mu); D.slots[s].busy = false; } D.slot_cv.notify_all(); };
+    std::vector<std::pair<uint32_t, uint32_t>> votes;
+    const size_t samples = std::min<size_t>(m, 9);
+    for (size_t i = 0; i < samples; ++i) { uint32_t a, b; if (shape_of(idx[samples > 1 ? i * (m - 1) / (samples - 1) : 0], a, b)) votes.push_back({a, b}); }
+    bool found = false;
+    if (!votes.empty()) {
+        size_t best = 0;
+        for (auto &v : votes) { const size_t cnt = (size_t)std::count(votes.begin(), votes.end(), v); if (cnt > best) { best = cnt; sh.n_old = v.first; sh.n_ev = v.second; } }
+        found = true;
+    }
+    for (size_t i = 0; i < m && !found; ++i) found = shape_of(idx[i], sh.n_old, sh.n_ev);
+    return found;
+}
 
-    auto fallback = [&](Chunk &ch) -> int {     // a folded check of the chunk failed: per-proof verdicts through the culprit search, from the same staging
+// One pass of the pipeline: verdict bytes of the proofs idx[0..m) of the call on device D that share ONE evaluation / recursion shape; well-formed proofs of another
+// shape are returned in `deferred` (their verdict bytes stay 0 until the caller runs them as a job of their own).  The members, by what they do for a chunk:
+// PARSE (the pool's jobs), STAGE (its slot, the tables prepared), QUEUE (its three steps onto the GPU), COLLECT (verdicts, culprit search) and run(), the DRIVER;
+// the job's SHAPE is vote_shape's.  The pool's jobs hold `this` and a Chunk *: `chunks` is sized once, before the first of them is submitted.
+struct ShapePass {
+    Device &D; const CallIn &in; const std::vector<size_t> &idx; uint8_t *const verdicts; std::vector<size_t> &deferred;
+    const uint32_t flags; const int network; const mina_verify_tuning &tu; const size_t m; mina_ctx *const c;
+    const std::chrono::steady_clock::time_point t_call = std::chrono::steady_clock::now();
+    const size_t chunk_target, single_max, nchunks; const double pace_ms; const size_t head_min; const int nslot; const size_t ahead, window, early_min, early_sub; const bool own_up, pack;
+    const HashLaunch hash_launch; std::vector<Chunk> chunks;
+    Shape sh; uint32_t prep_key = 0; Layout lay; int rc_all = MINA_OK;
+
+    ShapePass(Device &D_, const CallIn &in_, const std::vector<size_t> &idx_, uint8_t *verdicts_, const CallEnv &env, std::vector<size_t> &deferred_)
+        : D(D_), in(in_), idx(idx_), verdicts(verdicts_), deferred(deferred_), flags(env.flags), network(env.network), tu(env.tu), m(idx_.size()), c(D_.c),
+          // read per call (tests force tiny chunks / shards to drive the pipeline's slot recycling with a handful of proofs)
+          // Measured on one MI355X (tools/boundary_sweep.sh, bench.py --boundary-only): 8192 full-size proofs as ONE chunk 55 - 58 ms, 2 x 4096: 74 ms,
+          // 8 x 1024: 87 ms, 16 x 512: 92 ms -- a job is a ~30 ms dependent chain of small kernels whatever its size, and jobs that start together do
+          // not fill each other's gaps the way the staggered steps of a long-running pipeline do.  Bigger calls in chunks of 8192 (16 384 proofs: 92 ms
+          // against 121 ms in chunks of 4096; 65 536: 305 against 336 ms = 215 k proofs/s): their parsing and upload overlap the previous chunk's job,
+          // and one bad proof costs a culprit search over 8192, not over everything.
+          chunk_target(std::max<size_t>(1, tu.chunk)), single_max(std::max<size_t>(1, tu.single_max)), nchunks(m <= single_max ? 1 : (m + chunk_target - 1) / chunk_target),
+          // chunks of ONE call on the GPU at a time (the next ones are parsed meanwhile)
+          // A call of more chunks than the window is a pipeline: jobs that enter the GPU together also leave it together (4 jobs started within 15 ms: all done
+          // at ~185 ms, then the next 4 -- 65 536 proofs: 345 ms), jobs one period apart keep the chip filled while one of them drains (four caller threads
+          // with 8192 proofs each reach 238 k proofs/s that way).  So the first `window` chunks of such a call are issued `pace_ms` apart.
+          pace_ms(tu.pace_us * 1e-3),
+          // (no parsing ahead of the window: a slot is a staging buffer AND four streams, and with more streams in use than the runtime's 16 hardware queues the
+          // jobs' legs wait for each other -- 65 536 proofs per call: 342 ms with two chunks parsed ahead, 285 ms with none; the wrap-proof halves of a chunk take 1 ms)
+          // slots of the device in use, over all callers: 4 jobs with their legs forked = 16 streams = the runtime's hardware queues (two callers of 32 768 proofs
+          // with 16 slots: 125 k proofs/s, six callers of 8192: 205 k -- against 235 k for four)
+          head_min(tu.head_min),      // 0: every streamed chunk; huge: never
+          nslot(std::min(NSLOT, std::max(1, (int)tu.slots))), ahead(tu.ahead), window(std::max<size_t>(1, tu.window)),
+          // streamed form of a chunk (stream_records below): from `early_min` entries, in runs of `early_sub` (0 = off)
+          early_min(std::max<size_t>(1, tu.early_min)), early_sub(tu.early_sub), own_up(tu.up_stream != 0),
+          // MINA_VERIFY_PACK_ON_DEVICE: the pool parses the wrap-proof halves only; the protocol-state bytes of a chunk go to the GPU as they are and the front end
+          // (api_pack.hip, through the context's pointer: null in a context that links no kernel = the host path) writes S_REC / S_NF / S_PRE in the device staging.
+          // The state leg then runs whole in finish(), as under MINA_VERIFY_DEDUP_STATES.
+          pack((flags & MINA_VERIFY_PACK_ON_DEVICE) && c->state_frontend),
+          hash_launch{tu.hash_piece_waves, 0}, chunks(nchunks) {}     // a chunk's state hashes go out in pieces, early ones and the rest alike
+
+    // ---------------------------------------------------------------------------------------------- parse
+    // a slot is taken: the pool's jobs over the chunk's entries, straight into the slot's page-locked staging
+    void submit_parsing(Chunk &ch) {
+        uint8_t *hbase = (uint8_t *)ch.slot->host.p;
+        Chunk *chp = &ch;
+        ch.sub = (early_sub && ch.n >= early_min && !pack) ? early_sub : ch.n; ch.nsub = (ch.n + ch.sub - 1) / ch.sub;
+        ch.sub_left.reset(new std::atomic<uint32_t>[ch.nsub]);
+        for (size_t r = 0; r < ch.nsub; ++r) ch.sub_left[r].store((uint32_t)(std::min(ch.n, (r + 1) * ch.sub) - r * ch.sub));
+        // the pool's order per chunk: the FIRST run whole (both halves: the state leg is the later one of a lone job, its first piece of hashes needs
+        // ~600 entries), then the wrap-proof halves of the rest (A), then their protocol states (B)
+        // (from ~6000 entries: below, the wrap-proof chain is the later leg and must not wait -- 4096 per call: 34.6 ms without, 35.4 with; 8192: 45.8 / 44.4)
+        const size_t head = (ch.nsub > 1 && ch.n >= head_min) ? ch.sub : 0;
+        ch.head = head;
+        auto run_done = [chp](size_t b) { if (chp->sub_left[b / chp->sub].fetch_sub(1) == 1) { std::lock_guard<std::mutex> lk(chp->mu); chp->cv.notify_all(); } };
+        ch.jobH = mb_pool_submit(head, [this, chp, hbase, run_done](size_t b) {
+            const size_t q = idx[chp->lo + b];
+            parse_proof_half(sh, lay, hbase, b, in.proofs[q], in.proof_lens[q], in.pubs[q], in.pub_lens[q], chp->hb[b], c);
+            parse_states_half(lay, hbase, b, in.proofs[q], in.proof_lens[q], in.pubs[q], in.pub_lens[q], chp->hb[b]);
+            run_done(b);
+        });
+        ch.jobA = mb_pool_submit(ch.n - head, [this, chp, hbase, head](size_t i) {
+            const size_t b = head + i, q = idx[chp->lo + b];
+            parse_proof_half(sh, lay, hbase, b, in.proofs[q], in.proof_lens[q], in.pubs[q], in.pub_lens[q], chp->hb[b], c);
+        });
+        ch.jobB = mb_pool_submit(pack ? 0 : ch.n - head, [this, chp, hbase, head, run_done](size_t i) {      // (packed on the device: gather_states below, once job A is through)
+            mb_pool_wait(chp->jobA);                                  // the pool hands jobs out in order, but the last items of A may still be running
+            const size_t b = head + i, q = idx[chp->lo + b];
+            parse_states_half(lay, hbase, b, in.proofs[q], in.proof_lens[q], in.pubs[q], in.pub_lens[q], chp->hb[b]);
+            run_done(b);
+        });
+    }
+    // MINA_VERIFY_PACK_ON_DEVICE, once the wrap-proof halves of a chunk are parsed (they say where an entry's states begin): lay out the front end's inputs and let
+    // the pool copy every entry's state bytes and ledger hashes into them -- a copy, no byte of a state is looked at.  An entry whose first half did not parse
+    // gets an empty range: FORMAT fails on the device, its records are zero and its `precheck` 0, as clear_states_half leaves them on the host path.
+    int gather_states(Chunk &ch) {
+        size_t total = 0;
+        std::vector<uint64_t> at(ch.n + 1, 0);
+        for (size_t b = 0; b < ch.n; ++b) {
+            HostBits &hb = ch.hb[b]; const size_t q = idx[ch.lo + b];
+            hb.parsed = hb.proof_ok;                                  // the rest of FORMAT is the device's: it reaches the verdict through `precheck`
+            at[b] = total; if (hb.proof_ok) total += in.proof_lens[q] - hb.states_at;
+        }
+        at[ch.n] = total;
+        ch.pk.build(ch.n, total);
+        if (ch.slot->pk_host.ensure(ch.pk.total)) return MINA_ERR_HIP;
+        uint8_t *ph = (uint8_t *)ch.slot->pk_host.p;
+        uint64_t *pb = ch.pk.begin(ph), *pe = ch.pk.end(ph);
+        for (size_t b = 0; b < ch.n; ++b) { pb[b] = at[b]; pe[b] = ch.hb[b].proof_ok ? at[b + 1] : at[b]; }
+        memset(ph + 529 * ch.n, 0, ch.pk.blob - 529 * ch.n);
+        Chunk *chp = &ch;
+        ch.jobB = mb_pool_submit(ch.n, [this, chp, ph](size_t b) {
+            const HostBits &hb = chp->hb[b]; const size_t q = idx[chp->lo + b];
+            const uint64_t lo = chp->pk.begin(ph)[b], hi = chp->pk.end(ph)[b];
+            chp->pk.band(ph)[b] = (hb.proof_ok && hb.shape) ? 1 : 0;
+            if (hb.proof_ok) { memcpy(chp->pk.ledger(ph) + 512 * b, in.pubs[q] + 545, 512); memcpy(chp->pk.bytes(ph) + lo, in.proofs[q] + hb.states_at, hi - lo); }      // (proof_ok: the public input has its 1057 bytes)
+            else memset(chp->pk.ledger(ph) + 512 * b, 0, 512);
+        });
+        return MINA_OK;
+    }
+
+    // ---------------------------------------------------------------------------------------------- stage
+    // D.mu, taken with the tables of this call's (domain, npub) prepared.  A re-prepare (another index since the last call) frees and rewrites the Lagrange tables --
+    // buffers a culprit search on the view context D.sc may be reading through its aliases, holding search_mu only (ADVICE r05, medium: round 5 re-prepared under
+    // D.mu alone).  So the re-prepare takes search_mu as well, FIRST (lock order g_mu, search_mu, mu: the installers', the fallback's); the common path -- already
+    // prepared -- never touches search_mu and never waits for a search.
+    int lock_prepared(std::unique_lock<std::mutex> &lk) {
+        for (;;) {
+            lk = std::unique_lock<std::mutex>(D.mu);
+            if (D.prepared_npub == prep_key) return MINA_OK;
+            lk.unlock();
+            std::lock_guard<std::mutex> sl(D.search_mu);
+            std::lock_guard<std::mutex> dl(D.mu);
+            if (D.prepared_npub == prep_key) continue;
+            HIPC(hipSetDevice(c->device));
+            int rc = mina_state_jobs_prepare(c, sh.k ? sh.k : 15, sh.statements ? 40 : 0);
+            if (rc) return rc;
+            D.prepared_npub = prep_key;
+        }
+    }
+    // device side of a chunk's slot, before anything is queued on it (idempotent).  Caller holds D.mu through lock_prepared.
+    int setup_slot(Chunk &ch) {
+        HIPC(hipSetDevice(c->device));
+        int rc;
+        if (D.prepared_npub != prep_key) return fail(MINA_ERR_STATE, "slot set up without the prepared tables");
+        Slot &S = *ch.slot;
+        if ((rc = S.dev.ensure(lay.total + Layout::out_bytes(lay.cap)))) return rc;
+        if (!S.ev) HIPC(hipEventCreateWithFlags(&S.ev, hipEventDisableTiming));
+        if (!S.ev_up) HIPC(hipEventCreateWithFlags(&S.ev_up, hipEventDisableTiming));
+        if (!S.up) HIPC(hipStreamCreateWithFlags(&S.up, hipStreamNonBlocking));
+        Lane &L = c->lanes[ch.slot_ix];
+        if (!L.stream) HIPC(hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking));
+        if (g_timing) for (auto &e : S.tev) if (!e) HIPC(hipEventCreate(&e));
+        return MINA_OK;
+    }
+    // the lanes of a chunk's job, decided once per chunk.  Caller holds D.mu.
+    int setup_legs(Chunk &ch) {
+        if (ch.legs_set) return MINA_OK;
+        ch.legs_set = true;
+        // few chunks in flight: the three legs of a job (state hashes / wrap proof / accumulator) go to three streams
+        // (up to 4 chunks in flight -- 32 768 proofs per call 186 -> 152 ms, three callers of 8192: 138 -> 158 k proofs/s; with 8 the streams outnumber the hardware queues: 322 -> 360 ms)
+        if (D.inflight.load() > tu.split_max) return MINA_OK;
+        Lane *LI = &c->lanes[MB_PIPE_LANES + 3 * ch.slot_ix], *LA = &c->lanes[MB_PIPE_LANES + 3 * ch.slot_ix + 1], *LS = &c->lanes[MB_PIPE_LANES + 3 * ch.slot_ix + 2];
+        // Alone on the GPU a job is a latency-bound chain of small kernels (~390 waves each, one behind the other) beside 20 ms of chip-filling
+        // hashes; where their waves share a SIMD both run at half speed, and the call waits for the chain (rocprofv3 timeline: the statement
+        // digests 10.7 ms beside the hashes against 4.1 ms alone).  So the chain's stream and the hashes' stream get DISJOINT CU masks: the chain
+        // `chain_cus` CUs -- 128 = a SIMD per wave; fewer and a kernel lasts as long as its doubled-up SIMDs: 96 CUs cost +16 ms -- the hashes the
+        // rest (bit i of a mask = CU i / 8 of XCD i % 8, tools/probes/cumask_probe.hip).  8192 proofs per call: 62.6 -> 57.7 ms.
+        const uint32_t chain_cus = tu.chain_cus;
+        int ncu = 0; (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device);
+        if (chain_cus > 0 && chain_cus < (uint32_t)ncu && ncu <= 256) {
+            const uint32_t period = std::max(1u, tu.cu_period);
+            auto masked = [&](Lane &ln, bool chain) -> int {
+                if (ln.stream) return MINA_OK;
+                uint32_t mk[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+                for (uint32_t b2 = 0; b2 < (uint32_t)ncu; ++b2) { const bool in_chain = (b2 % period) < chain_cus * period / 256; if (in_chain == chain) mk[b2 >> 5] |= 1u << (b2 & 31); }
+                if (hipExtStreamCreateWithCUMask(&ln.stream, 8, mk) != hipSuccess) {       // a runtime without CU masks: plain streams, the legs share the CUs
+                    (void)hipGetLastError(); ln.stream = nullptr;
+                    HIPC(hipStreamCreateWithFlags(&ln.stream, hipStreamNonBlocking));
+                }
+                return MINA_OK;
+            };
+            int rc;
+            if ((rc = masked(*LI, true)) || (rc = masked(*LS, false))) return rc;
+            // the accumulator leg (fold GEMM + one MSM: chip-filling kernels, done within ~8 ms) shares the chain's CUs: the hashes are the later leg of a lone
+            // job, and unmasked this leg slowed their first pieces (8192 per call: 45.4 -> 44.5 ms; mina_verify_tuning.acc_mask = 0 chain | 1 hash | 2 none)
+            if (tu.acc_mask == 0) { if ((rc = masked(*LA, true))) return rc; } else if (tu.acc_mask == 1) { if ((rc = masked(*LA, false))) return rc; }
+        } else LS = nullptr;
+        ch.LI = LI; ch.LA = LA; ch.LS = LS;
+        return MINA_OK;
+    }
+    // `lk` = D.mu with the tables prepared, the chunk's slot and legs set up, and the chunk marked: what is queued from here on must not outlive the slot (harvest)
+    int open_slot(Chunk &ch, std::unique_lock<std::mutex> &lk) {
+        int rc;
+        if ((rc = lock_prepared(lk)) || (rc = setup_slot(ch)) || (rc = setup_legs(ch))) return rc;
+        if (g_timing && !ch.queued) HIPC(hipEventRecord(ch.slot->tev[0], upload_stream(ch)));
+        ch.queued = true;
+        return MINA_OK;
+    }
+
+    // ---------------------------------------------------------------------------------------------- queue
+    // where a chunk's uploads go: the slot's own upload stream (see Slot::up), or the chunk's lane ...
+    hipStream_t upload_stream(const Chunk &ch) const { return own_up ? ch.slot->up : c->lanes[ch.slot_ix].stream; }
+    int lane_waits_for_uploads(Chunk &ch) {      // ... which then waits for what has been uploaded so far
+        if (own_up) { HIPC(hipEventRecord(ch.slot->ev_up, ch.slot->up)); HIPC(hipStreamWaitEvent(c->lanes[ch.slot_ix].stream, ch.slot->ev_up, 0)); }
+        return MINA_OK;
+    }
+    void lane_forms() { c->nlanes = (int)std::max(1u, std::min<unsigned>(D.inflight.load(), NSLOT)); }       // the lane forms of the sponge kernels follow the work in flight on the device (ctx.h use_coop*)
+    uint32_t *verdict_words(Chunk &ch) const { return (uint32_t *)(ch.slot->dev.as<uint8_t>() + lay.out_off()); }      // [n] verdicts, 4 flags of the folded checks, [n] statement words
+    StateJobPlan chunk_plan(Chunk &ch, uint32_t phase, uint32_t *d_stmt_out) {
+        StateJobPlan p; p.wrap = ch.LI; p.acc = ch.LA; p.states = ch.LS; p.phase = phase; p.carry = &ch.carry; p.d_stmt_out = d_stmt_out;
+        p.hashed_early = ch.hashed; p.hash = hash_launch;
+        return p;
+    }
+    // a phase of the chunk's job, over the device staging, on the chunk's lane (the caller made it the current one)
+    int queue_job(Chunk &ch, uint32_t phase) {
+        JobStructs js; make_jobs(sh, lay, ch.slot->dev.as<uint8_t>(), ch.n, true, true, true, js);
+        uint32_t *dv = verdict_words(ch), *df = dv + ch.n, *ds = df + 4;
+        const int rc = mb_state_jobs_on_lane(c, &js.j, dv, df, chunk_plan(ch, phase, ds));
+        c->use_lane0();
+        return rc;
+    }
+
+    // A chunk goes to the GPU in three steps, each as soon as its input is parsed (8192 full-size proofs per call: the job's wrap-proof chain
+    // takes ~42 ms on its CUs and the state hashes ~43 ms on theirs, so the call is as long as the later of the two STARTS):
+    //   issue_legs      after the wrap-proof halves (pool job A, ~1/3 of the parsing): patch, draw the randomisers, upload everything but the records,
+    //                   queue the accumulator and wrap-proof legs
+    //   stream_records  run by run of pool job B: upload the run's protocol-state records (34 KB of an entry's 47 KB) and queue their hashes
+    //   finish          upload `precheck`, queue the rest of the state leg, the joins and the verdict kernel, the download
+    int issue_legs(Chunk &ch) {
+        uint8_t *hbase = (uint8_t *)ch.slot->host.p;
+        // host side of the chunk: collect the other shapes, patch what cannot go to the GPU as it is
+        size_t donor = SIZE_MAX;
+        for (size_t b = 0; b < ch.n; ++b) { if (ch.hb[b].proof_ok && ch.hb[b].shape && donor == SIZE_MAX) donor = b; if (ch.hb[b].deferred) deferred.push_back(idx[ch.lo + b]); }
+        if (donor == SIZE_MAX) { ch.skipped = true; return MINA_OK; }                         // nothing of this chunk can pass
+        for (size_t b = 0; b < ch.n; ++b) if (!(ch.hb[b].proof_ok && ch.hb[b].shape)) copy_proof_half(lay, hbase, b, donor);
+        if (!ch.randomised) return fail(MINA_ERR_STATE, "no entropy for the folding randomisers");
+        std::unique_lock<std::mutex> lk;
+        int rc;
+        if ((rc = open_slot(ch, lk))) return rc;
+        lane_forms();
+        c->L = &c->lanes[ch.slot_ix];
+        uint8_t *dbase = ch.slot->dev.as<uint8_t>();
+        hipStream_t up = upload_stream(ch);
+        // everything behind the records and their field counts, EXCEPT `precheck`: the pool is still writing those bytes (parse_states_half) -- finish() sends them.
+        // (Until round 5 the one copy ran over them too and finish() re-sent them: harmless, since only the FINISH phase reads `precheck`, but a read of memory
+        // another thread is writing -- the one report of the ThreadSanitizer tier, tests/fuzz/tsan_boundary.cpp.)
+        HIPC(hipMemcpyAsync(dbase + lay.off[S_EXP], hbase + lay.off[S_EXP], lay.off[S_PRE] - lay.off[S_EXP], hipMemcpyHostToDevice, up));
+        HIPC(hipMemcpyAsync(dbase + lay.off[S_APRE], hbase + lay.off[S_APRE], lay.total - lay.off[S_APRE], hipMemcpyHostToDevice, up));
+        if ((rc = lane_waits_for_uploads(ch))) return rc;
+        return queue_job(ch, MB_JOB_LEGS);
+    }
+    int stream_records(Chunk &ch, size_t r_lo, size_t r_hi) {
+        uint8_t *hbase = (uint8_t *)ch.slot->host.p;
+        Slot &S = *ch.slot;
+        for (size_t r = r_lo; r < r_hi && r < ch.nsub; ++r) {
+            { std::unique_lock<std::mutex> lk(ch.mu); ch.cv.wait(lk, [&] { return ch.sub_left[r].load() == 0; }); }
+            const size_t lo = r * ch.sub, hi = std::min(ch.n, lo + ch.sub);
+            for (size_t b = lo; b < hi; ++b) if (!ch.hb[b].parsed) clear_states_half(lay, hbase, b);      // malformed (or of another shape / to be patched): defined records, verdict 0 through `precheck`
+            std::unique_lock<std::mutex> lk;
+            { int src; if ((src = open_slot(ch, lk))) return src; }
+            Lane &L = c->lanes[ch.slot_ix];
+            uint8_t *dbase = S.dev.as<uint8_t>();
+            if (S.rec_ev.size() < ch.nsub) S.rec_ev.resize(ch.nsub, nullptr);
+            if (!S.rec_ev[r]) HIPC(hipEventCreateWithFlags(&S.rec_ev[r], hipEventDisableTiming));
+            hipStream_t up = upload_stream(ch);
+            HIPC(hipMemcpyAsync(lay.at(dbase, S_REC, lo), lay.at(hbase, S_REC, lo), (hi - lo) * lay.stride[S_REC], hipMemcpyHostToDevice, up));
+            HIPC(hipMemcpyAsync(lay.at(dbase, S_NF, lo), lay.at(hbase, S_NF, lo), (hi - lo) * lay.stride[S_NF], hipMemcpyHostToDevice, up));
+            HIPC(hipEventRecord(S.rec_ev[r], up));
+            lane_forms();
+            // hashes in WHOLE pieces (a piece = `hash_piece_waves` waves of the form that runs -- 21 states each in the 3-lane form, 64 in the single-lane one (ctx.h
+            // hash_piece_states) -- = two waves on every SIMD of the state leg's 128 CUs): a run of
+            // 1024 entries is 829 waves -- launched run by run, a fifth of the leg's SIMDs would hold one wave where the others hold two, for as long
+            // The odd piece goes FIRST: it is complete after fewer runs, so the leg starts earlier, and it ends with a full piece instead of a half-empty one.
+            const size_t total = ch.n * MINA_STATES_PER_PROOF, piece = hash_piece_states(c, total, hash_launch.piece_waves), ready = hi * MINA_STATES_PER_PROOF;
+            const size_t first = piece ? (total % piece ? total % piece : piece) : 0;
+            const size_t upto = (r + 1 == ch.nsub || !piece) ? ready : (ready < first ? 0 : first + (ready - first) / piece * piece);
+            int rc = MINA_OK;
+            if (upto > ch.hashed && !(flags & MINA_VERIFY_DEDUP_STATES))      // deduplicated: the whole state leg runs in finish() (a piece cannot know its duplicates in later pieces)
+                rc = mb_state_hashes_early(c, ch.LS ? ch.LS : &L, ch.n * MINA_STATES_PER_PROOF, ch.hashed, upto - ch.hashed,
+                                           (const uint32_t *)lay.at(dbase, S_REC, 0), (const uint32_t *)lay.at(dbase, S_NF, 0), S.rec_ev[r], hash_launch);
+            c->use_lane0();
+            if (rc) return rc;
+            if (!(flags & MINA_VERIFY_DEDUP_STATES)) ch.hashed = std::max(ch.hashed, upto);
+        }
+        return MINA_OK;
+    }
+    int finish(Chunk &ch) {
+        uint8_t *hbase = (uint8_t *)ch.slot->host.p;
+        std::lock_guard<std::mutex> lk(D.mu);
+        HIPC(hipSetDevice(c->device));
+        Slot &S = *ch.slot;
+        Lane &L = c->lanes[ch.slot_ix];
+        lane_forms();
+        c->L = &L;
+        uint8_t *dbase = S.dev.as<uint8_t>();
+        hipStream_t up = upload_stream(ch);
+        int rc;
+        if (pack) { if ((rc = S.pk_dev.ensure(ch.pk.total))) return rc; HIPC(hipMemcpyAsync(S.pk_dev.p, S.pk_host.p, ch.pk.total, hipMemcpyHostToDevice, up)); }
+        else HIPC(hipMemcpyAsync(lay.at(dbase, S_PRE, 0), lay.at(hbase, S_PRE, 0), ch.n * lay.stride[S_PRE], hipMemcpyHostToDevice, up));
+        if (g_timing) HIPC(hipEventRecord(S.tev[1], up));
+        if ((rc = lane_waits_for_uploads(ch))) return rc;
+        if (pack) {       // records, field counts and `precheck` of the chunk, on its lane ahead of the state leg (which forks from this lane)
+            uint8_t *pd = S.pk_dev.as<uint8_t>();
+            rc = c->state_frontend(c, ch.n, ch.pk.bytes(pd), ch.pk.total - ch.pk.blob, ch.pk.begin(pd), ch.pk.end(pd), lay.at(dbase, S_EXP, 0), ch.pk.ledger(pd), ch.pk.band(pd),
+                                   lay.at(dbase, S_REC, 0), lay.at(dbase, S_NF, 0), lay.at(dbase, S_PRE, 0), nullptr);
+            if (rc) { c->use_lane0(); return rc; }
+        }
+        { const bool want = (flags & MINA_VERIFY_DEDUP_STATES) != 0; if (want != c->state_dedup && (rc = mb_ctx_state_dedup(c, want))) return rc; }      // MINA_VERIFY_DEDUP_STATES: per chunk, under the device's lock
+        if ((rc = queue_job(ch, MB_JOB_FINISH))) return rc;
+        if (g_timing) HIPC(hipEventRecord(S.tev[2], L.stream));
+        if (own_up) { const uint32_t words = (uint32_t)(Layout::out_bytes(ch.n) / 4); launch_words_out(L.stream, words, verdict_words(ch), (uint32_t *)S.out.p); HIPC(hipGetLastError()); }
+        else HIPC(hipMemcpyAsync(S.out.p, verdict_words(ch), Layout::out_bytes(ch.n), hipMemcpyDeviceToHost, L.stream));
+        HIPC(hipEventRecord(S.ev, L.stream));
+        ch.issued = true;
+        return MINA_OK;
+    }
+    // the three steps of chunk q, each behind the part of the parsing it needs
+    int queue_chunk(Chunk &ch, size_t q) {
+        ch.counted = true; D.inflight.fetch_add(1);
+        // the folding randomisers of the chunk's job (262 KB from the OS for 8192 proofs: ~0.5 ms), while the pool parses: the proofs are the caller's
+        // bytes, fixed since the call was made, and the values never leave the process
+        ch.randomised = draw_randomisers(sh, lay, (uint8_t *)ch.slot->host.p, ch.n);
+        int rc = ch.head ? stream_records(ch, 0, 1) : MINA_OK;          // the first run's records and hashes, ahead of everything else
+        mb_pool_wait(ch.jobH); mb_pool_wait(ch.jobA);
+        const double t_a = g_timing ? ms_since(t_call) : 0;
+        if (!rc && pack) rc = gather_states(ch);
+        if (!rc) rc = issue_legs(ch);
+        const double t_legs = g_timing ? ms_since(t_call) : 0;
+        if (!rc && !ch.skipped && !pack) rc = stream_records(ch, ch.head ? 1 : 0, ch.nsub);
+        mb_pool_wait(ch.jobB);
+        const double t_parsed = g_timing ? ms_since(t_call) : 0;
+        if (!rc && !ch.skipped) rc = finish(ch);
+        if (g_timing) fprintf(stderr, "mina_verify:   chunk %zu (%zu proofs): wrap proofs parsed at %.2f ms, legs queued at %.2f, states parsed at %.2f, all queued at %.2f ms\n", q, ch.n, t_a, t_legs, t_parsed, ms_since(t_call));
+        return rc;
+    }
+
+    // ---------------------------------------------------------------------------------------------- collect
+    int fallback(Chunk &ch) {     // a folded check of the chunk failed: per-proof verdicts through the culprit search, from the same staging
         if (pack) {                               // ... whose records, field counts and `precheck` were made on the GPU (the chunk's job is complete: harvest waited for it)
             uint8_t *hb_ = (uint8_t *)ch.slot->host.p; const uint8_t *db_ = ch.slot->dev.as<uint8_t>();
             HIPC(hipSetDevice(c->device));
@@ -644,8 +928,8 @@ int run_device_shape(Device &D, const CallIn &in, const std::vector<size_t> &idx
         if (rc) return rc;
         for (size_t b = 0; b < ch.n; ++b) verdicts[idx[ch.lo + b]] = (v[b] && ch.hb[b].parsed && ch.hb[b].shape) ? 1 : 0;
         return MINA_OK;
-    };
-    auto harvest = [&](Chunk &ch) {
+    }
+    void harvest(Chunk &ch) {
         if (ch.harvested) return;
         ch.harvested = true;
         if (ch.issued) {
@@ -664,305 +948,63 @@ int run_device_shape(Device &D, const CallIn &in, const std::vector<size_t> &idx
             (void)hipSetDevice(c->device);
             (void)hipDeviceSynchronize();
         }
-        if (ch.slot_ix >= 0) release(ch.slot_ix);
+        if (ch.slot_ix >= 0) D.release(ch.slot_ix);
         if (ch.counted) D.inflight.fetch_sub(1);
-    };
-
-    // D.mu, taken with the tables of this call's (domain, npub) prepared.  A re-prepare (another index since the last call) frees and rewrites the Lagrange tables --
-    // buffers a culprit search on the view context D.sc may be reading through its aliases, holding search_mu only (ADVICE r05, medium: round 5 re-prepared under
-    // D.mu alone).  So the re-prepare takes search_mu as well, FIRST (lock order g_mu, search_mu, mu: the installers', the fallback's); the common path -- already
-    // prepared -- never touches search_mu and never waits for a search.
-    const uint32_t prep_key = ((sh.k ? sh.k : 15u) << 16) | (sh.statements ? 40u : 0u);          // the Lagrange table belongs to (domain, npub): another index -> prepare again
-    auto lock_prepared = [&](std::unique_lock<std::mutex> &lk) -> int {
-        for (;;) {
-            lk = std::unique_lock<std::mutex>(D.mu);
-            if (D.prepared_npub == prep_key) return MINA_OK;
-            lk.unlock();
-            std::lock_guard<std::mutex> sl(D.search_mu);
-            std::lock_guard<std::mutex> dl(D.mu);
-            if (D.prepared_npub == prep_key) continue;
-            HIPC(hipSetDevice(c->device));
-            int rc = mina_state_jobs_prepare(c, sh.k ? sh.k : 15, sh.statements ? 40 : 0);
-            if (rc) return rc;
-            D.prepared_npub = prep_key;
-        }
-    };
-    // device side of a chunk's slot, before anything is queued on it (idempotent).  Caller holds D.mu through lock_prepared.
-    auto setup_slot = [&](Chunk &ch) -> int {
-        HIPC(hipSetDevice(c->device));
-        int rc;
-        if (D.prepared_npub != prep_key) return fail(MINA_ERR_STATE, "slot set up without the prepared tables");
-        Slot &S = *ch.slot;
-        if ((rc = S.dev.ensure(lay.total + Layout::out_bytes(lay.cap)))) return rc;
-        if (!S.ev) HIPC(hipEventCreateWithFlags(&S.ev, hipEventDisableTiming));
-        if (!S.ev_up) HIPC(hipEventCreateWithFlags(&S.ev_up, hipEventDisableTiming));
-        if (!S.up) HIPC(hipStreamCreateWithFlags(&S.up, hipStreamNonBlocking));
-        Lane &L = c->lanes[ch.slot_ix];
-        if (!L.stream) HIPC(hipStreamCreateWithFlags(&L.stream, hipStreamNonBlocking));
-        if (g_timing) for (auto &e : S.tev) if (!e) HIPC(hipEventCreate(&e));
-        return MINA_OK;
-    };
-    // the lanes of a chunk's job, decided once per chunk.  Caller holds D.mu.
-    auto setup_legs = [&](Chunk &ch) -> int {
-        if (ch.legs_set) return MINA_OK;
-        ch.legs_set = true;
-        // few chunks in flight: the three legs of a job (state hashes / wrap proof / accumulator) go to three streams
-        // (up to 4 chunks in flight -- 32 768 proofs per call 186 -> 152 ms, three callers of 8192: 138 -> 158 k proofs/s; with 8 the streams outnumber the hardware queues: 322 -> 360 ms)
-        if (D.inflight.load() > tu.split_max) return MINA_OK;
-        Lane *LI = &c->lanes[MB_PIPE_LANES + 3 * ch.slot_ix], *LA = &c->lanes[MB_PIPE_LANES + 3 * ch.slot_ix + 1], *LS = &c->lanes[MB_PIPE_LANES + 3 * ch.slot_ix + 2];
-        // Alone on the GPU a job is a latency-bound chain of small kernels (~390 waves each, one behind the other) beside 20 ms of chip-filling
-        // hashes; where their waves share a SIMD both run at half speed, and the call waits for the chain (rocprofv3 timeline: the statement
-        // digests 10.7 ms beside the hashes against 4.1 ms alone).  So the chain's stream and the hashes' stream get DISJOINT CU masks: the chain
-        // `chain_cus` CUs -- 128 = a SIMD per wave; fewer and a kernel lasts as long as its doubled-up SIMDs: 96 CUs cost +16 ms -- the hashes the
-        // rest (bit i of a mask = CU i / 8 of XCD i % 8, tools/probes/cumask_probe.hip).  8192 proofs per call: 62.6 -> 57.7 ms.
-        const uint32_t chain_cus = tu.chain_cus;
-        int ncu = 0; (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device);
-        if (chain_cus > 0 && chain_cus < (uint32_t)ncu && ncu <= 256) {
-            const uint32_t period = std::max(1u, tu.cu_period);
-            auto masked = [&](Lane &ln, bool chain) -> int {
-                if (ln.stream) return MINA_OK;
-                uint32_t mk[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-                for (uint32_t b2 = 0; b2 < (uint32_t)ncu; ++b2) { const bool in_chain = (b2 % period) < chain_cus * period / 256; if (in_chain == chain) mk[b2 >> 5] |= 1u << (b2 & 31); }
-                if (hipExtStreamCreateWithCUMask(&ln.stream, 8, mk) != hipSuccess) {       // a runtime without CU masks: plain streams, the legs share the CUs
-                    (void)hipGetLastError(); ln.stream = nullptr;
-                    HIPC(hipStreamCreateWithFlags(&ln.stream, hipStreamNonBlocking));
-                }
-                return MINA_OK;
-            };
-            int rc;
-            if ((rc = masked(*LI, true)) || (rc = masked(*LS, false))) return rc;
-            // the accumulator leg (fold GEMM + one MSM: chip-filling kernels, done within ~8 ms) shares the chain's CUs: the hashes are the later leg of a lone
-            // job, and unmasked this leg slowed their first pieces (8192 per call: 45.4 -> 44.5 ms; mina_verify_tuning.acc_mask = 0 chain | 1 hash | 2 none)
-            if (tu.acc_mask == 0) { if ((rc = masked(*LA, true))) return rc; } else if (tu.acc_mask == 1) { if ((rc = masked(*LA, false))) return rc; }
-        } else LS = nullptr;
-        ch.LI = LI; ch.LA = LA; ch.LS = LS;
-        return MINA_OK;
-    };
-    const bool own_up = tu.up_stream != 0;
-    auto lane_forms = [&]() {       // the lane forms of the sponge kernels follow the work in flight on the device (ctx.h use_coop*)
-        c->nlanes = (int)std::max(1u, std::min<unsigned>(D.inflight.load(), NSLOT));
-    };
-    const HashLaunch hash_launch{tu.hash_piece_waves, 0};      // a chunk's state hashes go out in pieces, early ones and the rest alike
-    auto chunk_plan = [&](Chunk &ch, uint32_t phase, uint32_t *d_stmt_out) {
-        StateJobPlan p; p.wrap = ch.LI; p.acc = ch.LA; p.states = ch.LS; p.phase = phase; p.carry = &ch.carry; p.d_stmt_out = d_stmt_out;
-        p.hashed_early = ch.hashed; p.hash = hash_launch;
-        return p;
-    };
-
-    // A chunk goes to the GPU in three steps, each as soon as its input is parsed (8192 full-size proofs per call: the job's wrap-proof chain
-    // takes ~42 ms on its CUs and the state hashes ~43 ms on theirs, so the call is as long as the later of the two STARTS):
-    //   issue_legs      after the wrap-proof halves (pool job A, ~1/3 of the parsing): patch, draw the randomisers, upload everything but the records,
-    //                   queue the accumulator and wrap-proof legs
-    //   stream_records  run by run of pool job B: upload the run's protocol-state records (34 KB of an entry's 47 KB) and queue their hashes
-    //   finish          upload `precheck`, queue the rest of the state leg, the joins and the verdict kernel, the download
-    auto issue_legs = [&](Chunk &ch) -> int {
-        uint8_t *hbase = (uint8_t *)ch.slot->host.p;
-        // host side of the chunk: collect the other shapes, patch what cannot go to the GPU as it is
-        size_t donor = SIZE_MAX;
-        for (size_t b = 0; b < ch.n; ++b) { if (ch.hb[b].proof_ok && ch.hb[b].shape && donor == SIZE_MAX) donor = b; if (ch.hb[b].deferred) deferred.push_back(idx[ch.lo + b]); }
-        if (donor == SIZE_MAX) { ch.skipped = true; return MINA_OK; }                         // nothing of this chunk can pass
-        for (size_t b = 0; b < ch.n; ++b) if (!(ch.hb[b].proof_ok && ch.hb[b].shape)) copy_proof_half(lay, hbase, b, donor);
-        if (!ch.randomised) return fail(MINA_ERR_STATE, "no entropy for the folding randomisers");
-        std::unique_lock<std::mutex> lk;
-        int rc;
-        if ((rc = lock_prepared(lk)) || (rc = setup_slot(ch)) || (rc = setup_legs(ch))) return rc;
-        Slot &S = *ch.slot;
-        Lane &L = c->lanes[ch.slot_ix];
-        lane_forms();
-        c->L = &L;
-        uint8_t *dbase = S.dev.as<uint8_t>();
-        hipStream_t up = own_up ? S.up : L.stream;
-        if (g_timing && !ch.queued) HIPC(hipEventRecord(S.tev[0], up));
-        ch.queued = true;
-        // everything behind the records and their field counts, EXCEPT `precheck`: the pool is still writing those bytes (parse_states_half) -- finish() sends them.
-        // (Until round 5 the one copy ran over them too and finish() re-sent them: harmless, since only the FINISH phase reads `precheck`, but a read of memory
-        // another thread is writing -- the one report of the ThreadSanitizer tier, tests/fuzz/tsan_boundary.cpp.)
-        HIPC(hipMemcpyAsync(dbase + lay.off[S_EXP], hbase + lay.off[S_EXP], lay.off[S_PRE] - lay.off[S_EXP], hipMemcpyHostToDevice, up));
-        HIPC(hipMemcpyAsync(dbase + lay.off[S_APRE], hbase + lay.off[S_APRE], lay.total - lay.off[S_APRE], hipMemcpyHostToDevice, up));
-        if (own_up) { HIPC(hipEventRecord(S.ev_up, up)); HIPC(hipStreamWaitEvent(L.stream, S.ev_up, 0)); }
-        JobStructs js; make_jobs(sh, lay, dbase, ch.n, true, true, true, js);
-        uint32_t *dv = (uint32_t *)(dbase + lay.out_off()), *df = dv + ch.n, *ds = df + 4;
-        rc = mb_state_jobs_on_lane(c, &js.j, dv, df, chunk_plan(ch, MB_JOB_LEGS, ds));
-        c->use_lane0();
-        return rc;
-    };
-    auto stream_records = [&](Chunk &ch, size_t r_lo, size_t r_hi) -> int {
-        uint8_t *hbase = (uint8_t *)ch.slot->host.p;
-        Slot &S = *ch.slot;
-        for (size_t r = r_lo; r < r_hi && r < ch.nsub; ++r) {
-            { std::unique_lock<std::mutex> lk(ch.mu); ch.cv.wait(lk, [&] { return ch.sub_left[r].load() == 0; }); }
-            const size_t lo = r * ch.sub, hi = std::min(ch.n, lo + ch.sub);
-            for (size_t b = lo; b < hi; ++b) if (!ch.hb[b].parsed) clear_states_half(lay, hbase, b);      // malformed (or of another shape / to be patched): defined records, verdict 0 through `precheck`
-            std::unique_lock<std::mutex> lk;
-            { int src; if ((src = lock_prepared(lk)) || (src = setup_slot(ch)) || (src = setup_legs(ch))) return src; }
-            Lane &L = c->lanes[ch.slot_ix];
-            if (g_timing && !ch.queued) HIPC(hipEventRecord(S.tev[0], own_up ? S.up : L.stream));
-            ch.queued = true;
-            uint8_t *dbase = S.dev.as<uint8_t>();
-            if (S.rec_ev.size() < ch.nsub) S.rec_ev.resize(ch.nsub, nullptr);
-            if (!S.rec_ev[r]) HIPC(hipEventCreateWithFlags(&S.rec_ev[r], hipEventDisableTiming));
-            hipStream_t up = own_up ? S.up : L.stream;
-            HIPC(hipMemcpyAsync(lay.at(dbase, S_REC, lo), lay.at(hbase, S_REC, lo), (hi - lo) * lay.stride[S_REC], hipMemcpyHostToDevice, up));
-            HIPC(hipMemcpyAsync(lay.at(dbase, S_NF, lo), lay.at(hbase, S_NF, lo), (hi - lo) * lay.stride[S_NF], hipMemcpyHostToDevice, up));
-            HIPC(hipEventRecord(S.rec_ev[r], up));
-            lane_forms();
-            // hashes in WHOLE pieces (a piece = `hash_piece_waves` waves of the form that runs -- 21 states each in the 3-lane form, 64 in the single-lane one (ctx.h
-            // hash_piece_states) -- = two waves on every SIMD of the state leg's 128 CUs): a run of
-            // 1024 entries is 829 waves -- launched run by run, a fifth of the leg's SIMDs would hold one wave where the others hold two, for as long
-            // The odd piece goes FIRST: it is complete after fewer runs, so the leg starts earlier, and it ends with a full piece instead of a half-empty one.
-            const size_t total = ch.n * MINA_STATES_PER_PROOF, piece = hash_piece_states(c, total, hash_launch.piece_waves), ready = hi * MINA_STATES_PER_PROOF;
-            const size_t first = piece ? (total % piece ? total % piece : piece) : 0;
-            const size_t upto = (r + 1 == ch.nsub || !piece) ? ready : (ready < first ? 0 : first + (ready - first) / piece * piece);
-            int rc = MINA_OK;
-            if (upto > ch.hashed && !(flags & MINA_VERIFY_DEDUP_STATES))      // deduplicated: the whole state leg runs in finish() (a piece cannot know its duplicates in later pieces)
-                rc = mb_state_hashes_early(c, ch.LS ? ch.LS : &L, ch.n * MINA_STATES_PER_PROOF, ch.hashed, upto - ch.hashed,
-                                           (const uint32_t *)lay.at(dbase, S_REC, 0), (const uint32_t *)lay.at(dbase, S_NF, 0), S.rec_ev[r], hash_launch);
-            c->use_lane0();
-            if (rc) return rc;
-            if (!(flags & MINA_VERIFY_DEDUP_STATES)) ch.hashed = std::max(ch.hashed, upto);
-        }
-        return MINA_OK;
-    };
-    auto finish = [&](Chunk &ch) -> int {
-        uint8_t *hbase = (uint8_t *)ch.slot->host.p;
-        std::lock_guard<std::mutex> lk(D.mu);
-        HIPC(hipSetDevice(c->device));
-        Slot &S = *ch.slot;
-        Lane &L = c->lanes[ch.slot_ix];
-        lane_forms();
-        c->L = &L;
-        uint8_t *dbase = S.dev.as<uint8_t>();
-        hipStream_t up = own_up ? S.up : L.stream;
-        if (pack) { int prc; if ((prc = S.pk_dev.ensure(ch.pk.total))) return prc; HIPC(hipMemcpyAsync(S.pk_dev.p, S.pk_host.p, ch.pk.total, hipMemcpyHostToDevice, up)); }
-        else HIPC(hipMemcpyAsync(lay.at(dbase, S_PRE, 0), lay.at(hbase, S_PRE, 0), ch.n * lay.stride[S_PRE], hipMemcpyHostToDevice, up));
-        if (g_timing) HIPC(hipEventRecord(S.tev[1], up));
-        if (own_up) { HIPC(hipEventRecord(S.ev_up, up)); HIPC(hipStreamWaitEvent(L.stream, S.ev_up, 0)); }
-        if (pack) {       // records, field counts and `precheck` of the chunk, on its lane ahead of the state leg (which forks from this lane)
-            uint8_t *pd = S.pk_dev.as<uint8_t>();
-            int prc = c->state_frontend(c, ch.n, ch.pk.bytes(pd), ch.pk.total - ch.pk.blob, ch.pk.begin(pd), ch.pk.end(pd), lay.at(dbase, S_EXP, 0), ch.pk.ledger(pd), ch.pk.band(pd),
-                                        lay.at(dbase, S_REC, 0), lay.at(dbase, S_NF, 0), lay.at(dbase, S_PRE, 0), nullptr);
-            if (prc) { c->use_lane0(); return prc; }
-        }
-        JobStructs js; make_jobs(sh, lay, dbase, ch.n, true, true, true, js);
-        uint32_t *dv = (uint32_t *)(dbase + lay.out_off()), *df = dv + ch.n, *ds = df + 4;
-        { const bool want = (flags & MINA_VERIFY_DEDUP_STATES) != 0; int drc; if (want != c->state_dedup && (drc = mb_ctx_state_dedup(c, want))) return drc; }      // MINA_VERIFY_DEDUP_STATES: per chunk, under the device's lock
-        int rc = mb_state_jobs_on_lane(c, &js.j, dv, df, chunk_plan(ch, MB_JOB_FINISH, ds));
-        c->use_lane0();
-        if (rc) return rc;
-        if (g_timing) HIPC(hipEventRecord(S.tev[2], L.stream));
-        if (own_up) { const uint32_t words = (uint32_t)(Layout::out_bytes(ch.n) / 4); launch_words_out(L.stream, words, dv, (uint32_t *)S.out.p); HIPC(hipGetLastError()); }
-        else HIPC(hipMemcpyAsync(S.out.p, dv, Layout::out_bytes(ch.n), hipMemcpyDeviceToHost, L.stream));
-        HIPC(hipEventRecord(S.ev, L.stream));
-        ch.issued = true;
-        return MINA_OK;
-    };
-
-    // MINA_VERIFY_PACK_ON_DEVICE, once the wrap-proof halves of a chunk are parsed (they say where an entry's states begin): lay out the front end's inputs and let
-    // the pool copy every entry's state bytes and ledger hashes into them -- a copy, no byte of a state is looked at.  An entry whose first half did not parse
-    // gets an empty range: FORMAT fails on the device, its records are zero and its `precheck` 0, as clear_states_half leaves them on the host path.
-    auto gather_states = [&](Chunk &ch) -> int {
-        size_t total = 0;
-        std::vector<uint64_t> at(ch.n + 1, 0);
-        for (size_t b = 0; b < ch.n; ++b) {
-            HostBits &hb = ch.hb[b]; const size_t q = idx[ch.lo + b];
-            hb.parsed = hb.proof_ok;                                  // the rest of FORMAT is the device's: it reaches the verdict through `precheck`
-            at[b] = total; if (hb.proof_ok) total += in.proof_lens[q] - hb.states_at;
-        }
-        at[ch.n] = total;
-        ch.pk.build(ch.n, total);
-        if (ch.slot->pk_host.ensure(ch.pk.total)) return MINA_ERR_HIP;
-        uint8_t *ph = (uint8_t *)ch.slot->pk_host.p;
-        uint64_t *pb = ch.pk.begin(ph), *pe = ch.pk.end(ph);
-        for (size_t b = 0; b < ch.n; ++b) { pb[b] = at[b]; pe[b] = ch.hb[b].proof_ok ? at[b + 1] : at[b]; }
-        memset(ph + 529 * ch.n, 0, ch.pk.blob - 529 * ch.n);
-        Chunk *chp = &ch;
-        ch.jobB = mb_pool_submit(ch.n, [&, chp, ph](size_t b) {
-            const HostBits &hb = chp->hb[b]; const size_t q = idx[chp->lo + b];
-            const uint64_t lo = chp->pk.begin(ph)[b], hi = chp->pk.end(ph)[b];
-            chp->pk.band(ph)[b] = (hb.proof_ok && hb.shape) ? 1 : 0;
-            if (hb.proof_ok) { memcpy(chp->pk.ledger(ph) + 512 * b, in.pubs[q] + 545, 512); memcpy(chp->pk.bytes(ph) + lo, in.proofs[q] + hb.states_at, hi - lo); }      // (proof_ok: the public input has its 1057 bytes)
-            else memset(chp->pk.ledger(ph) + 512 * b, 0, 512);
-        });
-        return MINA_OK;
-    };
-
-    size_t next_submit = 0, next_issue = 0, oldest = 0;
-    auto t_issued = t_call;
-    while (next_issue < nchunks && !rc_all) {
-        while (next_submit < nchunks && next_submit < oldest + window + ahead) {        // parsing runs `ahead` chunks ahead of the window
-            const int s = try_acquire();
-            if (s < 0) break;
-            Chunk &ch = chunks[next_submit];
-            ch.slot = &D.slots[s]; ch.slot_ix = s;
-            if (ch.slot->host.ensure(lay.total) || ch.slot->out.ensure(Layout::out_bytes(lay.cap))) { release(s); ch.slot = nullptr; ch.slot_ix = -1; rc_all = MINA_ERR_HIP; break; }
-            uint8_t *hbase = (uint8_t *)ch.slot->host.p;
-            Chunk *chp = &ch;
-            ch.sub = (early_sub && ch.n >= early_min && !pack) ? early_sub : ch.n; ch.nsub = (ch.n + ch.sub - 1) / ch.sub;
-            ch.sub_left.reset(new std::atomic<uint32_t>[ch.nsub]);
-            for (size_t r = 0; r < ch.nsub; ++r) ch.sub_left[r].store((uint32_t)(std::min(ch.n, (r + 1) * ch.sub) - r * ch.sub));
-            // the pool's order per chunk: the FIRST run whole (both halves: the state leg is the later one of a lone job, its first piece of hashes needs
-            // ~600 entries), then the wrap-proof halves of the rest (A), then their protocol states (B)
-            // (from ~6000 entries: below, the wrap-proof chain is the later leg and must not wait -- 4096 per call: 34.6 ms without, 35.4 with; 8192: 45.8 / 44.4)
-            const size_t head = (ch.nsub > 1 && ch.n >= head_min) ? ch.sub : 0;
-            ch.head = head;
-            auto run_done = [chp](size_t b) { if (chp->sub_left[b / chp->sub].fetch_sub(1) == 1) { std::lock_guard<std::mutex> lk(chp->mu); chp->cv.notify_all(); } };
-            ch.jobH = mb_pool_submit(head, [&, chp, hbase, run_done](size_t b) {
-                const size_t q = idx[chp->lo + b];
-                parse_proof_half(sh, lay, hbase, b, in.proofs[q], in.proof_lens[q], in.pubs[q], in.pub_lens[q], chp->hb[b], c);
-                parse_states_half(lay, hbase, b, in.proofs[q], in.proof_lens[q], in.pubs[q], in.pub_lens[q], chp->hb[b]);
-                run_done(b);
-            });
-            ch.jobA = mb_pool_submit(ch.n - head, [&, chp, hbase, head](size_t i) {
-                const size_t b = head + i, q = idx[chp->lo + b];
-                parse_proof_half(sh, lay, hbase, b, in.proofs[q], in.proof_lens[q], in.pubs[q], in.pub_lens[q], chp->hb[b], c);
-            });
-            ch.jobB = mb_pool_submit(pack ? 0 : ch.n - head, [&, chp, hbase, head, run_done](size_t i) {      // (packed on the device: gather_states below, once job A is through)
-                mb_pool_wait(chp->jobA);                                  // the pool hands jobs out in order, but the last items of A may still be running
-                const size_t b = head + i, q = idx[chp->lo + b];
-                parse_states_half(lay, hbase, b, in.proofs[q], in.proof_lens[q], in.pubs[q], in.pub_lens[q], chp->hb[b]);
-                run_done(b);
-            });
-            ++next_submit;
-        }
-        if (rc_all) break;
-        if (next_issue == next_submit) {                 // no slot for the next chunk: take back the oldest of this call, or wait for another caller's
-            if (oldest < next_issue) { harvest(chunks[oldest++]); continue; }
-            std::unique_lock<std::mutex> lk(D.slot_mu);
-            D.slot_cv.wait_for(lk, std::chrono::milliseconds(2));
-            continue;
-        }
-        if (next_issue - oldest >= window) { harvest(chunks[oldest++]); continue; }
-        if (pace_ms > 0 && nchunks > window && next_issue > 0 && next_issue < window) {      // fill the window one job period apart (see `pace_ms`)
-            const double wait = pace_ms - ms_since(t_issued);
-            if (wait > 0) std::this_thread::sleep_for(std::chrono::duration<double, std::milli>(wait));
-        }
-        t_issued = std::chrono::steady_clock::now();
-        Chunk &ch = chunks[next_issue];
-        ch.counted = true; D.inflight.fetch_add(1);
-        // the folding randomisers of the chunk's job (262 KB from the OS for 8192 proofs: ~0.5 ms), while the pool parses: the proofs are the caller's
-        // bytes, fixed since the call was made, and the values never leave the process
-        ch.randomised = draw_randomisers(sh, lay, (uint8_t *)ch.slot->host.p, ch.n);
-        int rc = ch.head ? stream_records(ch, 0, 1) : MINA_OK;          // the first run's records and hashes, ahead of everything else
-        mb_pool_wait(ch.jobH); mb_pool_wait(ch.jobA);
-        const double t_a = g_timing ? ms_since(t_call) : 0;
-        if (!rc && pack) rc = gather_states(ch);
-        if (!rc) rc = issue_legs(ch);
-        const double t_legs = g_timing ? ms_since(t_call) : 0;
-        if (!rc && !ch.skipped && !pack) rc = stream_records(ch, ch.head ? 1 : 0, ch.nsub);
-        mb_pool_wait(ch.jobB);
-        const double t_parsed = g_timing ? ms_since(t_call) : 0;
-        if (!rc && !ch.skipped) rc = finish(ch);
-        if (g_timing) fprintf(stderr, "mina_verify:   chunk %zu (%zu proofs): wrap proofs parsed at %.2f ms, legs queued at %.2f, states parsed at %.2f, all queued at %.2f ms\n", next_issue, ch.n, t_a, t_legs, t_parsed, ms_since(t_call));
-        if (rc && !rc_all) rc_all = rc;
-        ++next_issue;
     }
-    for (size_t q = 0; q < next_submit; ++q) { mb_pool_wait(chunks[q].jobH); mb_pool_wait(chunks[q].jobA); mb_pool_wait(chunks[q].jobB); }     // nothing may still write into a slot (error paths)
-    for (size_t q = 0; q < nchunks; ++q) {
-        if (q < next_submit) { harvest(chunks[q]); if (g_timing) fprintf(stderr, "mina_verify:   chunk %zu harvested at %.2f ms\n", q, ms_since(t_call)); }
+
+    // ---------------------------------------------------------------------------------------------- driver
+    int run() {
+        deferred.clear();
+        for (size_t i = 0; i < m; ++i) verdicts[idx[i]] = 0;
+        if (m == 0) return MINA_OK;
+        const Config cf = read_config(D, flags, network);
+        if (!cf.usable) return MINA_OK;
+        if (!cf.kimchi && !(flags & MINA_VERIFY_ALLOW_MISSING_KIMCHI)) return MINA_OK;          // the kimchi step cannot run: nothing can pass
+        sh = shape_of_config(cf);
+        if (sh.statements && !vote_shape(in, idx, sh)) return MINA_OK;                          // nothing parses
+        prep_key = ((sh.k ? sh.k : 15u) << 16) | (sh.statements ? 40u : 0u);          // the Lagrange table belongs to (domain, npub): another index -> prepare again
+        for (size_t q = 0; q < nchunks; ++q) { chunks[q].lo = m * q / nchunks; chunks[q].n = m * (q + 1) / nchunks - chunks[q].lo; chunks[q].hb.resize(chunks[q].n); }
+        lay.build(sh, (m + nchunks - 1) / nchunks);
+        // per turn ONE of: give the next chunks a slot and the pool their parsing; take the oldest chunk's verdicts back (no slot, or the window is full); queue the
+        // next chunk's three steps
+        size_t next_submit = 0, next_issue = 0, oldest = 0;
+        auto t_issued = t_call;
+        while (next_issue < nchunks && !rc_all) {
+            while (next_submit < nchunks && next_submit < oldest + window + ahead) {        // parsing runs `ahead` chunks ahead of the window
+                const int s = D.try_acquire(nslot);
+                if (s < 0) break;
+                Chunk &ch = chunks[next_submit];
+                ch.slot = &D.slots[s]; ch.slot_ix = s;
+                if (ch.slot->host.ensure(lay.total) || ch.slot->out.ensure(Layout::out_bytes(lay.cap))) { D.release(s); ch.slot = nullptr; ch.slot_ix = -1; rc_all = MINA_ERR_HIP; break; }
+                submit_parsing(ch);
+                ++next_submit;
+            }
+            if (rc_all) break;
+            if (next_issue == next_submit) {                 // no slot for the next chunk: take back the oldest of this call, or wait for another caller's
+                if (oldest < next_issue) { harvest(chunks[oldest++]); continue; }
+                std::unique_lock<std::mutex> lk(D.slot_mu);
+                D.slot_cv.wait_for(lk, std::chrono::milliseconds(2));
+                continue;
+            }
+            if (next_issue - oldest >= window) { harvest(chunks[oldest++]); continue; }
+            if (pace_ms > 0 && nchunks > window && next_issue > 0 && next_issue < window) {      // fill the window one job period apart (see `pace_ms`)
+                const double wait = pace_ms - ms_since(t_issued);
+                if (wait > 0) std::this_thread::sleep_for(std::chrono::duration<double, std::milli>(wait));
+            }
+            t_issued = std::chrono::steady_clock::now();
+            const int rc = queue_chunk(chunks[next_issue], next_issue);
+            if (rc && !rc_all) rc_all = rc;
+            ++next_issue;
+        }
+        for (size_t q = 0; q < next_submit; ++q) { mb_pool_wait(chunks[q].jobH); mb_pool_wait(chunks[q].jobA); mb_pool_wait(chunks[q].jobB); }     // nothing may still write into a slot (error paths)
+        for (size_t q = 0; q < next_submit; ++q) { harvest(chunks[q]); if (g_timing) fprintf(stderr, "mina_verify:   chunk %zu harvested at %.2f ms\n", q, ms_since(t_call)); }
+        if (g_timing) fprintf(stderr, "mina_verify: device %d: %zu proofs in %zu chunk(s), %.2f ms\n", D.ordinal, m, nchunks, ms_since(t_call));
+        if (rc_all) { for (size_t i = 0; i < m; ++i) verdicts[idx[i]] = 0; deferred.clear(); return rc_all; }
+        return MINA_OK;
     }
-    if (g_timing) fprintf(stderr, "mina_verify: device %d: %zu proofs in %zu chunk(s), %.2f ms\n", D.ordinal, m, nchunks, ms_since(t_call));
-    if (rc_all) { for (size_t i = 0; i < m; ++i) verdicts[idx[i]] = 0; deferred.clear(); return rc_all; }
-    return MINA_OK;
+};
+int run_device_shape(Device &D, const CallIn &in, const std::vector<size_t> &idx, uint8_t *verdicts, const CallEnv &env, std::vector<size_t> &deferred) {
+    return ShapePass(D, in, idx, verdicts, env, deferred).run();
 }
 
 // verdict bytes of the proofs idx[0..m) of the call on device D: one pass per evaluation / recursion shape among them (Mina's blockchain proofs share
@@ -1013,7 +1055,7 @@ int state_checks(const uint8_t *proof, size_t proof_len, const uint8_t *pub, siz
     Device *D; uint32_t flags; int network;
     { std::lock_guard<std::mutex> lk(g_mu); auto &ds = devices(); if (ds.empty()) return MINA_ERR_HIP; D = ds[0]; flags = g_flags; network = g_network; }
     const Config cf = read_config(*D, flags | MINA_VERIFY_ALLOW_SURROGATE, network);
-    Shape sh; sh.kimchi = cf.kimchi; sh.statements = cf.kimchi && cf.statements; sh.k = cf.k; sh.network = cf.network; sh.feature_aware = cf.feature_aware;
+    Shape sh = shape_of_config(cf);
     uint32_t passed = 0, ran = MINA_CHECK_FORMAT;
     *passed_out = 0; *ran_out = ran;
     if (sh.statements) {

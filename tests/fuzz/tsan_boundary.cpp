@@ -32,6 +32,7 @@
 
 // ------------------------------------------------------------------------------------------------ the stub device layer
 static std::atomic<long> g_jobs{0}, g_searches{0}, g_account_jobs{0}, g_installs{0};
+static int sid(const Lane *l) { return l ? mb_stub_id(l->stream) : 0; }      // a lane by its stream's name in the call trace (hip_stub: -DMB_STUB_TRACE)
 static bool marked_bad(const void *ft_eval1, size_t b) { return ft_eval1 && memcmp((const uint8_t *)ft_eval1 + 32 * b, "BAD!", 4) == 0; }
 
 extern "C" int mina_ctx_create(int device_id, mina_ctx **out) {
@@ -39,13 +40,13 @@ extern "C" int mina_ctx_create(int device_id, mina_ctx **out) {
     for (int i = 0; i < 4; ++i) (void)hipStreamCreateWithFlags(&c->lanes[i].stream, hipStreamNonBlocking);
     c->use_lane0(); *out = c; return MINA_OK;
 }
-int mb_ctx_create_view(mina_ctx *parent, mina_ctx **out) { int rc = mina_ctx_create(parent->device, out); if (!rc) mb_ctx_refresh_view(*out, parent); return rc; }
+int mb_ctx_create_view(mina_ctx *parent, mina_ctx **out) { int rc = mina_ctx_create(parent->device, out); if (!rc) { (*out)->is_view = true; mb_ctx_refresh_view(*out, parent); } return rc; }
 void mb_ctx_refresh_view(mina_ctx *v, mina_ctx *p) { v->have_kimchi = p->have_kimchi; v->kimchi_log2 = p->kimchi_log2; v->have_state_salts = p->have_state_salts; }   // (read under the parent's lock by the caller)
 extern "C" void mina_ctx_destroy(mina_ctx *c) { if (!c) return; for (auto &l : c->lanes) { if (l.stream) (void)hipStreamDestroy(l.stream); l.release_all(); } delete c; }
 extern "C" int mina_poseidon_set_params(mina_ctx *c, int field, const uint8_t *) { c->have_pparams[field] = true; c->pparams_surrogate[field] = false; return MINA_OK; }
 extern "C" int mina_srs_create(mina_ctx *c, int curve, uint32_t depth) { c->srs[curve].depth = depth; return MINA_OK; }
 int mb_poseidon_env_params(mina_ctx *) { return MINA_OK; }
-extern "C" int mina_state_jobs_prepare(mina_ctx *c, uint32_t, uint32_t) { c->have_state_salts = true; return MINA_OK; }
+extern "C" int mina_state_jobs_prepare(mina_ctx *c, uint32_t k, uint32_t npub) { MB_TRACE("mina_state_jobs_prepare k %u npub %u\n", k, npub); c->have_state_salts = true; return MINA_OK; }
 // the installed indexes: flags the installer thread flips under the boundary's own locks (mina_verify_install_* takes g_mu and every device's mu)
 extern "C" int mina_verifier_index_install(mina_ctx *c, const mina_verifier_index *ix) {
     c->have_kimchi = true; c->kimchi_log2 = ix->log2_domain; g_installs.fetch_add(1); return MINA_OK;
@@ -57,8 +58,9 @@ int mb_step_index_feature_aware(mina_ctx *) { return 0; }
 int mb_kimchi_available(mina_ctx *c) { return c->have_kimchi ? 1 : 0; }
 extern "C" int mina_merkle_verify_batch(mina_ctx *, int, size_t n, uint32_t, const uint8_t *, const uint8_t *, const uint8_t *, const uint8_t *, uint8_t *ok) { for (size_t i = 0; i < n; ++i) ok[i] = 1; return MINA_OK; }
 
-int mb_state_hashes_early(mina_ctx *c, Lane *LS, size_t ns_total, size_t lo, size_t cnt, const uint32_t *, const uint32_t *, hipEvent_t, HashLaunch) {
+int mb_state_hashes_early(mina_ctx *c, Lane *LS, size_t ns_total, size_t lo, size_t cnt, const uint32_t *, const uint32_t *, hipEvent_t after, HashLaunch hash) {
     if (!LS || lo + cnt > ns_total) return mb_fail(MINA_ERR_ARG, "bad early state range");
+    MB_TRACE("mb_state_hashes_early states [%zu, +%zu) of %zu on s%d after e%d, piece_waves %u, current lane s%d, nlanes %d\n", lo, cnt, ns_total, sid(LS), mb_stub_id(after), hash.piece_waves, sid(c->L), c->nlanes);
     Lane *const keep = c->L; c->L = LS; c->L = keep;       // (the real one hashes with LS as the current lane: a write to the context, under the device's lock)
     return MINA_OK;
 }
@@ -68,6 +70,7 @@ int mb_state_jobs_on_lane(mina_ctx *c, const mina_state_jobs *j, uint32_t *d_ver
     if (phase != MB_JOB_ALL && !carry) return mb_fail(MINA_ERR_ARG, "a split job needs a carry");
     const size_t B = j->batch;
     Lane &L = *c->L;
+    MB_TRACE("mb_state_jobs_on_lane phase %u batch %zu hashed_early %zu, wrap s%d acc s%d states s%d, current lane s%d, nlanes %d, dedup %d\n", phase, B, plan.hashed_early, sid(plan.wrap), sid(plan.acc), sid(plan.states), sid(&L), c->nlanes, (int)c->state_dedup);
     int rc;
     if ((rc = L.st_flags.ensure(16 * 4))) return rc;          // the lane's own scratch words, as in the real pipeline: two jobs on one lane at once would race HERE
     uint32_t *w = L.st_flags.as<uint32_t>();
@@ -89,7 +92,8 @@ int mb_state_jobs_on_lane(mina_ctx *c, const mina_state_jobs *j, uint32_t *d_ver
     return MINA_OK;
 }
 // the culprit search of a failed job (host-buffer form): every proof's own verdict
-extern "C" int mina_state_job_batch(mina_ctx *, const mina_state_jobs *j, uint8_t *verdicts) {
+extern "C" int mina_state_job_batch(mina_ctx *c, const mina_state_jobs *j, uint8_t *verdicts) {
+    MB_TRACE("mina_state_job_batch batch %zu on the %s, lanes s%d s%d s%d s%d, nlanes %d\n", (size_t)j->batch, c->is_view ? "view" : "context", sid(&c->lanes[0]), sid(&c->lanes[1]), sid(&c->lanes[2]), sid(&c->lanes[3]), c->nlanes);
     for (size_t b = 0; b < j->batch; ++b) {
         const uint8_t pre = j->precheck ? ((const uint8_t *)j->precheck)[b] : 1;
         verdicts[b] = (pre && !(j->with_ipa && j->kimchi && marked_bad(j->kimchi->ft_eval1, b))) ? 1 : 0;
@@ -133,12 +137,65 @@ static std::string unb64(const std::string &s) {
 }
 static std::string slurp(const char *path) { std::ifstream f(path, std::ios::binary); std::stringstream ss; ss << f.rdbuf(); return ss.str(); }
 
+// `trace` mode (built with -DMB_STUB_TRACE: `make trace`; tests/test_boundary_trace.py compares its stdout with tests/golden/boundary_call_trace.txt): ONE caller
+// on ONE logical device runs a fixed script of calls -- the shapes of test_boundary_pipeline_chunks_and_device_shards_give_the_same_verdicts -- while the stand-in
+// runtime and the stub device layer write down every call they get.  Every runtime call of a pass is made by the calling thread (the pool only parses), so the log
+// is the same run after run: it pins the ORDER of copies, events, waits and job phases per stream, which ThreadSanitizer does not look at.
+static int run_trace(const std::vector<std::string> &proofs, const std::vector<std::string> &pubs, const std::vector<std::string> &bad_proofs, const std::string &truncated) {
+    const std::string garbage("\x01\x02\x03", 3);
+    std::vector<const std::string *> pr, pu; std::vector<uint8_t> want;
+    for (size_t i = 0; i < 37; ++i) {          // good ones; a failing folded check at 0, 12, 13, 36; states cut short at 5, 25; three bytes of garbage at 30
+        const size_t k = i % proofs.size();
+        const bool bad = i == 0 || i == 12 || i == 13 || i == 36, cut = i == 5 || i == 25, junk = i == 30;
+        pr.push_back(junk ? &garbage : cut ? &truncated : bad ? &bad_proofs[k] : &proofs[k]); pu.push_back(&pubs[cut ? 0 : k]); want.push_back(!(bad || cut || junk));
+    }
+    int failed = 0;
+    auto call = [&](const char *what, const mina_verify_tuning *t, size_t lo, size_t hi, uint32_t more_flags = 0) {
+        MB_TRACE("# %s: proofs [%zu, %zu)\n", what, lo, hi);
+        mina_verify_configure_ex(t);
+        mina_verify_configure(MINA_VERIFY_ALLOW_SURROGATE | MINA_VERIFY_ALLOW_UNBOUND_STATEMENT | more_flags);
+        const size_t n = hi - lo;
+        std::vector<const uint8_t *> P(n), Q(n); std::vector<size_t> PL(n), QL(n); std::vector<uint8_t> got(n, 7);
+        for (size_t i = 0; i < n; ++i) { P[i] = (const uint8_t *)pr[lo + i]->data(); PL[i] = pr[lo + i]->size(); Q[i] = (const uint8_t *)pu[lo + i]->data(); QL[i] = pu[lo + i]->size(); }
+        const int rc = mina_verify_state_batch(n, P.data(), PL.data(), Q.data(), QL.data(), got.data());
+        if (rc != MINA_OK) { ++failed; fprintf(stderr, "%s: call failed: %s\n", what, mina_last_error()); return; }
+        for (size_t i = 0; i < n; ++i) if (got[i] != want[lo + i]) { ++failed; fprintf(stderr, "%s: proof %zu: verdict %d, expected %d\n", what, lo + i, got[i], want[lo + i]); }
+    };
+    auto tuned = [](auto set) { mina_verify_tuning t; mina_verify_tuning_default(&t); set(t); return t; };
+    mina_verify_tuning t;
+    call("one chunk, defaults", nullptr, 0, 37);
+    t = tuned([](mina_verify_tuning &t) { t.single_max = 1; t.chunk = 5; });                                   call("chunks of 5", &t, 0, 37);
+    t = tuned([](mina_verify_tuning &t) { t.single_max = 1; t.chunk = 2; });                                   call("chunks of 2: 19 chunks over 4 slots", &t, 0, 37);
+    t = tuned([](mina_verify_tuning &t) { t.early_min = 1; t.head_min = 0; t.early_sub = 3; });                call("streamed, runs of 3", &t, 0, 37); call("streamed to the end, runs of 3", &t, 14, 25);
+    t = tuned([](mina_verify_tuning &t) { t.early_min = 1; t.head_min = 0; t.early_sub = 2; t.single_max = 1; t.chunk = 5; }); call("streamed, runs of 2 in chunks of 5", &t, 0, 37);
+    t = tuned([](mina_verify_tuning &t) { t.early_min = 1; t.head_min = 0; t.early_sub = 1; });                call("streamed, runs of 1", &t, 0, 37);
+    t = tuned([](mina_verify_tuning &t) { t.early_min = 1; t.head_min = 0; t.early_sub = 0; });                call("streaming off", &t, 0, 37);
+    for (uint32_t wa : {0x0100u, 0x0302u, 0x1004u}) {
+        t = tuned([wa](mina_verify_tuning &t) { t.early_min = 1; t.head_min = 0; t.single_max = 1; t.chunk = 2; t.early_sub = 1; t.window = wa >> 8; t.ahead = wa & 0xff; t.slots = 16; });
+        call(wa == 0x0100u ? "window 1, 0 ahead, 16 slots" : wa == 0x0302u ? "window 3, 2 ahead, 16 slots" : "window 16, 4 ahead, 16 slots", &t, 0, 37);
+    }
+    t = tuned([](mina_verify_tuning &t) { t.up_stream = 0; t.single_max = 1; t.chunk = 5; t.early_min = 1; t.head_min = 0; t.early_sub = 2; }); call("no upload stream", &t, 0, 37);
+    t = tuned([](mina_verify_tuning &t) { t.search_ctx = 0; t.single_max = 1; t.chunk = 5; });                 call("culprit search on the device's one context", &t, 0, 37);
+    t = tuned([](mina_verify_tuning &t) { t.early_min = 1; t.head_min = 0; t.early_sub = 3; });                call("MINA_VERIFY_DEDUP_STATES, streamed", &t, 0, 37, MINA_VERIFY_DEDUP_STATES); call("... and off again", &t, 14, 25);
+    for (size_t i = 26; i < 30; ++i) { pr[i] = &garbage; want[i] = 0; }
+    t = tuned([](mina_verify_tuning &t) { t.single_max = 1; t.chunk = 2; });                                   call("chunks in which nothing parses", &t, 26, 32);
+    // with a step index the job's shape is voted over the call's proofs and the tables belong to another (domain, npub): prepared again
+    mina_step_index six; memset(&six, 0, sizeof six);
+    if (mina_verify_install_step_index(&six) != MINA_OK) { fprintf(stderr, "install: %s\n", mina_last_error()); return 2; }
+    t = tuned([](mina_verify_tuning &t) { t.single_max = 1; t.chunk = 5; });                                   call("step index installed: shape vote, tables prepared again", &t, 0, 37); call("... a call in which nothing parses", &t, 26, 30);
+    MB_TRACE("# mina_verify_shutdown\n");
+    mina_verify_configure_ex(nullptr);
+    mina_verify_shutdown();
+    fprintf(stderr, "trace: %ld device jobs, %ld culprit searches, %d failures\n", g_jobs.load(), g_searches.load(), failed);
+    return (failed || g_searches.load() == 0 || g_jobs.load() == 0) ? 1 : 0;
+}
 
 int main(int argc, char **argv) {
-    if (argc < 4) { fprintf(stderr, "usage: %s state_proofs_k15_bytes.json account_proofs_bytes.json seconds [state_callers account_callers bad_every]\n", argv[0]); return 2; }
+    if (argc < 4) { fprintf(stderr, "usage: %s state_proofs_k15_bytes.json account_proofs_bytes.json seconds|trace [state_callers account_callers bad_every]\n", argv[0]); return 2; }
+    const bool trace = !strcmp(argv[3], "trace");
     const double seconds = atof(argv[3]);
     const int n_state = argc > 4 ? atoi(argv[4]) : 6, n_acct = argc > 5 ? atoi(argv[5]) : 3, bad_every = argc > 6 ? atoi(argv[6]) : 5;
-    setenv("MINA_VERIFY_DEVICES", "0,0", 1);                        // two logical contexts: a large call is cut into shards, one pipeline per device
+    setenv("MINA_VERIFY_DEVICES", trace ? "0" : "0,0", 1);          // two logical contexts: a large call is cut into shards, one pipeline per device
     setenv("MINA_HOST_THREADS", "4", 1);
     const std::string st = slurp(argv[1]), ac = slurp(argv[2]);
     std::vector<std::string> proofs, pubs, aproofs, apubs;
@@ -165,6 +222,7 @@ int main(int argc, char **argv) {
     mina_verifier_index ix; memset(&ix, 0, sizeof ix);
     ix.log2_domain = 15; ix.zk_rows = 3;
     if (mina_verify_install_verifier_index(&ix) != MINA_OK) { fprintf(stderr, "install: %s\n", mina_last_error()); return 2; }
+    if (trace) return run_trace(proofs, pubs, bad_proofs, truncated);
 
     std::atomic<bool> stop{false}; std::atomic<long> wrong{0}, calls{0}, verdicts{0}, errors{0};
     auto state_caller = [&](int id) {
