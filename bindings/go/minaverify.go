@@ -67,6 +67,52 @@ func ConfigurePackOnDevice(otherFlags uint32) { C.mina_verify_configure(C.uint32
 // (mina_account_job_dev; bincode only); off by default, verdicts unchanged; other flags are kept by the caller.
 func ConfigureAccountOnDevice(otherFlags uint32) { C.mina_verify_configure(C.uint32_t(otherFlags) | C.MINA_VERIFY_ACCOUNT_ON_DEVICE) }
 
+// ConfigureGroupedSearch: a chunk of the process-wide boundary whose folded check failed is searched for its culprits in groups of 64, from its staging in HBM
+// (mina_ctx_set_search_groups, mina_state_job_each_dev); off by default, verdicts unchanged; other flags are kept by the caller.
+func ConfigureGroupedSearch(otherFlags uint32) { C.mina_verify_configure(C.uint32_t(otherFlags) | C.MINA_VERIFY_GROUPED_SEARCH) }
+
+// SetSearchGroups: the culprit search of the context's failed Proof-of-State jobs cuts a failing range into `groups` parts (2 .. 128) and checks all parts of a
+// round in one pass on the job's lane; 0 (the default) keeps the fan search.
+func (c *Ctx) SetSearchGroups(groups uint32) error {
+	if rc := C.mina_ctx_set_search_groups(c.p, C.uint32_t(groups)); rc != 0 {
+		return lastError()
+	}
+	return nil
+}
+
+// SearchStats: legs searched in groups, their rounds and the parts checked, since the context was created.
+func (c *Ctx) SearchStats() (searches, rounds, parts uint64, err error) {
+	var a, b, d C.uint64_t
+	if rc := C.mina_ctx_search_stats(c.p, &a, &b, &d); rc != 0 {
+		return 0, 0, 0, lastError()
+	}
+	return uint64(a), uint64(b), uint64(d), nil
+}
+
+// StateJobEachDev: per-proof verdicts (one uint32 each in dVerdicts) of a Proof-of-State job whose inputs are in HBM; waits for its lane.
+func (c *Ctx) StateJobEachDev(jobs *C.mina_state_jobs, dVerdicts, dFlags unsafe.Pointer) error {
+	if rc := C.mina_state_job_each_dev(c.p, jobs, dVerdicts, dFlags); rc != 0 {
+		return lastError()
+	}
+	return nil
+}
+
+// MsmSegmentsDev: nseg variable-base MSMs over ranges [begin[s], end[s]) of one point / scalar array in HBM, one 68-byte record each (device pointers).
+func (c *Ctx) MsmSegmentsDev(curve int, nTotal, nseg int, dBegin, dEnd, dBases, dScalars, dOut unsafe.Pointer) error {
+	if rc := C.mina_msm_segments_dev(c.p, C.int(curve), C.size_t(nTotal), C.size_t(nseg), dBegin, dEnd, dBases, dScalars, dOut); rc != 0 {
+		return lastError()
+	}
+	return nil
+}
+
+// BPolyFoldSegmentsDev: nseg weighted folds of challenge polynomials over ranges of one batch in HBM, 2^k scalars each (device pointers).
+func (c *Ctx) BPolyFoldSegmentsDev(field int, k uint32, batch, nseg int, dBegin, dEnd, dChals, dWeights, dOut unsafe.Pointer) error {
+	if rc := C.mina_b_poly_fold_segments_dev(c.p, C.int(field), C.uint32_t(k), C.size_t(batch), C.size_t(nseg), dBegin, dEnd, dChals, dWeights, dOut); rc != 0 {
+		return lastError()
+	}
+	return nil
+}
+
 // SelftestFe29: one routine of the 9 x 29-bit layer (op = C.MINA_FE29_*) on rows of 73 uint32 words, 37 words out per row.  Test-facing: the caller owns the
 // operand bounds, nothing is range-checked on the device.
 func (c *Ctx) SelftestFe29(field, op int, rows []uint32) ([]uint32, error) {

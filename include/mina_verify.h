@@ -546,6 +546,26 @@ int mina_state_job_fold_dev(mina_ctx *ctx, const mina_state_jobs *jobs, void *d_
  * re-checked concurrently (and failing parts cut again) so that every proof gets its own verdict byte; the opening check of well-formed
  * proofs is re-checked from the rows of the failed batch, without repeating the transcripts. */
 int mina_state_job_batch(mina_ctx *ctx, const mina_state_jobs *jobs, uint8_t *verdicts /* batch */);
+/* Per-proof verdicts for a job whose inputs are already in HBM: mina_state_job_batch without its staging copy (the two share one body).  `jobs` as for
+ * mina_state_job_batch_dev (device pointers).  Runs the job on the next pipeline lane (the pinned one under mina_ctx_pin_lane); if a folded check fails, runs the
+ * job's per-proof part again without the folded legs and searches the failed legs for their culprits (in groups or over the fan, as the context is set).  Writes
+ * d_verdicts[b] = 1 / 0 (u32 per proof) and, if d_flags is not NULL, the four words mina_state_job_batch_dev writes for the WHOLE job.  SYNCHRONISES ITS LANE: when
+ * it returns the verdicts are in d_verdicts.  Call mina_state_jobs_prepare first. */
+int mina_state_job_each_dev(mina_ctx *ctx, const mina_state_jobs *jobs, void *d_verdicts /* batch u32 */, void *d_flags /* 4 u32 or NULL */);
+/* The grouped culprit search (off by default).  groups = 0: the fan search above.  groups = G in 2 .. 128: each failed leg starts with failing = {[0, batch)};
+ * every round cuts every failing range [lo, lo + cnt) of more than one proof into g = min(G, cnt) parts [lo + cnt*q/g, lo + cnt*(q+1)/g), checks ALL parts of the
+ * round in one pass on the job's own lane (mina_b_poly_fold_segments_dev's fold, the fixed-base MSM with one problem per part, mina_msm_segments_dev's MSM, one
+ * comparison launch, one wait, one read-back of a flag per part) and keeps the parts that fail; a failing range of one proof is a culprit.  ceil(log_G batch) rounds
+ * instead of ceil(log_4 batch), no lane but the job's, no stream created.  A round is split into passes only beyond min(128, 2^28 / (2^k * 16)) parts.  The opening
+ * leg runs from the rows the failed batch left on its lane; where those cannot be used (malformed opening input, mina_verify_tuning.search_full, rows of another
+ * batch) that leg keeps the fan search.  A part of the accumulator leg that holds a malformed commitment fails.  Verdicts are those of the fan search for every
+ * input.  Measured: not on an MI355X yet -- tools/bench_search.py is the tool; the expected gain is derived from round depth and launch counts only.
+ * mina_ctx_search_stats: legs searched in groups, rounds (levels) and parts (segments checked) since the context was created; functions of (batch, G, culprits). */
+int mina_ctx_set_search_groups(mina_ctx *ctx, uint32_t groups);
+int mina_ctx_search_stats(mina_ctx *ctx, uint64_t *searches, uint64_t *rounds, uint64_t *parts);
+/* Test-facing: *live = the streams the context's lanes hold now, *made_by_searches = the streams its culprit searches have created since the context was created
+ * (the fan search creates the streams its lanes lack and destroys them when it is done; the grouped search creates none and queues on the job's lane only). */
+int mina_ctx_lane_streams(mina_ctx *ctx, uint32_t *live, uint64_t *made_by_searches);
 
 /* ---- multi-GPU building blocks --------------------------------------------------------------------
  * One process per GPU; RCCL moves bytes (all-to-all of scalar slices, all-gather of partial points), these entry points are the
@@ -561,6 +581,27 @@ int mina_msm_dev(mina_ctx *ctx, int curve, size_t n, const void *d_bases /* n*64
 /* sum of n point records (the all-gathered partial results) */
 int mina_points_sum_dev(mina_ctx *ctx, int curve, size_t n, const void *d_records /* n*68 */, void *d_out /* record */);
 int mina_point_records_equal_dev(mina_ctx *ctx, const void *d_a, const void *d_b, void *d_verdict /* u32 */);
+/* ---- segmented building blocks: many independent sums over ranges of ONE input array, in one launch set -------------
+ * Segment s covers entries [seg_begin[s], seg_end[s]) of the arrays (u32 tables in device memory, nseg words each).  Segments may be empty, of different
+ * lengths, overlapping or out of order; entries no segment names are ignored.  Both calls queue on the next pipeline lane (the pinned one under
+ * mina_ctx_pin_lane).  They read the two tables back first -- 8 * nseg bytes, one wait for what the lane already holds -- because the longest segment sizes
+ * the launches and a segment that breaks begin <= end <= limit is refused with MINA_ERR_ARG before any kernel is queued; they do not wait for their own
+ * kernels.  Null or misaligned pointers and shapes beyond the limits are refused before the device is touched.  Measured: nothing yet (no MI355X timing of
+ * either call is recorded); what the tests pin is that the bytes equal those of the single-range calls.
+ *
+ * mina_msm_segments_dev: d_out[s] = sum over i in segment s of scalars[i] * bases[i], a 68-byte point record each (an empty segment: is_infinity = 1), equal byte
+ * for byte to mina_msm_dev over that range alone.  The segments are the problems of one multi-problem bucket pipeline: every segment owns W bucket sets of NB
+ * buckets, chosen by the LONGEST segment L (W x NB = 32 x 128 for L < 2048, 20 x 4096 for L < 2^17, 18 x 16384 above), and the pipeline's limits are
+ * NB * W * nseg <= 2^26 and max(L, 1) * W * nseg <= 2^28; n_total <= 2^24.  Scalars are canonical (< 2^255).  d_bases and d_scalars: 16-byte aligned.
+ *
+ * mina_b_poly_fold_segments_dev: d_out[s][j] = sum over b in segment s of weights[b] * b_poly_coefficients(chals[b])[j], canonical, equal byte for byte to
+ * mina_b_poly_fold_dev over that range alone (both are exact sums modulo p, whichever kernels that call takes; an empty segment gives zeros).  d_weights may be
+ * null (every weight 1).  nseg <= 65535, nseg * 2^k <= 2^28; d_out 16-byte aligned. */
+int mina_msm_segments_dev(mina_ctx *ctx, int curve, size_t n_total, size_t nseg, const void *d_seg_begin, const void *d_seg_end /* nseg u32 each */,
+                          const void *d_bases /* n_total*64 canonical affine */, const void *d_scalars /* n_total*32 */, void *d_out /* nseg records */);
+int mina_b_poly_fold_segments_dev(mina_ctx *ctx, int field, uint32_t k, size_t batch, size_t nseg, const void *d_seg_begin,
+                                  const void *d_seg_end /* nseg u32 each, in proofs */, const void *d_chals /* batch*k*32 */,
+                                  const void *d_weights /* batch*32 */, void *d_out /* nseg * 2^k * 32 */);
 
 struct mina_pickles_statements;
 /* ---- kimchi verifier for the Pickles wrap proof (a11): `oracles` + `to_batch` on the GPU ---------------------------------
@@ -744,6 +785,11 @@ int mina_state_proof_split(const uint8_t *bytes, size_t len, size_t *proof_len, 
 #define MINA_VERIFY_ACCOUNT_ON_DEVICE 32u    /* mina_verify_account, _account_batch and _account_checks do not read a call's proofs on the host: the bytes are uploaded
                                                   as they are and mina_account_job_dev's job parses, cross-checks, hashes, folds and compares on the GPU.  Off by
                                                   default; verdicts and masks are unchanged.  A context without the device path or without Fp tables keeps the host path. */
+#define MINA_VERIFY_GROUPED_SEARCH 64u       /* when a folded check of a chunk fails, its culprits are searched in groups of 64 (mina_ctx_set_search_groups) from the
+                                                  chunk's staging in HBM, through mina_state_job_each_dev's body: no second upload of the chunk and, under
+                                                  MINA_VERIFY_PACK_ON_DEVICE, no download of the records and `precheck` the GPU made.  Off by default; verdicts and masks
+                                                  are unchanged.  Works together with the other flags.  The searches are counted on the device's context
+                                                  (mina_ctx_search_stats of mina_verify_device_ctx).  Not measured on an MI355X yet (tools/bench_search.py). */
 #include <stdbool.h>
 bool mina_verify_state(const uint8_t *proof, size_t proof_len, const uint8_t *pub_input, size_t pub_len);
 int mina_verify_state_batch(size_t n, const uint8_t *const *proofs, const size_t *proof_lens, const uint8_t *const *pub_inputs,

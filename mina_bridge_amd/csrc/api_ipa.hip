@@ -332,6 +332,34 @@ __global__ void xyzz_eq_affine_kernel(const xyzz_t *__restrict__ a, const uint32
     *verdict = eq ? 1u : 0u;
 }
 
+// the grouped culprit search: the accumulator commitments of a whole batch with ONE malformed word per proof (a part of the search fails iff it holds one)
+template <int F>
+__global__ void points_to_mont_checked_each_kernel(uint32_t n, const uint32_t *__restrict__ in_words, FieldK kb, affine_t *__restrict__ out, uint32_t *__restrict__ bad) { mb_wave_prio();
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    bool ok = true;
+    out[i] = load_point_checked<F>(in_words + (size_t)i * 16, kb, ok);
+    bad[i] = ok ? 0u : 1u;
+}
+// one block per part p: flags[p] = 1 iff  A[p] + sign * B[p] == identity  and no proof of [begin[p], end[p]) has its malformed word set (bad may be null)
+template <int F>
+__global__ void __launch_bounds__(64)
+xyzz_compare_parts_kernel(const xyzz_t *__restrict__ a, const xyzz_t *__restrict__ b, int negate_b, const uint32_t *__restrict__ begin, const uint32_t *__restrict__ end,
+                          const uint32_t *__restrict__ bad, uint32_t nbad, uint32_t *__restrict__ flags) { mb_wave_prio();
+    const uint32_t p = blockIdx.x;
+    int any = 0;
+    if (bad) { const uint32_t e = end[p] < nbad ? end[p] : nbad; for (uint32_t i = begin[p] + threadIdx.x; i < e; i += 64) any |= bad[i] != 0; }
+    any = __syncthreads_or(any);
+    if (threadIdx.x) return;
+    if (any) { flags[p] = 0u; return; }
+    xyzz_t A = a[p], B = b[p];
+    if (negate_b) B.y = fe_neg<F>(B.y);
+    bool ai = xyzz_is_inf(A), bi = xyzz_is_inf(B), eq;
+    if (ai || bi) eq = ai && bi;
+    else eq = fe_eq(fe_mul<F>(A.x, B.zz), fe_mul<F>(B.x, A.zz)) && fe_eq(fe_mul<F>(A.y, B.zzz), fe_mul<F>(B.y, A.zzz));
+    flags[p] = eq ? 1u : 0u;
+}
+
 }  // namespace mb
 
 // ------------------------------------------------------------------------------------------------
@@ -598,6 +626,92 @@ int mb_ipa_recheck_rows(mina_ctx *c, size_t lo, size_t cnt, uint32_t *d_verdict)
     if ((rc = mb_msm_fixed(c, curve, 1u << k, L.ipa_folded.as<uint32_t>(), nullptr, L.ipa_xyzz_a.p))) return rc;
     if ((rc = mb_msm_variable(c, curve, (uint32_t)(cnt * per), src->ipa_scalars.as<uint32_t>() + lo * per * 8, src->ipa_points.as<affine_t>() + lo * per, nullptr, L.ipa_xyzz_b.p))) return rc;
     DISPATCH_FIELD(FB, { xyzz_compare_kernel<F_><<<1, 64, 0, L.stream>>>(L.ipa_xyzz_a.as<xyzz_t>(), L.ipa_xyzz_b.as<xyzz_t>(), 1, d_verdict, d_verdict + 1); });
+    HIPC(hipGetLastError());
+    return MINA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The grouped culprit search (api_state.hip): every part of a round in one pass on the current lane.
+size_t mb_search_parts_cap(mina_ctx *c, int curve, uint32_t k) {
+    const SrsState &s = c->srs[curve];
+    const uint64_t by_entries = ((uint64_t)1 << 28) / (((uint64_t)1 << k) * (s.W ? s.W : 1));
+    return (size_t)std::max<uint64_t>(1, std::min<uint64_t>(128, by_entries));
+}
+
+// the tables of a pass into the lane's gs_tab: [begin | end] in proofs, then [begin | end] scaled by `per` (entries of the rows), np words each.  They go through
+// the lane's pinned staging buffer at `stage_off`: the passes of a round are queued back to back, each with its own 16 * np bytes of it, and the search waits for the
+// lane at the end of the round -- the buffer is free again when the next round fills it.
+static int parts_tables(mina_ctx *c, size_t np, const uint32_t *lo, const uint32_t *cnt, uint32_t base, uint32_t per, size_t stage_off) {
+    Lane &L = *c->L;
+    int rc;
+    if ((rc = L.host_stage.ensure(stage_off + np * 16)) || (rc = L.gs_tab.ensure(np * 16))) return rc;      // (the caller sized the staging buffer for the whole round: no reallocation between its passes)
+    uint32_t *t = (uint32_t *)((uint8_t *)L.host_stage.p + stage_off);
+    for (size_t p = 0; p < np; ++p) {
+        t[p] = lo[p] - base; t[np + p] = lo[p] - base + cnt[p];
+        t[2 * np + p] = (lo[p] - base) * per; t[3 * np + p] = (lo[p] - base + cnt[p]) * per;
+    }
+    HIPC(hipMemcpyAsync(L.gs_tab.p, t, np * 16, hipMemcpyHostToDevice, L.stream));
+    return MINA_OK;
+}
+
+int mb_ipa_recheck_rows_parts(mina_ctx *c, size_t np, const uint32_t *lo, const uint32_t *cnt, uint32_t *d_flags, size_t stage_off) {
+    Lane *src = c->ipa_rows;
+    if (!src || np == 0) return fail(MINA_ERR_STATE, "no prepared rows");
+    const int curve = c->ipa_rows_curve, FB = base_field_of(curve), FS = scalar_field_of(curve);
+    const uint32_t k = c->ipa_rows_k, per = c->ipa_rows_per, n = 1u << k;
+    SrsState &s = c->srs[curve];
+    uint32_t first = 0xffffffffu, last = 0, longest = 0;
+    for (size_t p = 0; p < np; ++p) {
+        if (cnt[p] == 0 || (uint64_t)lo[p] + cnt[p] > c->ipa_rows_batch) return fail(MINA_ERR_STATE, "no prepared rows for that range");
+        first = std::min(first, lo[p]); last = std::max(last, lo[p] + cnt[p]); longest = std::max(longest, cnt[p]);
+    }
+    const uint32_t span = last - first;                         // the pass works on proofs [first, last) of the rows; the tables are relative to `first`
+    Lane &L = *c->L;
+    int rc;
+    if ((rc = L.gs_folded.ensure(np * (size_t)n * 32)) || (rc = L.gs_xa.ensure(np * sizeof(xyzz_t))) || (rc = L.gs_xb.ensure(np * sizeof(xyzz_t)))) return rc;
+    if ((rc = parts_tables(c, np, lo, cnt, first, per, stage_off))) return rc;
+    const uint32_t *tab = L.gs_tab.as<uint32_t>();
+    if (const uint32_t nsh = c->ipa_rows_nshared)              // these proofs get their own scalars of the batch-shared points back (idempotent)
+        mb::ipa_shared_restore_kernel<<<cdiv((size_t)span * nsh * 8, 256), 256, 0, L.stream>>>(first, span, nsh, per, src->ipa_shared_off.as<uint32_t>(), src->ipa_shared.as<uint32_t>(), src->ipa_scalars.as<uint32_t>());
+    if ((rc = mb_bpoly_fold_segments(c, FS, k, span, np, longest, tab, tab + np, src->ipa_chals.as<uint32_t>() + (size_t)first * k * 8, src->ipa_sigma.as<uint32_t>() + (size_t)first * 8, L.gs_folded.as<uint32_t>()))) return rc;
+    if ((rc = mb_msm_table(c, curve, s.table.p, s.depth, s.c, s.W, 0, n, (uint32_t)np, L.gs_folded.as<uint32_t>(), nullptr, L.gs_xa.p))) return rc;
+    if ((rc = mb_msm_segments(c, curve, span * per, np, longest * per, tab + 2 * np, tab + 3 * np, src->ipa_scalars.as<uint32_t>() + (size_t)first * per * 8,
+                              src->ipa_points.as<affine_t>() + (size_t)first * per, nullptr, L.gs_xb.p))) return rc;
+    DISPATCH_FIELD(FB, { mb::xyzz_compare_parts_kernel<F_><<<(uint32_t)np, 64, 0, L.stream>>>(L.gs_xa.as<xyzz_t>(), L.gs_xb.as<xyzz_t>(), 1, tab, tab + np, nullptr, 0, d_flags); });
+    HIPC(hipGetLastError());
+    return MINA_OK;
+}
+
+int mb_accumulator_parts_prepare(mina_ctx *c, int curve, uint32_t k, size_t batch, const uint32_t *d_prechal, const uint32_t *d_sg_words) {
+    const int FS = scalar_field_of(curve), FB = base_field_of(curve);
+    Lane &L = *c->L;
+    int rc;
+    if ((rc = L.gs_chals.ensure(batch * k * 32)) || (rc = L.gs_points.ensure(batch * sizeof(affine_t))) || (rc = L.gs_bad.ensure(batch * 4))) return rc;
+    DISPATCH_FIELD(FS, { challenge_to_field_kernel<F_><<<cdiv(batch * k, 64), 64, 0, L.stream>>>((uint32_t)(batch * k), c->fk[F_], d_prechal, L.gs_chals.as<uint32_t>()); });
+    DISPATCH_FIELD(FB, { mb::points_to_mont_checked_each_kernel<F_><<<cdiv(batch, 256), 256, 0, L.stream>>>((uint32_t)batch, d_sg_words, c->fk[F_], L.gs_points.as<affine_t>(), L.gs_bad.as<uint32_t>()); });
+    HIPC(hipGetLastError());
+    return MINA_OK;
+}
+
+int mb_accumulator_check_parts(mina_ctx *c, int curve, uint32_t k, size_t batch, const uint32_t *d_rho, size_t np, const uint32_t *lo, const uint32_t *cnt, uint32_t *d_flags, size_t stage_off) {
+    SrsState &s = c->srs[curve];
+    if (s.depth == 0 || k < 1 || k > 20 || ((size_t)1 << k) > s.depth || np == 0 || !d_rho) return fail(MINA_ERR_ARG, "bad grouped accumulator check");
+    const int FS = scalar_field_of(curve), FB = base_field_of(curve);
+    const uint32_t n = 1u << k;
+    uint32_t longest = 0;
+    for (size_t p = 0; p < np; ++p) {
+        if (cnt[p] == 0 || (uint64_t)lo[p] + cnt[p] > batch) return fail(MINA_ERR_ARG, "part outside the batch");
+        longest = std::max(longest, cnt[p]);
+    }
+    Lane &L = *c->L;
+    int rc;
+    if ((rc = L.gs_folded.ensure(np * (size_t)n * 32)) || (rc = L.gs_xa.ensure(np * sizeof(xyzz_t))) || (rc = L.gs_xb.ensure(np * sizeof(xyzz_t)))) return rc;
+    if ((rc = parts_tables(c, np, lo, cnt, 0, 1, stage_off))) return rc;
+    const uint32_t *tab = L.gs_tab.as<uint32_t>();
+    if ((rc = mb_bpoly_fold_segments(c, FS, k, batch, np, longest, tab, tab + np, L.gs_chals.as<uint32_t>(), d_rho, L.gs_folded.as<uint32_t>()))) return rc;
+    if ((rc = mb_msm_table(c, curve, s.table.p, s.depth, s.c, s.W, 0, n, (uint32_t)np, L.gs_folded.as<uint32_t>(), nullptr, L.gs_xa.p))) return rc;
+    if ((rc = mb_msm_segments(c, curve, (uint32_t)batch, np, longest, tab, tab + np, d_rho, L.gs_points.p, nullptr, L.gs_xb.p))) return rc;
+    DISPATCH_FIELD(FB, { mb::xyzz_compare_parts_kernel<F_><<<(uint32_t)np, 64, 0, L.stream>>>(L.gs_xa.as<xyzz_t>(), L.gs_xb.as<xyzz_t>(), 0, tab, tab + np, L.gs_bad.as<uint32_t>(), (uint32_t)batch, d_flags); });
     HIPC(hipGetLastError());
     return MINA_OK;
 }

@@ -1,6 +1,7 @@
 // api_msm.hip -- K1 host driver: queues the MSM kernel pipeline of msm.cuh on the context stream.
 #include "ctx.h"
 #include "msm.cuh"
+#include "msm_seg.cuh"
 #include <vector>
 #include <cstdlib>
 
@@ -21,7 +22,8 @@ template <int F>
 static int run_msm(mina_ctx *c, const MsmShape &sh, const uint32_t *d_scalars, const affine_t *d_points,
                    uint32_t *d_out_words /* 17 words per problem */, xyzz_t *d_out_xyzz /* one per problem */,
                    const affine_t *d_points29 = nullptr /* the table's 2^261-domain twin (SrsState::table29): the accumulate kernels then run on 29-bit limbs (ec29.cuh) */,
-                   const void *d_points29s = nullptr /* ... or its pre-split form (SrsState::table29s, tab29_t records; mina_verify_tuning.msm_fp29 = 2) */) {
+                   const void *d_points29s = nullptr /* ... or its pre-split form (SrsState::table29s, tab29_t records; mina_verify_tuning.msm_fp29 = 2) */,
+                   const MsmSegments *seg = nullptr /* the problems are ranges of ONE scalar / point array (msm_seg.cuh): sh.n = the longest range, `d_scalars` and the references index the whole array */) {
     if (d_points29 && !mb_tune().msm_fp29) d_points29 = nullptr;      // cross-check switch: the 8 x 32 law everywhere
     const bool split = d_points29 && d_points29s && mb_tune().msm_fp29 == 2;
     bool red29 = false;                                              // msm_fp29 = 3: the buckets of the multi-MSM form stay on 29-bit limbs and the 2-D reduction runs on them too
@@ -82,10 +84,12 @@ static int run_msm(mina_ctx *c, const MsmShape &sh, const uint32_t *d_scalars, c
     const bool fused_finish = sh.nsets == sh.nprob && !d_out_words && d_out_xyzz;
     if (part_sort) {
         { ProfScope ps_(c, PS_DIGITS);
-          msm_part_kernel<false><<<ss.Gl * sh.nprob, 1024, 0, st>>>(sh, ss, d_scalars, w.ghist.as<uint32_t>(), nullptr, w.ekey.as<uint32_t>());
+          if (seg) msm_part_seg_kernel<false><<<ss.Gl * sh.nprob, 1024, 0, st>>>(sh, ss, *seg, d_scalars, w.ghist.as<uint32_t>(), nullptr, w.ekey.as<uint32_t>());
+          else msm_part_kernel<false><<<ss.Gl * sh.nprob, 1024, 0, st>>>(sh, ss, d_scalars, w.ghist.as<uint32_t>(), nullptr, w.ekey.as<uint32_t>());
           msm_excl_scan_kernel<<<1, 1024, 0, st>>>((uint32_t)gh_words, w.ghist.as<uint32_t>()); }
         { ProfScope ps_(c, PS_SCATTER);
-          msm_part_kernel<true><<<ss.Gl * sh.nprob, 1024, 0, st>>>(sh, ss, d_scalars, w.ghist.as<uint32_t>(), w.stage.as<uint2>(), w.ekey.as<uint32_t>());
+          if (seg) msm_part_seg_kernel<true><<<ss.Gl * sh.nprob, 1024, 0, st>>>(sh, ss, *seg, d_scalars, w.ghist.as<uint32_t>(), w.stage.as<uint2>(), w.ekey.as<uint32_t>());
+          else msm_part_kernel<true><<<ss.Gl * sh.nprob, 1024, 0, st>>>(sh, ss, d_scalars, w.ghist.as<uint32_t>(), w.stage.as<uint2>(), w.ekey.as<uint32_t>());
           msm_part_sort_kernel<<<ss.Pl * sh.nprob, 1024, 0, st>>>(ss, w.ghist.as<uint32_t>(), w.stage.as<uint2>(), w.count.as<uint32_t>(), w.sorted.as<uint32_t>(), w.info.as<uint32_t>()); }
         if (bucket_lanes) {
             ProfScope ps_(c, PS_SCAN);
@@ -97,7 +101,9 @@ static int run_msm(mina_ctx *c, const MsmShape &sh, const uint32_t *d_scalars, c
         }
     } else {
         HIPC(hipMemsetAsync(w.count.p, 0, (size_t)nb_total * 4, st));
-        { ProfScope ps_(c, PS_DIGITS); msm_digits_kernel<<<cdiv(entries, 256), 256, 0, st>>>(sh, d_scalars, w.count.as<uint32_t>(), w.ekey.as<uint32_t>(),
+        { ProfScope ps_(c, PS_DIGITS);
+          if (seg) msm_digits_seg_kernel<<<cdiv(entries, 256), 256, 0, st>>>(sh, *seg, d_scalars, w.count.as<uint32_t>(), w.ekey.as<uint32_t>(), w.eval.as<uint32_t>(), w.eoff.as<uint32_t>());
+          else msm_digits_kernel<<<cdiv(entries, 256), 256, 0, st>>>(sh, d_scalars, w.count.as<uint32_t>(), w.ekey.as<uint32_t>(),
                                                            w.eval.as<uint32_t>(), w.eoff.as<uint32_t>()); }
         { ProfScope ps_(c, PS_SCAN); msm_scan_kernel<<<1, 1024, 0, st>>>(nb_total, w.count.as<uint32_t>(), w.start.as<uint32_t>(), w.task_start.as<uint32_t>(),
                                                                        w.rem_pos.as<uint32_t>(), w.info.as<uint32_t>());
@@ -220,6 +226,77 @@ int mb_msm_variable(mina_ctx *c, int curve, uint32_t n, const uint32_t *d_scalar
     }
     DISPATCH_FIELD(base_field_of(curve), { rc = run_msm<F_>(c, sh, d_scalars, (const affine_t *)d_points_mont, d_out_words, (xyzz_t *)d_out_xyzz, twin); });
     return rc;
+}
+
+// The segment tables of the two segmented entry points (device memory): read back on the current lane -- the one host wait of those calls, behind whatever
+// the lane already holds -- and checked: begin <= end <= limit for every segment.  max_len = the longest segment.
+int mb_read_segments(mina_ctx *c, size_t nseg, const void *d_begin, const void *d_end, size_t limit, uint32_t *max_len) {
+    std::vector<uint32_t> h(2 * nseg);
+    HIPC(hipMemcpyAsync(h.data(), d_begin, nseg * 4, hipMemcpyDeviceToHost, c->L->stream));
+    HIPC(hipMemcpyAsync(h.data() + nseg, d_end, nseg * 4, hipMemcpyDeviceToHost, c->L->stream));
+    HIPC(hipStreamSynchronize(c->L->stream));
+    uint32_t mx = 0;
+    for (size_t s = 0; s < nseg; ++s) {
+        const uint32_t b = h[s], e = h[nseg + s];
+        if (e < b || e > limit) return fail(MINA_ERR_ARG, "segment " + std::to_string(s) + ": need begin <= end <= " + std::to_string(limit));
+        mx = std::max(mx, e - b);
+    }
+    *max_len = mx;
+    return MINA_OK;
+}
+
+// nseg variable-base MSMs over ranges of one point / scalar array: the ranges are the problems of ONE pipeline (msm_seg.cuh)
+static int msm_segments_shape(uint32_t max_len, size_t nseg, MsmShape &sh) {
+    sh = variable_shape(max_len ? max_len : 1);                  // every segment empty: one scalar slot per problem that no lane fills -> nseg times infinity
+    if ((uint64_t)sh.NB * sh.W * nseg > (1u << 26) || (uint64_t)sh.n * sh.W * nseg > (1u << 28))
+        return fail(MINA_ERR_ARG, "segmented MSM too large for one pipeline: need NB * W * nseg <= 2^26 and longest segment * W * nseg <= 2^28 (W windows of NB buckets: 32 x 128 below 2048 points per segment, 20 x 4096 below 2^17, 18 x 16384 above)");
+    sh.nprob = (uint32_t)nseg; sh.nsets = sh.W * (uint32_t)nseg;
+    return MINA_OK;
+}
+
+bool mb_msm_segments_fit(uint32_t max_len, size_t nseg) {
+    const MsmShape v = variable_shape(max_len ? max_len : 1);
+    return nseg > 0 && (uint64_t)v.NB * v.W * nseg <= (1u << 26) && (uint64_t)v.n * v.W * nseg <= (1u << 28);
+}
+
+// on the current lane; the points are Montgomery affine already; max_len = the longest segment (the caller has read or made the tables)
+int mb_msm_segments(mina_ctx *c, int curve, uint32_t n_total, size_t nseg, uint32_t max_len, const uint32_t *d_begin, const uint32_t *d_end,
+                    const uint32_t *d_scalars, const void *d_points_mont, uint32_t *d_out_words, void *d_out_xyzz) {
+    MsmShape sh;
+    int rc;
+    if ((rc = msm_segments_shape(max_len, nseg, sh))) return rc;
+    MsmWorkspace &w = c->L->ws;
+    const int F = base_field_of(curve);
+    const affine_t *twin = nullptr;
+    if (mb_tune().msm_fp29 && max_len >= 32 && n_total) {         // as mb_msm_variable: below 32 points per problem the 8 x 32 law, no twin
+        if ((rc = w.points29.ensure((size_t)n_total * sizeof(affine_t)))) return rc;
+        DISPATCH_FIELD(F, { msm_table29_kernel<F_><<<cdiv(n_total, 256), 256, 0, c->L->stream>>>(n_total, (const affine_t *)d_points_mont, c->fk[F_].m32, w.points29.as<affine_t>()); });
+        twin = w.points29.as<affine_t>();
+    }
+    const MsmSegments sg{d_begin, d_end, n_total};
+    DISPATCH_FIELD(F, { rc = run_msm<F_>(c, sh, d_scalars, (const affine_t *)d_points_mont, d_out_words, (xyzz_t *)d_out_xyzz, twin, nullptr, &sg); });
+    return rc;
+}
+
+extern "C" int mina_msm_segments_dev(mina_ctx *c, int curve, size_t n_total, size_t nseg, const void *d_seg_begin, const void *d_seg_end,
+                                     const void *d_bases, const void *d_scalars, void *d_out) {
+    if (!c || !d_seg_begin || !d_seg_end || !d_out || (n_total && (!d_bases || !d_scalars))) return fail(MINA_ERR_ARG, "null argument");
+    if (curve != 0 && curve != 1) return fail(MINA_ERR_ARG, "bad curve");
+    if (((uintptr_t)d_seg_begin | (uintptr_t)d_seg_end | (uintptr_t)d_out) & 3u) return fail(MINA_ERR_ARG, "segment tables and records are arrays of 32-bit words: 4-byte alignment");
+    if (((uintptr_t)d_bases | (uintptr_t)d_scalars) & 15u) return fail(MINA_ERR_ARG, "bases and scalars are read 16 bytes at a time: 16-byte alignment");
+    if (nseg == 0 || nseg > (1u << 19) || n_total > (1u << 24)) return fail(MINA_ERR_ARG, "bad nseg / n_total");
+    MsmShape sh;
+    int rc;
+    if ((rc = msm_segments_shape(0, nseg, sh))) return rc;       // the bucket limit at the smallest window shape: refused before the device is touched
+    HIPC(hipSetDevice(c->device));
+    c->next_lane();
+    uint32_t max_len = 0;
+    if ((rc = mb_read_segments(c, nseg, d_seg_begin, d_seg_end, n_total, &max_len))) return rc;
+    if ((rc = msm_segments_shape(max_len, nseg, sh))) return rc;
+    MsmWorkspace &w = c->L->ws;
+    if ((rc = w.points.ensure((n_total ? n_total : 1) * sizeof(affine_t)))) return rc;
+    if (n_total) DISPATCH_FIELD(base_field_of(curve), { points_to_mont_kernel<F_><<<cdiv(n_total, 256), 256, 0, c->L->stream>>>((uint32_t)n_total, (const uint32_t *)d_bases, c->fk[F_].r2, w.points.as<affine_t>()); });
+    return mb_msm_segments(c, curve, (uint32_t)n_total, nseg, max_len, (const uint32_t *)d_seg_begin, (const uint32_t *)d_seg_end, (const uint32_t *)d_scalars, w.points.p, (uint32_t *)d_out, nullptr);
 }
 
 extern "C" int mina_msm(mina_ctx *c, int curve, size_t n, const uint8_t *bases, const uint8_t *scalars, uint8_t *out) {

@@ -2,6 +2,7 @@
 #include "ctx.h"
 #include "sponge.cuh"
 #include "bpoly_mfma.cuh"
+#include "bpoly_seg.cuh"
 
 // ------------------------------------------------------------------------------------------------
 // // K2
@@ -74,6 +75,53 @@ extern "C" int mina_b_poly_fold_dev(mina_ctx *c, int field, uint32_t k, size_t b
     HIPC(hipSetDevice(c->device));
     c->next_lane();
     return mb_bpoly_fold(c, field, k, batch, (const uint32_t *)d_chals, (const uint32_t *)d_weights, (uint32_t *)d_out);
+}
+
+// nseg folds over ranges of one batch in one launch set: the half tables of the whole batch once (bpoly_tables_kernel, as the single fold's VALU path), then
+// the fold with the segment on grid.y and the conversion to canonical words.  Sums of canonical Montgomery products modulo p: the words equal those of
+// mina_b_poly_fold_dev over each range alone, whichever of its kernels (VALU, matrix cores, single-proof) that call takes.
+template <int F>
+static int run_bpoly_fold_segments(mina_ctx *c, uint32_t k, size_t batch, size_t nseg, uint32_t max_len, const MsmSegments &sg, const uint32_t *d_chals, const uint32_t *d_weights, uint32_t *d_out) {
+    BpolyShape sh = bp_shape(k, batch);
+    const uint32_t nl = 1u << sh.lb, nh = 1u << sh.hb, n = 1u << k;
+    const uint32_t lo_blocks = cdiv(nl, 256), hi_tiles = cdiv(nh, BP_HT);
+    uint32_t slices = 1;                                         // few long segments: slices of each fill the chip, as in run_bpoly_fold
+    while (slices * 2 <= max_len && (size_t)lo_blocks * hi_tiles * nseg * slices < 2048 && slices < 64) slices *= 2;
+    Lane &L = *c->L;
+    int rc;
+    if ((rc = L.bp_ltab.ensure(batch * nl * sizeof(fe_t))) || (rc = L.bp_htab.ensure(batch * nh * sizeof(fe_t)))) return rc;
+    if (slices > 1 && (rc = L.bp_partial.ensure(nseg * slices * n * sizeof(fe_t)))) return rc;
+    fe_t *partial = slices > 1 ? L.bp_partial.as<fe_t>() : (fe_t *)d_out;      // one slice: the fold writes into the output, converted in place
+    { ProfScope ps_(c, PS_BPOLY_TABLES); bpoly_tables_kernel<F><<<cdiv(batch * (nl + nh), 256), 256, 0, L.stream>>>(sh, c->fk[F], d_chals, d_weights, L.bp_ltab.as<fe_t>(), L.bp_htab.as<fe_t>()); }
+    { ProfScope ps_(c, PS_BPOLY_FOLD); bpoly_fold_seg_kernel<F><<<dim3(lo_blocks * hi_tiles * slices, (uint32_t)nseg), 256, 0, L.stream>>>(sh, slices, sg, L.bp_ltab.as<fe_t>(), L.bp_htab.as<fe_t>(), partial); }
+    { ProfScope ps_(c, PS_BPOLY_FINISH); bpoly_finish_seg_kernel<F><<<dim3(cdiv(n, 256), (uint32_t)nseg), 256, 0, L.stream>>>(n, slices, partial, d_out); }
+    HIPC(hipGetLastError());
+    return MINA_OK;
+}
+
+int mb_bpoly_fold_segments(mina_ctx *c, int field, uint32_t k, size_t batch, size_t nseg, uint32_t max_len, const uint32_t *d_begin, const uint32_t *d_end,
+                           const uint32_t *d_chals, const uint32_t *d_weights, uint32_t *d_out) {
+    if (bad_field(field) || k < 1 || k > 20 || batch == 0 || batch > (1u << 24) || nseg == 0 || nseg > 65535) return fail(MINA_ERR_ARG, "bad segmented fold shape");
+    const MsmSegments sg{d_begin, d_end, (uint32_t)batch};
+    int rc = MINA_OK;
+    DISPATCH_FIELD(field, { rc = run_bpoly_fold_segments<F_>(c, k, batch, nseg, max_len, sg, d_chals, d_weights, d_out); });
+    return rc;
+}
+
+extern "C" int mina_b_poly_fold_segments_dev(mina_ctx *c, int field, uint32_t k, size_t batch, size_t nseg, const void *d_seg_begin, const void *d_seg_end,
+                                             const void *d_chals, const void *d_weights, void *d_out) {
+    if (!c || !d_seg_begin || !d_seg_end || !d_chals || !d_out) return fail(MINA_ERR_ARG, "null argument");      // d_weights may be null: every weight 1, as mina_b_poly_fold_dev
+    if (bad_field(field)) return fail(MINA_ERR_ARG, "bad field");
+    if (((uintptr_t)d_seg_begin | (uintptr_t)d_seg_end | (uintptr_t)d_chals | (uintptr_t)d_weights) & 3u) return fail(MINA_ERR_ARG, "segment tables, challenges and weights are arrays of 32-bit words: 4-byte alignment");
+    if ((uintptr_t)d_out & 15u) return fail(MINA_ERR_ARG, "the output is written 16 bytes at a time: 16-byte alignment");
+    if (k < 1 || k > 20 || batch == 0 || batch > (1u << 24) || nseg == 0 || nseg > 65535) return fail(MINA_ERR_ARG, "bad k, batch or nseg (1 .. 65535 segments)");
+    if (((uint64_t)nseg << k) > (1u << 28)) return fail(MINA_ERR_ARG, "nseg * 2^k beyond 2^28 output scalars");
+    HIPC(hipSetDevice(c->device));
+    c->next_lane();
+    int rc;
+    uint32_t max_len = 0;
+    if ((rc = mb_read_segments(c, nseg, d_seg_begin, d_seg_end, batch, &max_len))) return rc;
+    return mb_bpoly_fold_segments(c, field, k, batch, nseg, max_len, (const uint32_t *)d_seg_begin, (const uint32_t *)d_seg_end, (const uint32_t *)d_chals, (const uint32_t *)d_weights, (uint32_t *)d_out);
 }
 
 extern "C" int mina_b_poly_fold(mina_ctx *c, int field, uint32_t k, size_t batch, const uint8_t *chals, const uint8_t *weights, uint8_t *out) {

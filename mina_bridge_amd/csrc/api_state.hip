@@ -772,64 +772,26 @@ extern "C" int mina_state_job_fold_dev(mina_ctx *c, const mina_state_jobs *jobs,
     return mb_state_jobs_on_lane(c, jobs, (uint32_t *)d_verdicts, (uint32_t *)d_flags, plan);
 }
 
-// host-buffer form: one upload of every section, the pipeline, one download; when a folded check fails the proofs are
-// re-checked in parts (32-way cuts, the parts of a round concurrently) so that every proof gets its own verdict (README.md:281-310: every failure is `false`)
 namespace {
 struct Section { const void **slot; size_t bytes; };
 }
-extern "C" int mina_state_job_batch(mina_ctx *c, const mina_state_jobs *jobs, uint8_t *verdicts) {
-    int rc = check_jobs(c, jobs);
-    if (rc) return rc;
-    if (!verdicts) return fail(MINA_ERR_ARG, "null argument");
-    HIPC(hipSetDevice(c->device));
-    c->use_lane0();
-    if ((rc = mina_state_jobs_prepare(c, jobs->log2_domain, jobs->npub))) return rc;
-    c->use_lane0();
-    Lane &L = *c->L;
-    mina_state_jobs d = *jobs;
-    const size_t B = jobs->batch, k = jobs->k, m = jobs->n_comms, np = jobs->n_evalpoints, S = MINA_STATES_PER_PROOF;
-    std::vector<Section> secs;
-    auto add = [&](const void *&slot, size_t bytes) { if (slot && bytes) secs.push_back({&slot, bytes}); };
-    if (d.with_states) { add(d.state_records, B * S * MINA_PSTATE_SLOTS * 32); add(d.state_nfields, B * S * 4); add(d.expected_hashes, B * S * 32); add(d.precheck, B); }
-    if (d.npub) add(d.public_inputs, B * d.npub * 32);
-    mina_kimchi_proofs kd{}; mina_pickles_statements sd{};
-    if (d.with_ipa && d.kimchi) {
-        kd = *d.kimchi; d.kimchi = &kd;
-        kd.public_inputs = nullptr;                                   // the job's own public_inputs section is the one uploaded
-        add(kd.prev_chals, B * kd.n_prev * k * 32); add(kd.prev_prechallenges, B * kd.n_prev * k * 16); add(kd.prev_comms, B * kd.n_prev * 64); add(kd.w_comm, B * 15 * 64); add(kd.z_comm, B * 64);
-        add(kd.t_comm, B * 7 * 64); add(kd.evals, B * 43 * 64); add(kd.ft_eval1, B * 32);
-        if (kd.statements) {
-            const void **slots[12]; size_t strides[12];
-            mb_pickles_sections(kd.statements, slots, strides, &sd);
-            kd.statements = &sd;
-            for (int i = 0; i < 12; ++i) add(*slots[i], B * strides[i]);
-        }
-        d.sponge_state = d.sponge_pos = d.cip = d.evalpoints = d.evalscale = d.polyscale = d.comms = nullptr;
-    }
-    if (d.with_ipa) {
-        add(d.sponge_state, B * 96); add(d.sponge_pos, B * 8); add(d.cip, B * 32); add(d.lr, B * 2 * k * 64); add(d.delta, B * 64); add(d.sg, B * 64);
-        add(d.z1, B * 32); add(d.z2, B * 32); add(d.evalpoints, B * np * 32); add(d.evalscale, B * 32); add(d.polyscale, B * 32); add(d.comms, B * m * 64);
-        add(d.rand_base, 32); add(d.sg_rand_base, 32);
-    }
-    if (d.with_accumulator) { add(d.acc_prechallenges, B * d.acc_k * 16); add(d.acc_sg, B * 64); add(d.acc_rho, B * 32); }
-    size_t total = 0;
-    std::vector<size_t> offs;
-    for (auto &s : secs) { offs.push_back(total); total += (s.bytes + 255) & ~(size_t)255; }
-    if ((rc = L.host_stage.ensure(total + B * 4))) return rc;
-    uint8_t *blob = (uint8_t *)L.host_stage.p;
-    for (size_t i = 0; i < secs.size(); ++i) memcpy(blob + offs[i], *secs[i].slot, secs[i].bytes);
-    if ((rc = L.st_in.ensure(total))) return rc;
-    HIPC(hipMemcpyAsync(L.st_in.p, blob, total, hipMemcpyHostToDevice, L.stream));
-    for (size_t i = 0; i < secs.size(); ++i) *secs[i].slot = L.st_in.as<uint8_t>() + offs[i];
-    if (d.kimchi) kd.public_inputs = d.public_inputs;
+// The body mina_state_job_batch (after its upload) and mina_state_job_each_dev share: the job on lane L from inputs in HBM (every pointer of `d` a device pointer),
+// one verdict byte per proof on the host.  When a folded check fails: a run without the folded legs for the per-proof chain verdicts, then the search for the
+// culprits of each failed leg -- in groups on lane L alone (mina_ctx_set_search_groups) or over the fan's lanes.  Waits for lane L.  flags: the four words of the
+// whole job's folded checks ([0] opening verdict, [1] malformed opening input, [2] accumulator verdict), or null.
+static int state_job_each(mina_ctx *c, Lane &L, const mina_state_jobs &d, uint8_t *verdicts, uint32_t *flags) {
+    c->L = &L;
+    const size_t B = d.batch, k = d.k, m = d.n_comms, np = d.n_evalpoints;
+    int rc;
     if ((rc = L.st_verdicts.ensure(2 * B * 4 + 16))) return rc;
     uint32_t *dv = L.st_verdicts.as<uint32_t>(), *df = dv + B, *ds = df + 4;
     // small, latency-bound batches: the three independent legs go to three lanes (lane 0 plus two helpers), joined by events
     StateJobPlan plan; plan.d_stmt_out = ds;
-    if (B <= 1024 && c->nlanes == 1) { plan.wrap = &c->lanes[1]; plan.acc = &c->lanes[2]; }
+    if (B <= 1024 && c->nlanes == 1 && &L == &c->lanes[0]) { plan.wrap = &c->lanes[1]; plan.acc = &c->lanes[2]; }
     if ((rc = mb_state_jobs_on_lane(c, &d, dv, df, plan))) return rc;
     std::vector<uint32_t> hv(2 * B + 4);
     if ((rc = d2h_sync(c, hv.data(), L.st_verdicts, (2 * B + 4) * 4))) return rc;
+    if (flags) memcpy(flags, &hv[B], 16);
     std::vector<uint8_t> stmt_each(B); for (size_t b = 0; b < B; ++b) stmt_each[b] = hv[B + 4 + b] ? 1 : 0;
     const bool ipa_ok = hv[B] != 0, acc_ok = hv[B + 2] != 0;
     if (ipa_ok && acc_ok) { for (size_t b = 0; b < B; ++b) verdicts[b] = hv[b] ? 1 : 0; return MINA_OK; }
@@ -882,7 +844,7 @@ extern "C" int mina_state_job_batch(mina_ctx *c, const mina_state_jobs *jobs, ui
             ~Restore() { for (size_t i : made) if (c->lanes[i].stream) { (void)hipStreamSynchronize(c->lanes[i].stream); (void)hipStreamDestroy(c->lanes[i].stream); c->lanes[i].stream = nullptr; } c->use_lane0(); }
         } restore{c, {}};
         for (size_t i = 0; i < FAN; ++i)
-            if (!c->lanes[i].stream) { HIPC(hipStreamCreateWithFlags(&c->lanes[i].stream, hipStreamNonBlocking)); restore.made.push_back(i); }
+            if (!c->lanes[i].stream) { HIPC(hipStreamCreateWithFlags(&c->lanes[i].stream, hipStreamNonBlocking)); restore.made.push_back(i); ++c->search_streams_made; }
         std::vector<std::pair<size_t, size_t>> failing{{0, B}};
         while (!failing.empty()) {
             std::vector<std::pair<size_t, size_t>> parts;
@@ -920,8 +882,158 @@ extern "C" int mina_state_job_batch(mina_ctx *c, const mina_state_jobs *jobs, ui
         }
         return MINA_OK;
     };
-    if (!ipa_ok && (rc = search(true, ipa_each))) return rc;
-    if (!acc_ok && (rc = search(false, acc_each))) return rc;
+    // The grouped search (mina_ctx_set_search_groups; off by default): a failing range is cut into min(G, cnt) parts by the same formula, and ALL parts of a round --
+    // of every failing range -- are checked in one pass on lane L: one segmented fold, the fixed-base MSM with one problem per part, one segmented variable-base
+    // MSM, one comparison launch, one wait and one read-back of the parts' flags.  Depth ceil(log_G B) rounds; no lane but L is used and no stream is created.  A
+    // round goes out in several passes only beyond mb_search_parts_cap parts (or where the segmented MSM's limits ask for fewer), queued back to back.  The opening
+    // leg needs the rows of the failed batch (rows_ok), else it keeps the fan search; the counters depend on (B, G, culprits) alone.
+    auto grouped = [&](bool ipa_leg, std::vector<uint8_t> &each) -> int {
+        c->L = &L;
+        const size_t G = c->search_groups;
+        const int curve = ipa_leg ? CURVE_PALLAS : CURVE_VESTA;
+        const size_t cap = mb_search_parts_cap(c, curve, ipa_leg ? d.k : d.acc_k);
+        const uint32_t per = ipa_leg ? c->ipa_rows_per : 1;
+        int r;
+        if (!ipa_leg && (r = mb_accumulator_parts_prepare(c, CURVE_VESTA, d.acc_k, B, (const uint32_t *)d.acc_prechallenges, (const uint32_t *)d.acc_sg))) return r;
+        ++c->gs_searches;
+        std::vector<std::pair<size_t, size_t>> failing{{0, B}};
+        while (!failing.empty()) {
+            std::vector<uint32_t> lo, cnt;
+            for (auto [l, n] : failing) {
+                if (n == 1) { each[l] = 0; continue; }
+                const size_t g = std::min(G, n);
+                for (size_t q = 0; q < g; ++q) { const size_t a = l + n * q / g, e = l + n * (q + 1) / g; lo.push_back((uint32_t)a); cnt.push_back((uint32_t)(e - a)); }
+            }
+            failing.clear();
+            const size_t nparts = lo.size();
+            if (nparts == 0) break;
+            ++c->gs_rounds; c->gs_parts += nparts;
+            if ((r = L.gs_flags.ensure(nparts * 4)) || (r = L.host_stage.ensure(nparts * 16))) return r;
+            uint32_t *fl = L.gs_flags.as<uint32_t>();
+            for (size_t base = 0; base < nparts;) {
+                size_t w = std::min(cap, nparts - base);
+                auto longest = [&](size_t w_) { uint32_t x = 0; for (size_t q = 0; q < w_; ++q) x = std::max(x, cnt[base + q]); return x; };
+                while (w > 1 && !mb_msm_segments_fit(longest(w) * per, w)) w = (w + 1) / 2;
+                r = ipa_leg ? mb_ipa_recheck_rows_parts(c, w, &lo[base], &cnt[base], fl + base, base * 16)
+                            : mb_accumulator_check_parts(c, CURVE_VESTA, d.acc_k, B, (const uint32_t *)d.acc_rho, w, &lo[base], &cnt[base], fl + base, base * 16);
+                if (r) return r;
+                base += w;
+            }
+            std::vector<uint32_t> f(nparts);
+            if ((r = d2h_sync(c, f.data(), L.gs_flags, nparts * 4))) return r;
+            for (size_t p = 0; p < nparts; ++p) if (!f[p]) failing.push_back({lo[p], cnt[p]});
+        }
+        return MINA_OK;
+    };
+    const bool in_groups = c->search_groups >= 2 && !mb_tune().search_full;
+    if (!ipa_ok) { rc = (in_groups && rows_ok) ? grouped(true, ipa_each) : search(true, ipa_each); c->L = &L; if (rc) return rc; }
+    if (!acc_ok) { rc = (in_groups && B > 1 && d.acc_rho) ? grouped(false, acc_each) : search(false, acc_each); c->L = &L; if (rc) return rc; }
     for (size_t b = 0; b < B; ++b) verdicts[b] = (chain_each[b] && ipa_each[b] && acc_each[b] && stmt_each[b]) ? 1 : 0;
+    return MINA_OK;
+}
+
+// host-buffer form: one upload of every section, the pipeline, one download; when a folded check fails the proofs are
+// re-checked in parts (32-way cuts, the parts of a round concurrently) so that every proof gets its own verdict (README.md:281-310: every failure is `false`)
+extern "C" int mina_state_job_batch(mina_ctx *c, const mina_state_jobs *jobs, uint8_t *verdicts) {
+    int rc = check_jobs(c, jobs);
+    if (rc) return rc;
+    if (!verdicts) return fail(MINA_ERR_ARG, "null argument");
+    HIPC(hipSetDevice(c->device));
+    c->use_lane0();
+    if ((rc = mina_state_jobs_prepare(c, jobs->log2_domain, jobs->npub))) return rc;
+    c->use_lane0();
+    Lane &L = *c->L;
+    mina_state_jobs d = *jobs;
+    const size_t B = jobs->batch, k = jobs->k, m = jobs->n_comms, np = jobs->n_evalpoints, S = MINA_STATES_PER_PROOF;
+    std::vector<Section> secs;
+    auto add = [&](const void *&slot, size_t bytes) { if (slot && bytes) secs.push_back({&slot, bytes}); };
+    if (d.with_states) { add(d.state_records, B * S * MINA_PSTATE_SLOTS * 32); add(d.state_nfields, B * S * 4); add(d.expected_hashes, B * S * 32); add(d.precheck, B); }
+    if (d.npub) add(d.public_inputs, B * d.npub * 32);
+    mina_kimchi_proofs kd{}; mina_pickles_statements sd{};
+    if (d.with_ipa && d.kimchi) {
+        kd = *d.kimchi; d.kimchi = &kd;
+        kd.public_inputs = nullptr;                                   // the job's own public_inputs section is the one uploaded
+        add(kd.prev_chals, B * kd.n_prev * k * 32); add(kd.prev_prechallenges, B * kd.n_prev * k * 16); add(kd.prev_comms, B * kd.n_prev * 64); add(kd.w_comm, B * 15 * 64); add(kd.z_comm, B * 64);
+        add(kd.t_comm, B * 7 * 64); add(kd.evals, B * 43 * 64); add(kd.ft_eval1, B * 32);
+        if (kd.statements) {
+            const void **slots[12]; size_t strides[12];
+            mb_pickles_sections(kd.statements, slots, strides, &sd);
+            kd.statements = &sd;
+            for (int i = 0; i < 12; ++i) add(*slots[i], B * strides[i]);
+        }
+        d.sponge_state = d.sponge_pos = d.cip = d.evalpoints = d.evalscale = d.polyscale = d.comms = nullptr;
+    }
+    if (d.with_ipa) {
+        add(d.sponge_state, B * 96); add(d.sponge_pos, B * 8); add(d.cip, B * 32); add(d.lr, B * 2 * k * 64); add(d.delta, B * 64); add(d.sg, B * 64);
+        add(d.z1, B * 32); add(d.z2, B * 32); add(d.evalpoints, B * np * 32); add(d.evalscale, B * 32); add(d.polyscale, B * 32); add(d.comms, B * m * 64);
+        add(d.rand_base, 32); add(d.sg_rand_base, 32);
+    }
+    if (d.with_accumulator) { add(d.acc_prechallenges, B * d.acc_k * 16); add(d.acc_sg, B * 64); add(d.acc_rho, B * 32); }
+    size_t total = 0;
+    std::vector<size_t> offs;
+    for (auto &s : secs) { offs.push_back(total); total += (s.bytes + 255) & ~(size_t)255; }
+    if ((rc = L.host_stage.ensure(total + B * 4))) return rc;
+    uint8_t *blob = (uint8_t *)L.host_stage.p;
+    for (size_t i = 0; i < secs.size(); ++i) memcpy(blob + offs[i], *secs[i].slot, secs[i].bytes);
+    if ((rc = L.st_in.ensure(total))) return rc;
+    HIPC(hipMemcpyAsync(L.st_in.p, blob, total, hipMemcpyHostToDevice, L.stream));
+    for (size_t i = 0; i < secs.size(); ++i) *secs[i].slot = L.st_in.as<uint8_t>() + offs[i];
+    if (d.kimchi) kd.public_inputs = d.public_inputs;
+    return state_job_each(c, L, d, verdicts, nullptr);
+}
+
+// the shared body on lane 0 with the verdict bytes on the host: what the boundary's fallback runs over a failed chunk's device staging (mina_ctx::state_job_each)
+int mb_state_job_each_host(mina_ctx *c, const mina_state_jobs *jobs, uint8_t *verdicts) {
+    int rc = check_jobs(c, jobs);
+    if (rc) return rc;
+    if (!verdicts) return fail(MINA_ERR_ARG, "null argument");
+    HIPC(hipSetDevice(c->device));
+    c->use_lane0();
+    if ((rc = mina_state_jobs_prepare(c, jobs->log2_domain, jobs->npub))) return rc;
+    c->use_lane0();
+    return state_job_each(c, *c->L, *jobs, verdicts, nullptr);
+}
+
+extern "C" int mina_state_job_each_dev(mina_ctx *c, const mina_state_jobs *jobs, void *d_verdicts, void *d_flags) {
+    int rc = check_jobs(c, jobs);
+    if (rc) return rc;
+    if (!d_verdicts) return fail(MINA_ERR_ARG, "null argument");
+    if (((uintptr_t)d_verdicts | (uintptr_t)d_flags) & 3u) return fail(MINA_ERR_ARG, "verdicts and flags are 32-bit words: 4-byte alignment");
+    if (!c->have_state_salts && jobs->with_states) return fail(MINA_ERR_STATE, "call mina_state_jobs_prepare first");
+    HIPC(hipSetDevice(c->device));
+    c->next_lane();
+    Lane &L = *c->L;
+    const size_t B = jobs->batch;
+    std::vector<uint8_t> each(B);
+    std::vector<uint32_t> words(B + 4);
+    if ((rc = state_job_each(c, L, *jobs, each.data(), &words[B]))) { c->L = &L; return rc; }
+    c->L = &L;
+    for (size_t b = 0; b < B; ++b) words[b] = each[b];
+    HIPC(hipMemcpyAsync(d_verdicts, words.data(), B * 4, hipMemcpyHostToDevice, L.stream));
+    if (d_flags) HIPC(hipMemcpyAsync(d_flags, &words[B], 16, hipMemcpyHostToDevice, L.stream));
+    HIPC(hipStreamSynchronize(L.stream));
+    return MINA_OK;
+}
+
+extern "C" int mina_ctx_set_search_groups(mina_ctx *c, uint32_t groups) {
+    if (!c) return fail(MINA_ERR_ARG, "null argument");
+    if (groups == 1 || groups > 128) return fail(MINA_ERR_ARG, "search groups: 0 (off) or 2 .. 128");
+    c->search_groups = groups;
+    return MINA_OK;
+}
+
+// test-facing: the streams the context's lanes hold now (main and side streams of every lane, helpers included) and the streams its culprit searches have created
+// so far (the fan search creates the ones its lanes lack and destroys them when it is done; the grouped search creates none)
+extern "C" int mina_ctx_lane_streams(mina_ctx *c, uint32_t *live, uint64_t *made_by_searches) {
+    if (!c || !live || !made_by_searches) return fail(MINA_ERR_ARG, "null argument");
+    uint32_t n = 0;
+    for (int i = 0; i < MB_MAX_LANES; ++i) n += (c->lanes[i].stream ? 1u : 0u) + (c->lanes[i].aux ? 1u : 0u);
+    *live = n; *made_by_searches = c->search_streams_made;
+    return MINA_OK;
+}
+
+extern "C" int mina_ctx_search_stats(mina_ctx *c, uint64_t *searches, uint64_t *rounds, uint64_t *parts) {
+    if (!c || !searches || !rounds || !parts) return fail(MINA_ERR_ARG, "null argument");
+    *searches = c->gs_searches; *rounds = c->gs_rounds; *parts = c->gs_parts;
     return MINA_OK;
 }

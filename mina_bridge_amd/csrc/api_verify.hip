@@ -882,14 +882,28 @@ struct ShapePass {
 
     // ---------------------------------------------------------------------------------------------- collect
     int fallback(Chunk &ch) {     // a folded check of the chunk failed: per-proof verdicts through the culprit search, from the same staging
-        if (pack) {                               // ... whose records, field counts and `precheck` were made on the GPU (the chunk's job is complete: harvest waited for it)
+        // MINA_VERIFY_GROUPED_SEARCH: the search context takes the chunk's DEVICE staging -- held by the slot until this returns, complete since harvest waited for the
+        // chunk's job -- through its pointer to the shared body of mina_state_job_batch / mina_state_job_each_dev, and searches in groups of 64: no second upload,
+        // and nothing of what the GPU packed comes back to the host.  A context without the pointer keeps the host-buffer path.
+        mina_ctx *const X = tu.search_ctx ? D.sc : c;
+        const bool from_dev = (flags & MINA_VERIFY_GROUPED_SEARCH) && X->state_job_each;
+        if (pack && !from_dev) {                  // ... whose records, field counts and `precheck` were made on the GPU (the chunk's job is complete: harvest waited for it)
             uint8_t *hb_ = (uint8_t *)ch.slot->host.p; const uint8_t *db_ = ch.slot->dev.as<uint8_t>();
             HIPC(hipSetDevice(c->device));
             HIPC(hipMemcpy(hb_ + lay.off[S_REC], db_ + lay.off[S_REC], lay.off[S_EXP] - lay.off[S_REC], hipMemcpyDeviceToHost));
             HIPC(hipMemcpy(hb_ + lay.off[S_PRE], db_ + lay.off[S_PRE], ch.n * lay.stride[S_PRE], hipMemcpyDeviceToHost));
         }
-        JobStructs js; make_jobs(sh, lay, (uint8_t *)ch.slot->host.p, ch.n, true, true, true, js);
+        JobStructs js; make_jobs(sh, lay, from_dev ? ch.slot->dev.as<uint8_t>() : (uint8_t *)ch.slot->host.p, ch.n, true, true, true, js);
         std::vector<uint8_t> v(ch.n, 0);
+        // (under X's lock)  The flag asks for groups of 64 for THIS search; without it the context keeps whatever its owner set (mina_ctx_set_search_groups on the device's context)
+        auto search_job = [&]() {
+            if (!from_dev) return mina_state_job_batch(X, &js.j, v.data());
+            const uint32_t keep = X->search_groups;
+            X->search_groups = 64u;
+            const int r = X->state_job_each(X, &js.j, v.data());
+            X->search_groups = keep;
+            return r;
+        };
         const auto t = std::chrono::steady_clock::now();
         int rc;
         if (tu.search_ctx) {
@@ -912,7 +926,9 @@ struct ShapePass {
                 }
             }
             for (int q = 0; q < 3; ++q) D.sc->lanes[1 + q].stream = borrowed[q];
-            rc = mina_state_job_batch(D.sc, &js.j, v.data());
+            const uint64_t s0 = D.sc->gs_searches, r0 = D.sc->gs_rounds, p0 = D.sc->gs_parts;
+            rc = search_job();
+            { std::lock_guard<std::mutex> dl(D.mu); c->gs_searches += D.sc->gs_searches - s0; c->gs_rounds += D.sc->gs_rounds - r0; c->gs_parts += D.sc->gs_parts - p0; }      // the device's context keeps the count: mina_ctx_search_stats(mina_verify_device_ctx(i))
             for (int q = 0; q < 3; ++q) { if (D.sc->lanes[1 + q].stream) (void)hipStreamSynchronize(D.sc->lanes[1 + q].stream); D.sc->lanes[1 + q].stream = nullptr; }
         } else {
             std::lock_guard<std::mutex> lk(D.mu);
@@ -922,7 +938,7 @@ struct ShapePass {
             (void)hipSetDevice(c->device);
             if (hipDeviceSynchronize() != hipSuccess) return fail(MINA_ERR_HIP, "hipDeviceSynchronize before the culprit search");
             c->nlanes = 1;
-            rc = mina_state_job_batch(c, &js.j, v.data());
+            rc = search_job();
         }
         if (g_timing) fprintf(stderr, "mina_verify: chunk of %zu: folded check failed, culprit search %.2f ms (rc %d)\n", ch.n, ms_since(t), rc);
         if (rc) return rc;

@@ -115,6 +115,7 @@ struct Lane {
     DevBuf dd_rep, dd_uniq, dd_table, dd_counts;  // its deduplicated state leg (state_dedup.cuh): 4 B x n each, the table 16 B x the power of two >= 2 n, counters + one word per 1024 states
     DevBuf pk_off, pk_len, pk_status, pk_info, pk_fmt;   // the packed-on-device front end (state_pack.cuh; api_pack.hip): 8 B + 4 B + 1 B per state, two info structs + 1 B per proof
     DevBuf ac_ws, ac_in;                     // the device path of a Proof-of-Account job (account_pack.cuh; api_account_dev.hip): its workspace (AccountWs), the uploaded bytes + verdict words of a boundary call
+    DevBuf gs_tab, gs_folded, gs_xa, gs_xb, gs_chals, gs_points, gs_bad, gs_flags;   // the grouped culprit search (api_ipa.hip mb_*_check_parts): segment tables, one folded vector and two sums per part, the accumulator leg's challenges / checked points / per-proof malformed words, one flag per part
     DevBuf kc_state, kc_pos, kc_cip, kc_pts, kc_v, kc_u, kc_comms, kc_xfer, kc_pch, pk_xe, pk_pub, pk_ok;                  // kimchi to_batch output rows (api_kimchi.hip)
     void release_all() {
         MsmWorkspace &w = ws;
@@ -124,6 +125,7 @@ struct Lane {
                          &ipa_sigma, &ipa_in_a, &ipa_in_b, &ipa_in_c, &ipa_verdict, &ipa_xfer, &ipa_shared, &ipa_shared_off, &acc_rho_scaled,
                          &st_ok, &st_hashes, &st_pub_xyzz, &st_pubcomm, &st_flags, &st_in, &st_verdicts,
                          &dd_rep, &dd_uniq, &dd_table, &dd_counts, &pk_off, &pk_len, &pk_status, &pk_info, &pk_fmt, &ac_ws, &ac_in,
+                         &gs_tab, &gs_folded, &gs_xa, &gs_xb, &gs_chals, &gs_points, &gs_bad, &gs_flags,
                          &kc_state, &kc_pos, &kc_cip, &kc_pts, &kc_v, &kc_u, &kc_comms, &kc_xfer, &kc_pch, &pk_xe, &pk_pub, &pk_ok};
         for (DevBuf *b : all) b->release();
         host_stage.release();
@@ -170,6 +172,14 @@ struct mina_ctx {
     DevBuf acct_defaults; bool have_acct_defaults = false;
     int (*account_on_device)(mina_ctx *c, size_t n, const uint8_t *const *proofs, const size_t *proof_lens, const uint8_t *const *pubs, const size_t *pub_lens,
                              uint32_t *passed, uint32_t *ran, Lane *lane, std::mutex *enq_mu) = nullptr;
+    // The grouped culprit search of a failed job (mina_ctx_set_search_groups; api_state.hip): 0 = the fan search.  The counters of mina_ctx_search_stats follow from
+    // (batch, groups, culprits) alone: searches = legs searched in groups, rounds = levels, parts = segments checked.
+    uint32_t search_groups = 0; uint64_t gs_searches = 0, gs_rounds = 0, gs_parts = 0;
+    uint64_t search_streams_made = 0;   // streams any culprit search of this context has created (the fan search, for the lanes it lacks): mina_ctx_lane_streams
+    // mina_state_job_batch without its upload: per-proof verdicts (host bytes) of a job whose inputs are in HBM, on lane 0, waited for (api_state.hip
+    // mb_state_job_each_host).  Filled by mina_ctx_create; the boundary hands a failed chunk's device staging to it under MINA_VERIFY_GROUPED_SEARCH, and a context
+    // without it -- the stand-in contexts of the ThreadSanitizer tier -- keeps the host-buffer path.
+    int (*state_job_each)(mina_ctx *c, const mina_state_jobs *dev_jobs, uint8_t *verdicts) = nullptr;
     uint32_t dev_fork_made = 0;      // the dev_fork value the helper lanes' streams were created under (streams keep their mask / priority for life)
     void use_lane0() { L = &lanes[0]; }
     void next_lane() { L = pinned >= 0 ? &lanes[pinned] : &lanes[rr++ % (unsigned)nlanes]; }
@@ -279,6 +289,7 @@ int mb_state_frontend_on_lane(mina_ctx *c, size_t batch, const void *d_blob, siz
                               const void *d_ledger_hashes, const void *d_and, void *d_records, void *d_nfields, void *d_precheck, void *d_masks);   // api_pack.hip
 int mb_verify_account_dev_on(mina_ctx *c, size_t n, const uint8_t *const *proofs, const size_t *proof_lens, const uint8_t *const *pubs, const size_t *pub_lens,
                              uint32_t *passed, uint32_t *ran, Lane *lane, std::mutex *enq_mu);   // api_account_dev.hip: the same on the device, from the bytes as they are
+int mb_state_job_each_host(mina_ctx *c, const mina_state_jobs *dev_jobs, uint8_t *verdicts);   // api_state.hip
 int mb_state_hashes_early(mina_ctx *c, Lane *LS, size_t ns_total, size_t lo, size_t cnt, const uint32_t *d_records, const uint32_t *d_nfields, hipEvent_t after, HashLaunch hash);
 
 // ---- host-side worker pool (api_core.hip): persistent threads, created on first use -- min(hardware threads / 2, 64), $MINA_HOST_THREADS
@@ -369,6 +380,14 @@ struct IpaDevIn {     // structure-of-arrays over the batch, canonical little-en
 }
 int mb_ipa_batch_check_dev(mina_ctx *c, int curve, mb::IpaShape sh, const mb::IpaDevIn &in, uint32_t *d_verdict /* [0] verdict, [1] malformed flag */, const FoldExport *fx = nullptr);
 int mb_ipa_recheck_rows(mina_ctx *c, size_t lo, size_t cnt, uint32_t *d_verdict /* [0] verdict */);   // folded check of proofs [lo, lo + cnt) of the batch prepared last, from its rows; on the current lane
+// The grouped culprit search's checks: `np` parts [lo[p], lo[p] + cnt[p]) (host arrays, proofs) in ONE pass on the current lane -- segmented fold, the fixed-base
+// MSM with one problem per part, the segmented variable-base MSM, one comparison launch; d_flags[p] = 1 iff part p's folded check holds.  Nothing waits for the GPU.
+// rows: from the rows of the opening check prepared last (as mb_ipa_recheck_rows).  accumulator: mb_accumulator_parts_prepare once per search (challenges,
+// checked points, one malformed word per proof -- a part holding a malformed commitment fails), then any number of passes.
+int mb_ipa_recheck_rows_parts(mina_ctx *c, size_t np, const uint32_t *lo, const uint32_t *cnt, uint32_t *d_flags, size_t stage_off /* this pass's 16 * np bytes of the lane's pinned staging buffer */);
+int mb_accumulator_parts_prepare(mina_ctx *c, int curve, uint32_t k, size_t batch, const uint32_t *d_prechal, const uint32_t *d_sg_words);
+int mb_accumulator_check_parts(mina_ctx *c, int curve, uint32_t k, size_t batch, const uint32_t *d_rho, size_t np, const uint32_t *lo, const uint32_t *cnt, uint32_t *d_flags, size_t stage_off);
+size_t mb_search_parts_cap(mina_ctx *c, int curve, uint32_t k);      // parts per pass: min(128, 2^28 / (2^k * W)) for the SRS table's W windows
 int mb_accumulator_check_dev(mina_ctx *c, int curve, uint32_t k, size_t batch, const uint32_t *d_prechal, const uint32_t *d_sg_words, const uint32_t *d_rho, uint32_t *d_verdict, const FoldExport *fx = nullptr);
 
 // cross-file entry points (C++ linkage)
@@ -383,3 +402,12 @@ int mb_bpoly_single_from_prechallenges(mina_ctx *c, int field, uint32_t k, const
 int mb_bpoly_fold(mina_ctx *c, int field, uint32_t k, size_t batch, const uint32_t *d_chals, const uint32_t *d_weights, uint32_t *d_out);
 int mb_msm_variable(mina_ctx *c, int curve, uint32_t n, const uint32_t *d_scalars, const void *d_points_mont,
                     uint32_t *d_out_words, void *d_out_xyzz);
+// the segment tables of mina_msm_segments_dev / mina_b_poly_fold_segments_dev, read back on the current lane (one host wait) and checked against `limit` (api_msm.hip)
+int mb_read_segments(mina_ctx *c, size_t nseg, const void *d_begin, const void *d_end, size_t limit, uint32_t *max_len);
+// the segmented forms on the current lane, tables already checked (max_len = the longest segment); the MSM takes Montgomery affine points and writes 17-word
+// records and / or XYZZ values, one per segment.  mb_msm_segments_fit: the pipeline's limits hold for nseg segments of up to max_len entries
+bool mb_msm_segments_fit(uint32_t max_len, size_t nseg);
+int mb_msm_segments(mina_ctx *c, int curve, uint32_t n_total, size_t nseg, uint32_t max_len, const uint32_t *d_begin, const uint32_t *d_end,
+                    const uint32_t *d_scalars, const void *d_points_mont, uint32_t *d_out_words, void *d_out_xyzz);
+int mb_bpoly_fold_segments(mina_ctx *c, int field, uint32_t k, size_t batch, size_t nseg, uint32_t max_len, const uint32_t *d_begin, const uint32_t *d_end,
+                           const uint32_t *d_chals, const uint32_t *d_weights, uint32_t *d_out);

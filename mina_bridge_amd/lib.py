@@ -39,6 +39,7 @@ EXPORTS = [
     "mina_protocol_state_pack_dev", "mina_state_frontend_dev", "mina_account_frontend_dev", "mina_account_job_dev",
     "mina_state_jobs_prepare", "mina_state_job_batch_dev", "mina_state_job_batch", "mina_state_job_fold_dev",
     "mina_challenge_to_field_dev", "mina_field_sum_rows_dev", "mina_msm_srs_range_dev", "mina_msm_dev", "mina_points_sum_dev", "mina_point_records_equal_dev",
+    "mina_msm_segments_dev", "mina_b_poly_fold_segments_dev", "mina_state_job_each_dev", "mina_ctx_set_search_groups", "mina_ctx_search_stats", "mina_ctx_lane_streams",
     "mina_step_index_install", "mina_step_index_load_json", "mina_polish_tokens_from_json", "mina_verifier_index_load_json", "mina_pickles_public_input",
     "mina_verifier_index_install", "mina_verifier_index_digest", "mina_kimchi_to_batch", "mina_pickles_public_inputs_batch", "mina_wrap_proof_flatten", "mina_state_proof_split",
     "mina_verify_state", "mina_verify_state_batch", "mina_verify_state_checks", "mina_verify_state_files", "mina_verify_account", "mina_verify_account_batch",
@@ -255,6 +256,7 @@ VERIFY_ALLOW_MISSING_KIMCHI, VERIFY_ALLOW_UNBOUND_STATEMENT, VERIFY_ALLOW_SURROG
 VERIFY_DEDUP_STATES = 8   # the boundary hashes each distinct protocol state of a chunk once (MinaContext.set_state_dedup on its contexts); verdicts unchanged
 VERIFY_ACCOUNT_ON_DEVICE = 32   # verify_account / _batch / _checks upload a call's bytes as they are and run the whole Proof-of-Account job on the GPU (MinaContext.account_job_dev); verdicts unchanged
 VERIFY_PACK_ON_DEVICE = 16   # the boundary packs and pre-checks the protocol states of a chunk on the GPU (MinaContext.state_frontend_dev) instead of on its host pool; verdicts unchanged
+VERIFY_GROUPED_SEARCH = 64   # a chunk whose folded check failed is searched for its culprits in groups of 64 from its staging in HBM (MinaContext.set_search_groups, state_job_each_dev); verdicts unchanged
 
 
 def _bytes_arg(b):
@@ -1093,6 +1095,39 @@ class MinaContext:
 
     def point_records_equal_dev(self, d_a: int, d_b: int, d_verdict: int):
         self._ck(self._lib.mina_point_records_equal_dev(self._h, ctypes.c_void_p(d_a), ctypes.c_void_p(d_b), ctypes.c_void_p(d_verdict)), "mina_point_records_equal_dev")
+
+    # -- segmented building blocks (device pointers; the u32 segment tables are read back first: one wait for the lane, none for the kernels queued here)
+    def msm_segments_dev(self, curve: int, n_total: int, nseg: int, d_seg_begin: int, d_seg_end: int, d_bases: int, d_scalars: int, d_out: int):
+        """d_out[s] (68-byte record) = the MSM of points / scalars [seg_begin[s], seg_end[s]) of the two arrays: nseg variable-base MSMs in one pipeline"""
+        v = ctypes.c_void_p
+        self._ck(self._lib.mina_msm_segments_dev(self._h, curve, ctypes.c_size_t(n_total), ctypes.c_size_t(nseg), v(d_seg_begin), v(d_seg_end), v(d_bases or None),
+                                                 v(d_scalars or None), v(d_out)), "mina_msm_segments_dev")
+
+    def b_poly_fold_segments_dev(self, field: int, k: int, batch: int, nseg: int, d_seg_begin: int, d_seg_end: int, d_chals: int, d_weights: int, d_out: int):
+        """d_out[s] (2^k x 32 bytes) = sum over proofs b of segment s of weights[b] * b_poly_coefficients(chals[b]); d_weights 0 = every weight 1"""
+        v = ctypes.c_void_p
+        self._ck(self._lib.mina_b_poly_fold_segments_dev(self._h, field, ctypes.c_uint32(k), ctypes.c_size_t(batch), ctypes.c_size_t(nseg), v(d_seg_begin), v(d_seg_end),
+                                                         v(d_chals), v(d_weights or None), v(d_out)), "mina_b_poly_fold_segments_dev")
+
+    def set_search_groups(self, groups: int):
+        """the culprit search of a failed job in groups of `groups` parts per failing range on the job's own lane (2 .. 128); 0 = the fan search (default)"""
+        self._ck(self._lib.mina_ctx_set_search_groups(self._h, ctypes.c_uint32(groups)), "mina_ctx_set_search_groups")
+
+    def search_stats(self) -> dict:
+        """legs searched in groups, their rounds (levels) and parts (segments checked) since the context was created"""
+        a, b, c = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self._ck(self._lib.mina_ctx_search_stats(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)), "mina_ctx_search_stats")
+        return {"searches": a.value, "rounds": b.value, "parts": c.value}
+
+    def lane_streams(self) -> dict:
+        """test-facing: streams the context's lanes hold now, and streams its culprit searches have created so far"""
+        a, b = ctypes.c_uint32(0), ctypes.c_uint64(0)
+        self._ck(self._lib.mina_ctx_lane_streams(self._h, ctypes.byref(a), ctypes.byref(b)), "mina_ctx_lane_streams")
+        return {"live": a.value, "made_by_searches": b.value}
+
+    def state_job_each_dev(self, jobs, d_verdicts: int, d_flags: int = 0):
+        """per-proof verdicts (u32 each) of a job whose inputs are in HBM (`jobs` as for state_job_batch_dev); waits for its lane"""
+        self._ck(self._lib.mina_state_job_each_dev(self._h, ctypes.byref(jobs), ctypes.c_void_p(d_verdicts), ctypes.c_void_p(d_flags or None)), "mina_state_job_each_dev")
 
     def state_jobs_prepare(self, log2_domain: int, npub: int):
         self._ck(self._lib.mina_state_jobs_prepare(self._h, ctypes.c_uint32(log2_domain), ctypes.c_uint32(npub)), "mina_state_jobs_prepare")
