@@ -80,6 +80,15 @@ func (c *Ctx) SetSearchGroups(groups uint32) error {
 	return nil
 }
 
+// SetStreamBudget: the streams the context's pipelined device-resident jobs may keep busy (1 .. 31; <= 0: GPU_MAX_HW_QUEUES less the null stream's).  Decides
+// between a fork per lane and the shared role streams; verdicts are the same either way.  Waits for what the context has queued.
+func (c *Ctx) SetStreamBudget(n int) error {
+	if rc := C.mina_ctx_set_stream_budget(c.p, C.int(n)); rc != 0 {
+		return lastError()
+	}
+	return nil
+}
+
 // SearchStats: legs searched in groups, their rounds and the parts checked, since the context was created.
 func (c *Ctx) SearchStats() (searches, rounds, parts uint64, err error) {
 	var a, b, d C.uint64_t

@@ -566,6 +566,14 @@ int mina_ctx_search_stats(mina_ctx *ctx, uint64_t *searches, uint64_t *rounds, u
 /* Test-facing: *live = the streams the context's lanes hold now, *made_by_searches = the streams its culprit searches have created since the context was created
  * (the fan search creates the streams its lanes lack and destroys them when it is done; the grouped search creates none and queues on the job's lane only). */
 int mina_ctx_lane_streams(mina_ctx *ctx, uint32_t *live, uint64_t *made_by_searches);
+/* The streams the pipelined device-resident jobs of the context (mina_state_job_batch_dev, mina_state_job_fold_dev over mina_ctx_set_pipeline lanes) may keep busy.
+ * Streams run side by side only on separate hardware queues, and the process has GPU_MAX_HW_QUEUES of them, one of which serves the caller's null stream: the
+ * default budget is that value (1 .. 32) less one, read when the first such job is queued.  With `lanes` jobs in flight: 4 * lanes <= budget, a lone job and a
+ * pinned context fork each job's three legs onto streams of its lane (plan A); otherwise the jobs of all lanes flow FIFO through shared role streams -- one for
+ * the state hashes, and s = clamp((budget - 1) / 2, 1, lanes) pairs for the two stages of the wrap-proof chain, the accumulator check and the verdict (plan B).
+ * Verdicts are the same under every plan; mina_ctx_synchronize waits for either.  n in 1 .. 31 forces a budget (tests, tools), n <= 0 goes back to the
+ * environment's.  Waits for what the context has queued. */
+int mina_ctx_set_stream_budget(mina_ctx *ctx, int n);
 
 /* ---- multi-GPU building blocks --------------------------------------------------------------------
  * One process per GPU; RCCL moves bytes (all-to-all of scalar slices, all-gather of partial points), these entry points are the

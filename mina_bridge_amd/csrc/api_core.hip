@@ -106,7 +106,9 @@ void mb_ctx_refresh_view(mina_ctx *v, mina_ctx *p) {
 extern "C" void mina_ctx_destroy(mina_ctx *c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    for (int i = 0; i < MB_MAX_LANES; ++i) if (c->lanes[i].stream) (void)hipStreamSynchronize(c->lanes[i].stream);
+    for (int i = 0; i < MB_DEV_HELPER0; ++i) if (c->lanes[i].stream) (void)hipStreamSynchronize(c->lanes[i].stream);
+    for (hipStream_t s : c->fork_own) if (s) (void)hipStreamSynchronize(s);
+    for (hipStream_t s : c->role) if (s) (void)hipStreamSynchronize(s);
     for (int i = 0; i < 2; ++i) { c->srs[i].table.release(); c->srs[i].table29.release(); c->srs[i].table29s.release(); c->srs[i].h.release(); c->srs[i].lagrange_table.release(); c->srs[i].lagrange_digits.release(); c->srs[i].lagrange_digits29.release(); c->pparams[i].release(); c->merkle_salts[i].release(); }
     c->state_salts.release(); c->acct_defaults.release(); c->dedup_totals.release(); c->kimchi_index.release(); c->kimchi_tokens.release(); c->kimchi_literals.release();
     c->pickles_index.release(); c->pickles_tokens.release(); c->pickles_literals.release();
@@ -118,8 +120,11 @@ extern "C" void mina_ctx_destroy(mina_ctx *c) {
         Lane &L = c->lanes[i];
         if (L.aux) { (void)hipStreamSynchronize(L.aux); (void)hipStreamDestroy(L.aux); (void)hipEventDestroy(L.ev_fork); (void)hipEventDestroy(L.ev_join); }
         if (L.ev_leg) (void)hipEventDestroy(L.ev_leg);
-        if (L.stream) (void)hipStreamDestroy(L.stream);
+        if (L.ev_done) (void)hipEventDestroy(L.ev_done);
+        if (L.stream && i < MB_DEV_HELPER0) (void)hipStreamDestroy(L.stream);      // (the helper lanes of the forked jobs alias the streams below)
     }
+    for (hipStream_t s : c->fork_own) if (s) (void)hipStreamDestroy(s);
+    for (hipStream_t s : c->role) if (s) (void)hipStreamDestroy(s);
     delete c;
 }
 
@@ -134,7 +139,17 @@ __attribute__((constructor)) static void mb_default_hw_queues() { setenv("GPU_MA
 extern "C" int mina_ctx_synchronize(mina_ctx *c) {
     if (!c) return fail(MINA_ERR_ARG, "null ctx");
     HIPC(hipSetDevice(c->device));
-    for (int i = 0; i < c->nlanes; ++i) HIPC(hipStreamSynchronize(c->lanes[i].stream));
+    HIPC(mb_ctx_wait_all(c));
+    return MINA_OK;
+}
+// The streams the forked device-resident jobs of this context may keep busy (ctx.h stream_plan): n <= 0 = what the environment gives (GPU_MAX_HW_QUEUES less the
+// caller's null stream).  Tests and tools force a plan with it; waits for what is queued, so that the next job may flow through other streams.
+extern "C" int mina_ctx_set_stream_budget(mina_ctx *c, int n) {
+    if (!c) return fail(MINA_ERR_ARG, "null ctx");
+    if (n > 31) return fail(MINA_ERR_ARG, "stream budget: at most 31 (32 hardware queues less the null stream's); <= 0 = the environment's");
+    HIPC(hipSetDevice(c->device));
+    HIPC(mb_ctx_wait_all(c));
+    c->stream_budget = n > 0 ? n : 0;
     return MINA_OK;
 }
 extern "C" void *mina_ctx_stream(mina_ctx *c) { return c ? (void *)c->lanes[c->pinned >= 0 ? c->pinned : 0].stream : nullptr; }
@@ -152,7 +167,7 @@ extern "C" int mina_ctx_set_pipeline(mina_ctx *c, int lanes) {
     if (!c) return fail(MINA_ERR_ARG, "null ctx");
     if (lanes < 1 || lanes > MB_PIPE_LANES) return fail(MINA_ERR_ARG, "lanes must be in 1..32");
     HIPC(hipSetDevice(c->device));
-    for (int i = 0; i < c->nlanes; ++i) HIPC(hipStreamSynchronize(c->lanes[i].stream));
+    HIPC(mb_ctx_wait_all(c));
     for (int i = 0; i < lanes; ++i)
         if (!c->lanes[i].stream) HIPC(hipStreamCreateWithFlags(&c->lanes[i].stream, hipStreamNonBlocking));
     c->nlanes = lanes; c->rr = 0; c->pinned = -1; c->use_lane0();
@@ -246,7 +261,7 @@ extern "C" int mina_prof_enable(mina_ctx *c, int stage_mask) {
 extern "C" int mina_prof_read(mina_ctx *c, char *buf, size_t cap) {
     if (!c || !buf || cap < 8) return fail(MINA_ERR_ARG, "bad argument");
     HIPC(hipSetDevice(c->device));
-    for (int i = 0; i < c->nlanes; ++i) HIPC(hipStreamSynchronize(c->lanes[i].stream));
+    HIPC(mb_ctx_wait_all(c));
     double tot[PS_COUNT] = {0}; int cnt[PS_COUNT] = {0};
     for (size_t i = 0; i < c->prof.used; ++i) {
         float ms = 0;

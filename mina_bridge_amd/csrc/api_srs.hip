@@ -28,7 +28,7 @@ extern "C" int mina_srs_split_table(mina_ctx *c, int curve, int on) {
     SrsState &s = c->srs[curve];
     if (s.depth == 0) return fail(MINA_ERR_STATE, "SRS not loaded for this curve");
     HIPC(hipSetDevice(c->device));
-    for (int i = 0; i < c->nlanes; ++i) HIPC(hipStreamSynchronize(c->lanes[i].stream));      // an MSM in flight may be reading the table
+    HIPC(mb_ctx_wait_all(c));      // an MSM in flight may be reading the table
     if (!on) { s.table29s.release(); return MINA_OK; }
     if (s.table29s.p) return MINA_OK;
     c->use_lane0();

@@ -572,10 +572,21 @@ static int accumulator_leg(mina_ctx *c, const mina_state_jobs *j, Lane &A, const
 }
 
 // wrap-proof leg: Pickles statement -> public-input commitment -> kimchi to_batch -> combined opening check; -> v.stmt_ok, v.kimchi_bad, v.ipa_v
-static int wrap_leg(mina_ctx *c, const mina_state_jobs *j, Lane &L, const FoldExport *fx, StateJobCarry &v) {
+// stage2: under the role plan (ctx.h StreamPlan) the leg has two stages, cut in front of the opening check: everything before runs on the stream L came with
+// (W1), the opening check on `stage2` (W2), behind ONE event recorded on W1.  L.stream is `stage2` when the leg returns: whatever the caller queues on L next
+// (its join, the verdict kernel) sees both stages.
+static int wrap_leg(mina_ctx *c, const mina_state_jobs *j, Lane &L, const FoldExport *fx, StateJobCarry &v, hipStream_t stage2 = nullptr) {
     c->L = &L;
     const size_t B = j->batch;
     int rc;
+    auto to_stage2 = [&]() -> int {
+        if (!stage2 || stage2 == L.stream) return MINA_OK;
+        if (!L.ev_leg) HIPC(hipEventCreateWithFlags(&L.ev_leg, hipEventDisableTiming));
+        HIPC(hipEventRecord(L.ev_leg, L.stream));
+        HIPC(hipStreamWaitEvent(stage2, L.ev_leg, 0));
+        L.stream = stage2;
+        return MINA_OK;
+    };
     if ((rc = L.st_flags.ensure(16 * 4))) return rc;
     const uint32_t *pub = (const uint32_t *)j->public_inputs, *comm_override = nullptr;
     if (j->kimchi && j->kimchi->statements) {      // the Pickles statement -> the wrap circuit's public inputs, on this lane ahead of everything that reads them
@@ -588,7 +599,7 @@ static int wrap_leg(mina_ctx *c, const mina_state_jobs *j, Lane &L, const FoldEx
         if ((rc = mb_pubcomm_dev(c, B, j->log2_domain, j->npub, pub, L.st_pubcomm.as<uint32_t>()))) return rc;
         comm_override = L.st_pubcomm.as<uint32_t>();
     }
-    if (!j->with_ipa) return MINA_OK;
+    if (!j->with_ipa) return to_stage2();
     mb::IpaShape sh; sh.batch = (uint32_t)B; sh.k = j->k; sh.npts = j->n_evalpoints; sh.ncomms = j->n_comms; sh.per = 2 * j->k + j->n_comms + 4;
     auto W = [](const void *p) { return (const uint32_t *)p; };
     v.ipa_v = L.st_flags.as<uint32_t>() + 4;
@@ -596,6 +607,7 @@ static int wrap_leg(mina_ctx *c, const mina_state_jobs *j, Lane &L, const FoldEx
         sh.override_slot = j->npub ? j->pub_comm_slot : 0xffffffffu;
         mb::IpaDevIn in{W(j->sponge_state), W(j->sponge_pos), W(j->cip), W(j->lr), W(j->delta), W(j->sg), W(j->z1), W(j->z2), W(j->evalpoints), W(j->evalscale),
                         W(j->polyscale), W(j->comms), comm_override, W(j->rand_base), W(j->sg_rand_base)};
+        if ((rc = to_stage2())) return rc;
         return mb_ipa_batch_check_dev(c, CURVE_PALLAS, sh, in, v.ipa_v, fx);
     }
     // kimchi oracles + to_batch produce the BatchEvaluationProof rows in lane buffers (the public-input commitment is already in the list)
@@ -632,7 +644,47 @@ static int wrap_leg(mina_ctx *c, const mina_state_jobs *j, Lane &L, const FoldEx
     mb::IpaDevIn iin{out.sponge_state, out.sponge_pos, out.cip, W(j->lr), W(j->delta), W(j->sg), W(j->z1), W(j->z2), out.evalpoints, out.evalscale, out.polyscale,
                      out.comms, nullptr, W(j->rand_base), W(j->sg_rand_base)};
     iin.expand = ex;
+    if ((rc = to_stage2())) return rc;
     return mb_ipa_batch_check_dev(c, CURVE_PALLAS, sh, iin, v.ipa_v, fx);
+}
+
+// One whole job under the role plan (ctx.h StreamPlan, plan B): nothing is queued on the current pipeline lane L0 -- a wait placed on its stream would be a barrier
+// in whatever hardware queue that stream shares.  The job flows through the role streams of `plan`, FIFO behind the jobs queued before it:
+//   H:   the state hashes, then the chain check;
+//   W2:  the accumulator check (first: the order rule of mb_state_jobs_on_lane), later the second stage of the wrap-proof leg;
+//   W1:  the first stage of the wrap-proof leg, then ONE event W1 -> W2 in front of the opening check (wrap_leg);
+//   W2:  the opening check, ONE event H -> W2, the verdict kernel, and the lane's `done` event.
+// The helper lanes plan.wrap / .acc / .states lend their workspaces (each job in flight has its own: they belong to L0) and take the role's stream handle.  The
+// NEXT job of L0 reuses them: H, W1 and W2 first wait for `done` (with two or more lanes it has long completed when the wait is queued).
+// Invariant: every wait names an event recorded EARLIER in host submission order -- each record below stands above the waits on it, and `done` was recorded by the
+// lane's previous job -- and every stream is fed in host submission order.  The dependency graph is therefore ordered by submission and cannot cycle; no wait is
+// ever queued on an event before its record (L0.on_roles guards the first job of a lane).
+static int state_job_on_roles(mina_ctx *c, const mina_state_jobs *j, uint32_t *d_verdicts, uint32_t *d_flags, const StateJobPlan &plan, Lane &L0) {
+    Lane &LI = *plan.wrap, &LA = *plan.acc, &LS = *plan.states;
+    const hipStream_t H = plan.role_h, W1 = plan.role_w1, W2 = plan.role_w2;
+    int rc;
+    if (!L0.ev_done) HIPC(hipEventCreateWithFlags(&L0.ev_done, hipEventDisableTiming));
+    if (!L0.on_roles) {      // the lane's last job ran under plan A (its verdict kernel on the lane's own stream), or another entry point used the lane: behind that
+        HIPC(hipEventRecord(L0.ev_done, L0.stream));
+        L0.on_roles = true;
+    }
+    for (hipStream_t s : {H, W1, W2}) HIPC(hipStreamWaitEvent(s, L0.ev_done, 0));
+    LS.stream = H; LI.stream = W1; LA.stream = W2;
+    const size_t B = j->batch;
+    StateJobCarry v;
+    if ((rc = LS.st_ok.ensure(B * 4))) return rc;
+    if ((rc = state_leg(c, j, LS, plan))) return rc;
+    if ((rc = accumulator_leg(c, j, LA, plan.fold_export, v))) return rc;
+    if ((rc = wrap_leg(c, j, LI, plan.fold_export, v, W2))) return rc;
+    if (H != W2) {
+        if (!LS.ev_leg) HIPC(hipEventCreateWithFlags(&LS.ev_leg, hipEventDisableTiming));
+        HIPC(hipEventRecord(LS.ev_leg, H));
+        HIPC(hipStreamWaitEvent(W2, LS.ev_leg, 0));
+    }
+    mb::state_job_verdict_kernel<<<cdiv(B, 64), 64, 0, W2>>>((uint32_t)B, LS.st_ok.as<uint32_t>(), v.ipa_v, v.acc_v, v.kimchi_bad, v.stmt_ok, d_verdicts, d_flags, plan.d_stmt_out);
+    HIPC(hipGetLastError());
+    HIPC(hipEventRecord(L0.ev_done, W2));
+    return MINA_OK;
 }
 
 // One job, queued as `plan` says (ctx.h StateJobPlan) from the current lane, which keeps the fork, the joins and the verdict kernel.
@@ -648,6 +700,11 @@ int mb_state_jobs_on_lane(mina_ctx *c, const mina_state_jobs *j, uint32_t *d_ver
     struct Restore { mina_ctx *c; Lane *l0; ~Restore() { c->L = l0; } } restore{c, L0};      // the legs switch the current lane: back to the caller's on every return
     Lane *LI = L0, *LA = L0, *LS = L0;
     int rc;
+    if (plan.role_h) {
+        if (phase != MB_JOB_ALL || !plan.role_w1 || !plan.role_w2 || !plan.wrap || !plan.acc || !plan.states || plan.wrap == plan.acc || plan.wrap == plan.states || plan.acc == plan.states ||
+            plan.wrap == L0 || plan.acc == L0 || plan.states == L0) return fail(MINA_ERR_ARG, "the role plan queues whole jobs on three helper lanes");
+        return state_job_on_roles(c, j, d_verdicts, d_flags, plan, *L0);
+    }
     if (plan.wrap && plan.acc && plan.wrap != L0 && plan.acc != L0 && plan.wrap != plan.acc) {
         LI = plan.wrap; LA = plan.acc;
         if (plan.states && plan.states != L0 && plan.states != LI) LS = plan.states;      // LS == LA: the accumulator leg shares the hashes' stream (behind them, or ahead: plan.acc_first)
@@ -685,43 +742,67 @@ int mb_state_jobs_on_lane(mina_ctx *c, const mina_state_jobs *j, uint32_t *d_ver
 // then in force (a stream keeps its CU mask / priority for life).  A pinned lane (mina_ctx_pin_lane: the caller queues its own work on that lane's stream) forks as well: the legs
 // start behind an event recorded on the lane and the lane waits for them before its verdict kernel, so everything the caller queued before the call is seen by every leg and
 // everything it queues after the call sees every leg's output -- the exchange variant (mina_state_job_fold_dev under sharded.py's `ordered()` scope) keeps its ONE ordering stream.
-// Fills in the lanes, the hash launch and `acc_first` of `plan`; a job that does not fork keeps the plan as it came (everything on the current lane, one launch).
+// That is plan A of ctx.h stream_plan: 4 streams per lane, taken when they fit the context's stream budget (GPU_MAX_HW_QUEUES less the null stream's queue, or
+// mina_ctx_set_stream_budget), for a lone job and for a pinned context.  Otherwise plan B: the helper lanes lend their workspaces and the job flows through the
+// context's role streams (state_job_on_roles).  The helper lanes own no stream under either plan: their handles alias mina_ctx::fork_own / ::role.
+// Fills in the lanes, the role streams, the hash launch and `acc_first` of `plan`; a job that does not fork keeps the plan as it came (everything on the current lane, one launch).
 static int dev_fork_lanes(mina_ctx *c, size_t leg_states, StateJobPlan &plan) {
     const mina_verify_tuning tu = mb_tune();
     const int li = (int)(c->L - c->lanes);
     if (!(tu.dev_fork & 1u) || c->nlanes > MB_DEV_FORK_MAX || li < 0 || li >= MB_DEV_FORK_MAX) return MINA_OK;
     const int in_flight = c->pinned >= 0 ? 1 : c->nlanes;          // a pinned context runs one job at a time
     Lane *h = &c->lanes[MB_DEV_HELPER0 + 3 * li];
-    if (!h[0].stream || !h[1].stream || !h[2].stream) {
-        const uint32_t mode = c->dev_fork_made ? c->dev_fork_made : tu.dev_fork;
-        c->dev_fork_made = mode;
+    Lane &L0 = *c->L;
+    if (c->stream_budget_env < 0) c->stream_budget_env = env_stream_budget();
+    const StreamPlan sp = stream_plan(in_flight, c->stream_budget > 0 ? c->stream_budget : c->stream_budget_env);
+    const uint32_t mode = c->dev_fork_made ? c->dev_fork_made : tu.dev_fork;
+    c->dev_fork_made = mode;
+    int prio_lo = 0, prio_hi = 0;
+    auto make = [&](hipStream_t &st, bool chain, bool masked, int prio) -> int {
+        if (st) return MINA_OK;
         int ncu = 0; (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, c->device);
-        int prio_lo = 0, prio_hi = 0; (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);      // numerically lower = higher priority
-        auto make = [&](Lane &ln, bool chain, bool masked, int prio) -> int {
-            if (ln.stream) return MINA_OK;
-            if (masked && tu.dev_chain_cus > 0 && tu.dev_chain_cus < (uint32_t)ncu && ncu <= 256) {
-                // bit i of a mask = CU i / 8 of XCD i % 8 (tools/probes/cumask_probe.hip): the first dev_chain_cus bits are the same CUs of every XCD
-                uint32_t mk[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-                for (uint32_t b2 = 0; b2 < (uint32_t)ncu; ++b2) if ((b2 < tu.dev_chain_cus) == chain) mk[b2 >> 5] |= 1u << (b2 & 31);
-                if (hipExtStreamCreateWithCUMask(&ln.stream, 8, mk) == hipSuccess) return MINA_OK;
-                (void)hipGetLastError(); ln.stream = nullptr;
-            }
-            if (prio_lo != prio_hi && (mode & 4u)) HIPC(hipStreamCreateWithPriority(&ln.stream, hipStreamNonBlocking, prio));
-            else HIPC(hipStreamCreateWithFlags(&ln.stream, hipStreamNonBlocking));
-            return MINA_OK;
-        };
-        int rc;
-        if ((rc = make(h[0], true, (mode & 2u) != 0, prio_hi)) || (rc = make(h[1], true, false, (prio_lo + prio_hi) / 2)) || (rc = make(h[2], false, (mode & 2u) != 0, prio_lo))) return rc;
+        if (masked && tu.dev_chain_cus > 0 && tu.dev_chain_cus < (uint32_t)ncu && ncu <= 256) {
+            // bit i of a mask = CU i / 8 of XCD i % 8 (tools/probes/cumask_probe.hip): the first dev_chain_cus bits are the same CUs of every XCD
+            uint32_t mk[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+            for (uint32_t b2 = 0; b2 < (uint32_t)ncu; ++b2) if ((b2 < tu.dev_chain_cus) == chain) mk[b2 >> 5] |= 1u << (b2 & 31);
+            if (hipExtStreamCreateWithCUMask(&st, 8, mk) == hipSuccess) return MINA_OK;
+            (void)hipGetLastError(); st = nullptr;
+        }
+        if (prio_lo != prio_hi && (mode & 4u)) HIPC(hipStreamCreateWithPriority(&st, hipStreamNonBlocking, prio));
+        else HIPC(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        return MINA_OK;
+    };
+    int rc;
+    if (sp.roles) {
+        // plan B: the role streams are the context's, created once (H at the hashes' priority, the chain streams at the chain's; no CU masks: a role serves every job)
+        if (!c->role[sp.streams - 1]) (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);      // numerically lower = higher priority
+        for (int i = 0; i < sp.streams; ++i) if ((rc = make(c->role[i], true, false, (i == 0 && sp.streams > 1) ? prio_lo : prio_hi))) return rc;
+        plan.role_h = c->role[0]; plan.role_w1 = c->role[sp.w1(li)]; plan.role_w2 = c->role[sp.w2(li)];
+        plan.wrap = &h[0]; plan.acc = &h[1]; plan.states = &h[2];
+    } else {
+        hipStream_t *own = &c->fork_own[3 * li];
+        if (!own[0] || !own[1] || !own[2]) {
+            (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);
+            if ((rc = make(own[0], true, (mode & 2u) != 0, prio_hi)) || (rc = make(own[1], true, false, (prio_lo + prio_hi) / 2)) || (rc = make(own[2], false, (mode & 2u) != 0, prio_lo))) return rc;
+        }
+        for (int q = 0; q < 3; ++q) h[q].stream = own[q];
+        if (L0.on_roles) {      // the lane's last job ran under plan B: its helper lanes' workspaces are free behind that job's `done` event
+            HIPC(hipStreamWaitEvent(L0.stream, L0.ev_done, 0));
+            L0.on_roles = false;
+        }
+        plan.wrap = &h[0]; plan.acc = tu.dev_acc_lane ? &h[2] : &h[1]; plan.states = &h[2];      // dev_acc_lane: the accumulator leg on the hashes' stream (1: behind them, 2: ahead)
+        plan.acc_first = tu.dev_acc_lane == 2;
     }
-    plan.wrap = &h[0]; plan.acc = tu.dev_acc_lane ? &h[2] : &h[1]; plan.states = &h[2];      // dev_acc_lane: the accumulator leg on the hashes' stream (1: behind them, 2: ahead)
-    plan.acc_first = tu.dev_acc_lane == 2;
     // The hashes of a forked job go out in pieces, so that the jobs in flight together ask for ~6 state-hash waves per SIMD (five fit beside nothing else, 96 VGPRs):
     // measured with the wave priorities on (lanes x piece grid at 4096 / 8192 / 16 384 proofs per call, profiles/r06_dev_fork.md) the best piece is ~6144 / lanes waves
     // whatever the call size -- 2 lanes 3072, 3: 2048, 4: 1536, 6: 1024 -- and a lone call is best left whole.  The single-lane form (ctx.h hash_one_lane) wants twice
     // as many of its waves of 64 states (profiles/r07_one_lane_hash.md, 4 lanes: 768 / 1536 / 3072 waves 253 / 262 / 282 k proofs/s; pieces of the 3-lane form's
     // states, 21 per wave, left a lone wave on half the SIMDs: -13 % on the step).
+    // Under the role plan H holds nothing but hashes, one launch behind the other: a piece only leaves wave slots idle until the next one starts, and the leg is
+    // best left whole (4 lanes at budget 3, one run each: pieces of 3072 waves 265 k proofs/s, the whole leg of 4352 waves 283 k; profiles/r08_role_streams.md).
+    // Under plan A one size above 3072 was tried as well: the whole leg, 315 k against 318 - 321 k -- the default stays.
     uint32_t piece = tu.dev_piece_waves;
-    if (piece == 0 && in_flight >= 2) piece = (hash_one_lane(c, leg_states) ? 12288u : 6144u) / (uint32_t)in_flight;
+    if (piece == 0 && in_flight >= 2 && !sp.roles) piece = (hash_one_lane(c, leg_states) ? 12288u : 6144u) / (uint32_t)in_flight;
     if (piece == 0xffffffffu) piece = 0;
     plan.hash.piece_waves = piece;
     // A lone forked job: its hashes would hold every wave slot their 96 VGPRs allow (5 per SIMD) and the chain's waves would wait for one to retire (~13 ms): the
@@ -1027,7 +1108,9 @@ extern "C" int mina_ctx_set_search_groups(mina_ctx *c, uint32_t groups) {
 extern "C" int mina_ctx_lane_streams(mina_ctx *c, uint32_t *live, uint64_t *made_by_searches) {
     if (!c || !live || !made_by_searches) return fail(MINA_ERR_ARG, "null argument");
     uint32_t n = 0;
-    for (int i = 0; i < MB_MAX_LANES; ++i) n += (c->lanes[i].stream ? 1u : 0u) + (c->lanes[i].aux ? 1u : 0u);
+    for (int i = 0; i < MB_MAX_LANES; ++i) n += ((c->lanes[i].stream && i < MB_DEV_HELPER0) ? 1u : 0u) + (c->lanes[i].aux ? 1u : 0u);      // (the forked jobs' helper lanes alias the streams below)
+    for (hipStream_t s : c->fork_own) n += s ? 1u : 0u;
+    for (hipStream_t s : c->role) n += s ? 1u : 0u;
     *live = n; *made_by_searches = c->search_streams_made;
     return MINA_OK;
 }

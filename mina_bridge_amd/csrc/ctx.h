@@ -106,6 +106,7 @@ struct Lane {
     hipStream_t stream = nullptr;
     hipStream_t aux = nullptr;               // second stream for work that can run beside the lane's main stream (IPA to_group)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_leg = nullptr;   // ev_leg: fork / join of the Proof-of-State job's legs
+    hipEvent_t ev_done = nullptr; bool on_roles = false;                 // a pipeline lane under the role plan (api_state.hip state_job_on_roles): recorded behind the verdict kernel of the lane's last job; on_roles: that job ran on the role streams
     MsmWorkspace ws;
     DevBuf tmp_a, tmp_b, tmp_c, tmp_d;       // staging for the host-buffer entry points
     PinnedBuf host_stage;                    // pinned host side of the big H2D blobs (synchronous entry points only)
@@ -131,9 +132,40 @@ struct Lane {
         host_stage.release();
     }
 };
+// ---- how the legs of pipelined device-resident jobs are laid over streams (api_state.hip dev_fork_lanes).  Streams only run side by side on separate hardware
+// queues, a stream's event wait is a barrier in the queue it shares, and the process has GPU_MAX_HW_QUEUES of them, one of which serves the caller's null stream:
+// `budget` = the streams the context may keep busy.  Pure: no HIP call.
+//   plan A (roles = false): every pipeline lane forks its job's three legs onto helper streams of its own, 4 streams per lane -- when they fit the budget, and
+//     always for a lone job (one lane, or a pinned context).
+//   plan B (roles = true): the jobs of all lanes flow FIFO through shared ROLE streams: H (every job's state hashes and chain check) and `sets` pairs W1[j] / W2[j]
+//     for the jobs of the lanes with lane % sets == j (W1: Pickles statement -> public-input commitment -> kimchi to_batch; W2: accumulator check, opening check,
+//     verdict kernel): 1 + 2 sets streams, sets = clamp((budget - 1) / 2, 1, lanes).  A budget below 3 cannot hold the three roles apart: W1 and W2 of the one
+//     set share a stream at 2, and H joins them at 1 (or less), so that the plan never keeps more than max(budget, 1) streams busy.
+struct StreamPlan {
+    bool roles = false; int sets = 0, streams = 0;            // streams: the role streams of plan B (index 0 = H); 0 under plan A
+    int w1(int lane) const { return streams >= 3 ? 1 + 2 * (lane % sets) : streams - 1; }
+    int w2(int lane) const { return streams >= 3 ? 2 + 2 * (lane % sets) : streams - 1; }
+};
+static inline StreamPlan stream_plan(int lanes_in_flight, int budget) {
+    StreamPlan p;
+    if (lanes_in_flight <= 1 || 4 * lanes_in_flight <= budget) return p;
+    p.roles = true;
+    p.sets = std::min(std::max((budget - 1) / 2, 1), lanes_in_flight);
+    p.streams = std::min(1 + 2 * p.sets, std::max(budget, 1));
+    return p;
+}
+// GPU_MAX_HW_QUEUES as the process has it (the library's load-time constructor sets a default where it is unset: api_core.hip), 1 .. 32, less the caller's null stream
+static inline int env_stream_budget() {
+    const char *e = getenv("GPU_MAX_HW_QUEUES");
+    const long q = e ? strtol(e, nullptr, 10) : 4;
+    return (int)std::min(std::max(q, 1L), 32L) - 1;
+}
 static constexpr int MB_PIPE_LANES = 32;                   // lanes a caller may pipeline over (mina_ctx_set_pipeline) = the fan-out of the culprit search
 static constexpr int MB_DEV_FORK_MAX = 8;                  // pipelines of up to this many lanes fork the legs of a device-resident job (mina_verify_tuning.dev_fork)
+static constexpr int MB_ROLE_STREAMS = 1 + 2 * MB_DEV_FORK_MAX;      // H + a W1 / W2 pair per lane at the most (StreamPlan)
 static constexpr int MB_DEV_HELPER0 = MB_PIPE_LANES + 3 * 16;   // helper lanes of pipeline lane i: MB_DEV_HELPER0 + 3 i .. (wrap-proof chain / accumulator / state hashes)
+// The helper lanes of the forked device-resident jobs own NO stream: their `stream` is an alias of one of the context's fork streams (mina_ctx::fork_own, plan A)
+// or role streams (mina_ctx::role, plan B), which the context creates and destroys once.
 static constexpr int MB_MAX_LANES = MB_DEV_HELPER0 + 3 * MB_DEV_FORK_MAX;  // pipeline lanes + the helper lanes of the boundary's 16 slots (api_verify.hip: legs of slot s on lanes 32 + 3 s ..) + those of the forked device-resident jobs
 enum : int { MB_SALT_PSTATE_BODY = 0, MB_SALT_PSTATE, MB_SALT_ACCOUNT, MB_SALT_ZKAPP_ACCOUNT, MB_SALT_ZKAPP_URI, MB_SALT_SIDE_LOADED_VK, MB_N_PREFIX_SALTS };
 
@@ -181,15 +213,26 @@ struct mina_ctx {
     // without it -- the stand-in contexts of the ThreadSanitizer tier -- keeps the host-buffer path.
     int (*state_job_each)(mina_ctx *c, const mina_state_jobs *dev_jobs, uint8_t *verdicts) = nullptr;
     uint32_t dev_fork_made = 0;      // the dev_fork value the helper lanes' streams were created under (streams keep their mask / priority for life)
+    // The streams behind the helper lanes of the forked jobs (StreamPlan), created on first use, destroyed once by mina_ctx_destroy: plan A's, three per pipeline
+    // lane, and plan B's role streams.  stream_budget: forced by mina_ctx_set_stream_budget (> 0), else the environment's, read when the first job forks (-1: not yet).
+    hipStream_t fork_own[3 * MB_DEV_FORK_MAX] = {}; hipStream_t role[MB_ROLE_STREAMS] = {};
+    int stream_budget = 0, stream_budget_env = -1;
     void use_lane0() { L = &lanes[0]; }
     void next_lane() { L = pinned >= 0 ? &lanes[pinned] : &lanes[rr++ % (unsigned)nlanes]; }
 };
+
+// waits for everything the `_dev` entry points have queued: the pipeline lanes and, for jobs that ran under plan B, the role streams
+static inline hipError_t mb_ctx_wait_all(mina_ctx *c) {
+    for (int i = 0; i < c->nlanes; ++i) if (c->lanes[i].stream) { hipError_t e = hipStreamSynchronize(c->lanes[i].stream); if (e != hipSuccess) return e; }
+    for (hipStream_t s : c->role) if (s) { hipError_t e = hipStreamSynchronize(s); if (e != hipSuccess) return e; }
+    return hipSuccess;
+}
 
 // mina_ctx_set_state_dedup without the argument checks (the boundary switches its contexts under their lock: api_verify.hip finish()).  The statistics start
 // again whenever the mode goes from off to on; that waits for the pipeline lanes.
 static inline int mb_ctx_state_dedup(mina_ctx *c, bool on) {
     if (on && !c->state_dedup) {
-        for (int i = 0; i < c->nlanes; ++i) if (c->lanes[i].stream && hipStreamSynchronize(c->lanes[i].stream) != hipSuccess) return MINA_ERR_HIP;
+        if (mb_ctx_wait_all(c) != hipSuccess) return MINA_ERR_HIP;
         int rc = c->dedup_totals.ensure(16);
         if (rc) return rc;
         if (hipMemsetAsync(c->dedup_totals.p, 0, 16, c->lanes[0].stream) != hipSuccess || hipStreamSynchronize(c->lanes[0].stream) != hipSuccess) return MINA_ERR_HIP;
@@ -280,6 +323,7 @@ struct StateJobPlan {
     size_t hashed_early = 0;                                    // states of the protocol-state leg already queued on its lane by mb_state_hashes_early
     HashLaunch hash;
     bool acc_first = false;                                     // the accumulator leg shares the hashes' lane: queue it AHEAD of them (mina_verify_tuning.dev_acc_lane = 2)
+    hipStream_t role_h = nullptr, role_w1 = nullptr, role_w2 = nullptr;   // plan B (StreamPlan): the role streams this job flows through; wrap / acc / states lend their workspaces
     const FoldExport *fold_export = nullptr;
 };
 int mb_state_jobs_on_lane(mina_ctx *c, const mina_state_jobs *j, uint32_t *d_verdicts, uint32_t *d_flags, const StateJobPlan &plan = {});

@@ -39,7 +39,7 @@ EXPORTS = [
     "mina_protocol_state_pack_dev", "mina_state_frontend_dev", "mina_account_frontend_dev", "mina_account_job_dev",
     "mina_state_jobs_prepare", "mina_state_job_batch_dev", "mina_state_job_batch", "mina_state_job_fold_dev",
     "mina_challenge_to_field_dev", "mina_field_sum_rows_dev", "mina_msm_srs_range_dev", "mina_msm_dev", "mina_points_sum_dev", "mina_point_records_equal_dev",
-    "mina_msm_segments_dev", "mina_b_poly_fold_segments_dev", "mina_state_job_each_dev", "mina_ctx_set_search_groups", "mina_ctx_search_stats", "mina_ctx_lane_streams",
+    "mina_msm_segments_dev", "mina_b_poly_fold_segments_dev", "mina_state_job_each_dev", "mina_ctx_set_search_groups", "mina_ctx_search_stats", "mina_ctx_lane_streams", "mina_ctx_set_stream_budget",
     "mina_step_index_install", "mina_step_index_load_json", "mina_polish_tokens_from_json", "mina_verifier_index_load_json", "mina_pickles_public_input",
     "mina_verifier_index_install", "mina_verifier_index_digest", "mina_kimchi_to_batch", "mina_pickles_public_inputs_batch", "mina_wrap_proof_flatten", "mina_state_proof_split",
     "mina_verify_state", "mina_verify_state_batch", "mina_verify_state_checks", "mina_verify_state_files", "mina_verify_account", "mina_verify_account_batch",
@@ -1124,6 +1124,10 @@ class MinaContext:
         a, b = ctypes.c_uint32(0), ctypes.c_uint64(0)
         self._ck(self._lib.mina_ctx_lane_streams(self._h, ctypes.byref(a), ctypes.byref(b)), "mina_ctx_lane_streams")
         return {"live": a.value, "made_by_searches": b.value}
+
+    def set_stream_budget(self, n: int):
+        """streams the pipelined device-resident jobs may keep busy (1 .. 31: forces the stream plan; <= 0: GPU_MAX_HW_QUEUES less the null stream's); waits for what is queued"""
+        self._ck(self._lib.mina_ctx_set_stream_budget(self._h, ctypes.c_int(n)), "mina_ctx_set_stream_budget")
 
     def state_job_each_dev(self, jobs, d_verdicts: int, d_flags: int = 0):
         """per-proof verdicts (u32 each) of a job whose inputs are in HBM (`jobs` as for state_job_batch_dev); waits for its lane"""
