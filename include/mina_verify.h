@@ -586,7 +586,10 @@ int mina_field_sum_rows_dev(mina_ctx *ctx, int field, size_t rows, size_t m, con
 int mina_msm_srs_range_dev(mina_ctx *ctx, int curve, uint32_t first, size_t n, const void *d_scalars, void *d_out /* record */);
 /* variable-base MSM over canonical affine points in HBM */
 int mina_msm_dev(mina_ctx *ctx, int curve, size_t n, const void *d_bases /* n*64 */, const void *d_scalars /* n*32 */, void *d_out /* record */);
-/* sum of n point records (the all-gathered partial results) */
+/* sum of n point records (the all-gathered partial results).  Record contract of this call and of mina_point_records_equal_dev: a record whose flag word is
+ * != 0 (any non-zero value, not only 1) is the point at infinity and its 64 coordinate bytes are ignored, whatever they hold; a record whose flag word is 0 holds
+ * canonical affine coordinates.  The sum skips infinity records; the comparison calls two infinity records equal and a finite record unequal to an infinity
+ * record, and writes the verdict word 1 or 0 over whatever it held.  Records written here are canonical: infinity is 64 zero bytes and the word 1. */
 int mina_points_sum_dev(mina_ctx *ctx, int curve, size_t n, const void *d_records /* n*68 */, void *d_out /* record */);
 int mina_point_records_equal_dev(mina_ctx *ctx, const void *d_a, const void *d_b, void *d_verdict /* u32 */);
 /* ---- segmented building blocks: many independent sums over ranges of ONE input array, in one launch set -------------

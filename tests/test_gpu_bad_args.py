@@ -155,3 +155,56 @@ def test_statement_and_kimchi_sections_reject_bad_shapes(oracle):
         assert (pub2 == pub).all() and ok2.tolist() == [1]
     finally:
         c.close()
+
+
+def test_exchange_building_blocks_refuse_bad_shapes_and_null_pointers(ctx_srs):
+    """the reduction operators of the multi-GPU exchange step (api_shard.hip): a shape outside the documented limits, a base range past the SRS or a null pointer
+    is MINA_ERR_ARG before anything is queued, and the context computes afterwards"""
+    c = ctx_srs
+    lib, h = c._lib, c._h
+    v, z, u32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32
+    d = c.dev_malloc(4096)
+    try:
+        def sum_rows(ctx_h=h, field=0, rows=2, m=3, d_in=d, d_out=d + 2048):
+            return lib.mina_field_sum_rows_dev(ctx_h, field, z(rows), z(m), v(d_in), v(d_out))
+        for kw in ({"rows": 0}, {"rows": 4097}, {"m": 0}, {"m": (1 << 24) + 1}, {"field": 2}, {"ctx_h": None}, {"d_in": None}, {"d_out": None}):
+            assert sum_rows(**kw) == MINA_ERR_ARG, kw
+
+        def points_sum(ctx_h=h, curve=1, n=2, recs=d, out=d + 2048):
+            return lib.mina_points_sum_dev(ctx_h, curve, z(n), v(recs), v(out))
+        for kw in ({"n": 0}, {"n": 65537}, {"curve": 2}, {"ctx_h": None}, {"recs": None}, {"out": None}):
+            assert points_sum(**kw) == MINA_ERR_ARG, kw
+
+        def srs_range(ctx_h=h, curve=1, first=0, n=4, sc=d, out=d + 2048):
+            return lib.mina_msm_srs_range_dev(ctx_h, curve, u32(first), z(n), v(sc), v(out))
+        assert c.srs_depth(1) == 65536
+        for kw in ({"first": 65536, "n": 1}, {"first": 65535, "n": 2}, {"first": 65533}, {"first": 1, "n": 65536}, {"first": 0xFFFFFFFF, "n": 2}, {"n": 65537}, {"n": 0},
+                   {"n": 1 << 32}, {"curve": 2}, {"ctx_h": None}, {"sc": None}, {"out": None}):
+            assert srs_range(**kw) == MINA_ERR_ARG, kw
+        assert b"SRS" in lib.mina_last_error() or b"null" in lib.mina_last_error()
+
+        def to_field(ctx_h=h, field=0, n=4, ch=d, out=d + 2048):
+            return lib.mina_challenge_to_field_dev(ctx_h, field, z(n), v(ch), v(out))
+        for kw in ({"field": 2}, {"ctx_h": None}, {"ch": None}, {"out": None}):
+            assert to_field(**kw) == MINA_ERR_ARG, kw
+
+        def equal(ctx_h=h, a=d, b=d + 1024, verdict=d + 2048):
+            return lib.mina_point_records_equal_dev(ctx_h, v(a), v(b), v(verdict))
+        for kw in ({"ctx_h": None}, {"a": None}, {"b": None}, {"verdict": None}):
+            assert equal(**kw) == MINA_ERR_ARG, kw
+
+        # and the context still computes: (p - 1) + 2 = 1 in Fp, one point summed is itself, it equals itself
+        p = 0x40000000000000000000000000000000224698FC094CF91B992D30ED00000001
+        c.dev_upload(d, np.frombuffer((p - 1).to_bytes(32, "little") + (2).to_bytes(32, "little"), np.uint8))
+        assert sum_rows(rows=2, m=1) == 0
+        assert c.dev_download(d + 2048, 32).tobytes() == (1).to_bytes(32, "little")
+        rec = np.concatenate([c.srs_get_g(1, 7, 1)[0], np.zeros(4, np.uint8)])
+        c.dev_upload(d, rec)
+        assert points_sum(n=1) == 0
+        assert c.dev_download(d + 2048, 68).tobytes() == rec.tobytes()
+        c.dev_upload(d + 3072, np.full(4, 0xFF, np.uint8))
+        assert equal(a=d, b=d + 2048, verdict=d + 3072) == 0
+        assert c.dev_download(d + 3072, 4).tobytes() == (1).to_bytes(4, "little")
+    finally:
+        c.synchronize()
+        c.dev_free(d)

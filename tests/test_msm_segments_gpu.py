@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 from conftest import rand_scalars
+from dev_helpers import Dev, record_to_affine
 
 pytestmark = pytest.mark.gpu
 
@@ -27,46 +28,11 @@ def points(oracle):
     return {c: oracle.srs_create(c, NPTS, threads=4)[0] for c in (0, 1)}
 
 
-class Dev:
-    """device arrays of one test, freed at its end"""
-
-    def __init__(self, ctx):
-        self.ctx, self.ptrs = ctx, []
-
-    def put(self, a) -> int:
-        a = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
-        p = self.ctx.dev_malloc(max(a.size, 16))
-        self.ptrs.append(p)
-        if a.size:
-            self.ctx.dev_upload(p, a)
-        return p
-
-    def alloc(self, n) -> int:
-        p = self.ctx.dev_malloc(max(n, 16))
-        self.ptrs.append(p)
-        return p
-
-    def get(self, p, n):
-        self.ctx.synchronize()
-        return self.ctx.dev_download(p, n)
-
-    def close(self):
-        self.ctx.synchronize()
-        for p in self.ptrs:
-            self.ctx.dev_free(p)
-
-
 @pytest.fixture
 def dev(ctx):
     d = Dev(ctx)
     yield d
     d.close()
-
-
-def record_to_affine(rec):
-    """68-byte record -> the 64 bytes mina_msm returns (zeros at infinity)"""
-    rec = np.asarray(rec, np.uint8)
-    return np.zeros(64, np.uint8) if rec[64:68].any() else rec[:64].copy()
 
 
 def msm_segments(ctx, dev, curve, bases, scalars, segs):
