@@ -106,7 +106,7 @@ struct Lane {
     hipStream_t stream = nullptr;
     hipStream_t aux = nullptr;               // second stream for work that can run beside the lane's main stream (IPA to_group)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr, ev_leg = nullptr;   // ev_leg: fork / join of the Proof-of-State job's legs
-    hipEvent_t ev_done = nullptr; bool on_roles = false;                 // a pipeline lane under the role plan (api_state.hip state_job_on_roles): recorded behind the verdict kernel of the lane's last job; on_roles: that job ran on the role streams
+    hipEvent_t ev_done = nullptr; bool on_roles = false;                 // a pipeline lane under the role plan (state_job.hip JobRoute): recorded behind the verdict kernel of the lane's last job; on_roles: that job ran on the role streams
     MsmWorkspace ws;
     DevBuf tmp_a, tmp_b, tmp_c, tmp_d;       // staging for the host-buffer entry points
     PinnedBuf host_stage;                    // pinned host side of the big H2D blobs (synchronous entry points only)
@@ -132,7 +132,7 @@ struct Lane {
         host_stage.release();
     }
 };
-// ---- how the legs of pipelined device-resident jobs are laid over streams (api_state.hip dev_fork_lanes).  Streams only run side by side on separate hardware
+// ---- how the legs of pipelined device-resident jobs are laid over streams (state_job.hip dev_fork_lanes).  Streams only run side by side on separate hardware
 // queues, a stream's event wait is a barrier in the queue it shares, and the process has GPU_MAX_HW_QUEUES of them, one of which serves the caller's null stream:
 // `budget` = the streams the context may keep busy.  Pure: no HIP call.
 //   plan A (roles = false): every pipeline lane forks its job's three legs onto helper streams of its own, 4 streams per lane -- when they fit the budget, and
@@ -305,7 +305,7 @@ static inline int sponge_batch_lanes(size_t n) { return n <= COOP8_MAX_GROUPS ? 
 // the Merkle fold (api_sponge.hip mb_merkle_fold_dev): a few paths take 16 lanes each (use_coop16), the rest as sponge_batch_lanes
 static inline int merkle_lanes(const mina_ctx *c, size_t paths) { return use_coop16(c, paths) ? 16 : sponge_batch_lanes(paths); }
 
-// ---- the Proof-of-State job on the lanes of a context (api_state.hip); every pointer of `j` is a device pointer
+// ---- the Proof-of-State job on the lanes of a context (state_job.hip); every pointer of `j` is a device pointer
 enum : uint32_t { MB_JOB_LEGS = 1, MB_JOB_FINISH = 2, MB_JOB_ALL = 3 };
 struct StateJobCarry { uint32_t *ipa_v = nullptr, *acc_v = nullptr, *kimchi_bad = nullptr; const uint32_t *stmt_ok = nullptr; };
 // How the protocol-state hashes of a leg are launched (api_state.hip pstate_hash_launch).  piece_waves > 0: in pieces of this many waves of the form that runs
@@ -315,17 +315,19 @@ struct HashLaunch { uint32_t piece_waves = 0, lds_bytes = 0; };
 // SURVEY.md 8e.2 (one exchange step over several GPUs): given one, the folded checks of a job do NOT run their fixed-base MSM and comparison -- they hand out
 // this shard's folded scalar vector and the 17-word record of its variable-base partial sum instead (mina_state_job_fold_dev); device pointers
 struct FoldExport { uint32_t *ipa_scalars = nullptr, *ipa_point = nullptr, *acc_scalars = nullptr, *acc_point = nullptr; };
-// How ONE job is queued: decided by the caller (api_state.hip dev_fork_lanes, the boundary's chunks in api_verify.hip), read by mb_state_jobs_on_lane and its legs.
+// How ONE job is queued: decided by the caller (state_job.hip dev_fork_lanes, the boundary's chunks in api_verify.hip), read by mb_state_jobs_on_lane and its legs.
 struct StateJobPlan {
     Lane *wrap = nullptr, *acc = nullptr, *states = nullptr;   // helper lanes of the wrap-proof / accumulator / protocol-state legs; null = the current lane
     uint32_t phase = MB_JOB_ALL; StateJobCarry *carry = nullptr;
     uint32_t *d_stmt_out = nullptr;                             // [batch] or null: the per-proof "Pickles statement well-formed" words
     size_t hashed_early = 0;                                    // states of the protocol-state leg already queued on its lane by mb_state_hashes_early
     HashLaunch hash;
-    bool acc_first = false;                                     // the accumulator leg shares the hashes' lane: queue it AHEAD of them (mina_verify_tuning.dev_acc_lane = 2)
-    hipStream_t role_h = nullptr, role_w1 = nullptr, role_w2 = nullptr;   // plan B (StreamPlan): the role streams this job flows through; wrap / acc / states lend their workspaces
     const FoldExport *fold_export = nullptr;
+    const struct LegStreams *lent = nullptr;                    // device-resident jobs only (state_job.hip dev_fork_lanes): the streams lent to wrap / acc / states for this job
 };
+// What dev_fork_lanes lends the helper lanes of a device-resident job, which own no stream: plan A's three of the pipeline lane, or plan B's roles (StreamPlan:
+// wrap = W1, acc = W2, states = H).  acc_first: the accumulator leg shares the hashes' lane and goes AHEAD of them (mina_verify_tuning.dev_acc_lane = 2).
+struct LegStreams { hipStream_t wrap = nullptr, acc = nullptr, states = nullptr; bool roles = false, acc_first = false; };
 int mb_state_jobs_on_lane(mina_ctx *c, const mina_state_jobs *j, uint32_t *d_verdicts, uint32_t *d_flags, const StateJobPlan &plan = {});
 int mb_verify_account_on(mina_ctx *c, size_t n, const uint8_t *const *proofs, const size_t *proof_lens, const uint8_t *const *pubs, const size_t *pub_lens,
                          uint32_t *passed, uint32_t *ran, Lane *lane, std::mutex *enq_mu);   // api_account.hip: Proof-of-Account on a lane of the caller's choice
@@ -334,7 +336,20 @@ int mb_state_frontend_on_lane(mina_ctx *c, size_t batch, const void *d_blob, siz
 int mb_verify_account_dev_on(mina_ctx *c, size_t n, const uint8_t *const *proofs, const size_t *proof_lens, const uint8_t *const *pubs, const size_t *pub_lens,
                              uint32_t *passed, uint32_t *ran, Lane *lane, std::mutex *enq_mu);   // api_account_dev.hip: the same on the device, from the bytes as they are
 int mb_state_job_each_host(mina_ctx *c, const mina_state_jobs *dev_jobs, uint8_t *verdicts);   // api_state.hip
-int mb_state_hashes_early(mina_ctx *c, Lane *LS, size_t ns_total, size_t lo, size_t cnt, const uint32_t *d_records, const uint32_t *d_nfields, hipEvent_t after, HashLaunch hash);
+int mb_state_hashes_early(mina_ctx *c, Lane *LS, size_t ns_total, size_t lo, size_t cnt, const uint32_t *d_records, const uint32_t *d_nfields, hipEvent_t after, HashLaunch hash);   // state_job.hip
+// The device layer under state_job.hip, defined where the kernels are (api_state.hip): the argument checks of a job, the state hashes of a leg on the current
+// lane (plain, or each distinct record once), and one launch function per kernel the legs launch themselves -- the same grid and block on the stream given, nothing else.
+int mb_check_jobs(mina_ctx *c, const mina_state_jobs *j);
+int pstate_hash_dev(mina_ctx *c, size_t n, size_t leg, HashLaunch hl, const uint32_t *d_records, const uint32_t *d_nfields, uint32_t *d_hashes, uint32_t *d_bodies);
+int pstate_hash_dedup_dev(mina_ctx *c, size_t n, size_t leg, HashLaunch hl, const uint32_t *d_records, const uint32_t *d_nfields, uint32_t *d_hashes, uint32_t *d_bodies, bool count);
+void mb_launch_pstate_chain_check(hipStream_t stream, uint32_t batch, const uint32_t *hashes, const uint32_t *expected, const uint32_t *records, const uint8_t *precheck, uint32_t *ok);
+void mb_launch_fill_u32(hipStream_t stream, uint32_t n, uint32_t v, uint32_t *out);
+void mb_launch_state_job_verdict(hipStream_t stream, uint32_t batch, const uint32_t *chain_ok, const uint32_t *ipa_v, const uint32_t *acc_v, const uint32_t *kimchi_bad,
+                                 const uint32_t *stmt_ok, uint32_t *verdicts, uint32_t *flags, uint32_t *stmt_out);
+void mb_launch_challenge_to_field_fq(hipStream_t stream, uint32_t n, FieldK fk, const uint32_t *chal, uint32_t *out_words);
+int mb_pubcomm_dev(mina_ctx *c, size_t batch, uint32_t log2_domain, uint32_t npub, const uint32_t *d_pub, uint32_t *d_out16);      // api_state.hip
+int mb_pickles_statements_dev(mina_ctx *c, size_t batch, const mina_pickles_statements *s, uint32_t *d_pub, uint32_t *d_ok);      // api_pickles.hip
+void mb_pickles_kimchi_digest(mina_ctx *c, const mina_pickles_statements *s, const void **first, uint32_t *stride);
 
 // ---- host-side worker pool (api_core.hip): persistent threads, created on first use -- min(hardware threads / 2, 64), $MINA_HOST_THREADS
 // overrides.  A job is `n` independent items handed out in index order; `mb_pool_submit` returns at once (the boundary's pipeline parses

@@ -39,8 +39,13 @@ inline std::string mb_stub_mem(const void *p) {
 }
 #define MB_TRACE(...) printf(__VA_ARGS__)
 #define MB_TRACE_ID(counter) (++mb_stub_trace().counter)
+#if defined(MB_STUB_TRACE_QUIET_ALLOC)      // allocations keep their names but write no line (trace_state_job.cpp: a log of streams and events)
+#define MB_TRACE_ALLOC(what, p, n) do { const int id_ = MB_TRACE_ID(allocs); mb_stub_trace().mem[(const char *)(p)] = {id_, (n) ? (n) : 1}; } while (0)
+#define MB_TRACE_FREE(what, p) do { if (p) mb_stub_trace().mem.erase((const char *)(p)); } while (0)
+#else
 #define MB_TRACE_ALLOC(what, p, n) do { const int id_ = MB_TRACE_ID(allocs); mb_stub_trace().mem[(const char *)(p)] = {id_, (n) ? (n) : 1}; printf("%s %zu -> m%d\n", what, (size_t)(n), id_); } while (0)
 #define MB_TRACE_FREE(what, p) do { if (p) { printf("%s %s\n", what, mb_stub_mem(p).c_str()); mb_stub_trace().mem.erase((const char *)(p)); } } while (0)
+#endif
 #else
 #define MB_TRACE(...) ((void)0)
 #define MB_TRACE_ID(counter) 0
@@ -78,6 +83,8 @@ static inline hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned) { *s
 static inline hipError_t hipExtStreamCreateWithCUMask(hipStream_t *s, uint32_t n, const uint32_t *mask) {
     *s = new mb_stub_stream{MB_TRACE_ID(streams)}; MB_TRACE("hipExtStreamCreateWithCUMask -> s%d, mask", (*s)->id); for (uint32_t i = 0; i < n; ++i) MB_TRACE(" %08x", mask[i]); MB_TRACE("\n"); return hipSuccess;
 }
+static inline hipError_t hipStreamCreateWithPriority(hipStream_t *s, unsigned, int priority) { *s = new mb_stub_stream{MB_TRACE_ID(streams)}; MB_TRACE("hipStreamCreateWithPriority %d -> s%d\n", priority, (*s)->id); return hipSuccess; }
+static inline hipError_t hipDeviceGetStreamPriorityRange(int *least, int *greatest) { *least = 0; *greatest = -1; return hipSuccess; }      // (numerically lower = higher priority)
 static inline hipError_t hipStreamDestroy(hipStream_t s) { MB_TRACE("hipStreamDestroy s%d\n", mb_stub_id(s)); delete s; return hipSuccess; }
 static inline hipError_t hipStreamSynchronize(hipStream_t s) { MB_TRACE("hipStreamSynchronize s%d\n", mb_stub_id(s)); return hipSuccess; }
 static inline hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) { MB_TRACE("hipStreamWaitEvent s%d waits for e%d\n", mb_stub_id(s), mb_stub_id(e)); return hipSuccess; }
