@@ -150,6 +150,24 @@ func (c *Ctx) SelftestFe32(field, op int, rows []uint32) ([]uint32, error) {
 	return out[:len(out)-1], nil
 }
 
+// SelftestIpaRows: the transcript stage of the opening check alone; the rows it leaves come back as canonical bytes in the caller's buffers (sizes: mina_verify.h).
+// Test-facing: opt may be nil; side and offsets may be nil when no entry is shared.  flags = malformed word, lane form (16 / 8 / 3), side-stream word.
+func (c *Ctx) SelftestIpaRows(curve int, openings []C.mina_ipa_opening, randBase, sgRandBase []byte, opt *C.mina_ipa_rows_options,
+	points, scalars, chals, sigma, side []byte, offsets []uint32) (flags [3]uint32, err error) {
+	var pSide *C.uint8_t
+	var pOff *C.uint32_t
+	if len(side) > 0 && len(offsets) > 0 {
+		pSide, pOff = (*C.uint8_t)(unsafe.Pointer(&side[0])), (*C.uint32_t)(unsafe.Pointer(&offsets[0]))
+	}
+	rc := C.mina_selftest_ipa_rows(c.p, C.int(curve), C.size_t(len(openings)), &openings[0], (*C.uint8_t)(unsafe.Pointer(&randBase[0])), (*C.uint8_t)(unsafe.Pointer(&sgRandBase[0])), opt,
+		(*C.uint8_t)(unsafe.Pointer(&points[0])), (*C.uint8_t)(unsafe.Pointer(&scalars[0])), (*C.uint8_t)(unsafe.Pointer(&chals[0])), (*C.uint8_t)(unsafe.Pointer(&sigma[0])),
+		pSide, pOff, (*C.uint32_t)(unsafe.Pointer(&flags[0])))
+	if rc != 0 {
+		return flags, lastError()
+	}
+	return flags, nil
+}
+
 // AccumulatorCheckMulti: one deterministic verdict per proof (len(sg)/64 proofs).
 func (c *Ctx) AccumulatorCheckMulti(curve int, k uint32, pre, sg []byte) ([]bool, error) {
 	n := len(sg) / 64

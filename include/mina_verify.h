@@ -365,6 +365,37 @@ int mina_ipa_batch_check(mina_ctx *ctx, int curve, size_t batch, const mina_ipa_
                          const uint8_t *rand_base /* 32 */, const uint8_t *sg_rand_base /* 32 */,
                          uint8_t *verdict /* 1 byte: 1 = all openings valid */);
 
+/* Test-facing, like mina_selftest_group_law / _fe29 / _fe32: the transcript stage of the opening check ALONE -- what mina_ipa_batch_check and the Proof-of-State
+ * job run before the fold and the two MSMs -- and the rows it leaves, handed back as canonical little-endian bytes.  Nothing on a job's path calls it.
+ * Per proof the rows are `per` (point, scalar) pairs in the order [h, sg, U, delta, L_0, R_0, .., L_{k-1}, R_{k-1}, comm_0 ..], per = 2k + n_comms + 4
+ * (+ 7 with an expanded slot: that commitment becomes its 8 terms), n_comms = the largest of the batch (shorter lists are padded with infinity); behind the
+ * batch * per rows come the `nshared` batch-shared points with the sums of their scalars.  Needs the SRS `h` and the Poseidon tables of the base field, NOT
+ * 2^k SRS points (k = 1..20 on any SRS).  Openings are validated as by mina_ipa_batch_check; their CONTENTS need not be a valid proof.
+ * The optional shape (NULL = none of it, as mina_ipa_batch_check runs) is what only the Proof-of-State job sets in production: */
+#define MINA_IPA_ROWS_NO_SLOT 4294967295
+typedef struct {
+    uint32_t struct_size;           /* sizeof(mina_ipa_rows_options) */
+    uint32_t pow_first;             /* 0 or 1: rho_b = rand_base^(b + pow_first), sigma_b likewise */
+    uint32_t override_slot;         /* commitment index taken from comm_override, or MINA_IPA_ROWS_NO_SLOT */
+    uint32_t expand_slot;           /* commitment index given as 8 (point, scalar) terms, or MINA_IPA_ROWS_NO_SLOT */
+    const uint8_t *comm_override;   /* batch * 64 */
+    const uint8_t *expand_point0;   /* 64: term 0's point, the same for every proof (trusted index data in production: not validated) */
+    const uint8_t *expand_points;   /* batch * 7 * 64: the points of terms 1..7 */
+    const uint8_t *expand_scalars;  /* batch * 8 * 32: canonical scalars */
+    uint64_t shared_mask;           /* bit i: commitment i has the same point in every proof (bits at or beyond n_comms are an error) */
+    uint32_t shared_h;              /* h is shared */
+    uint32_t shared_expand0;        /* term 0 of the expanded slot is shared */
+    uint32_t restore_lo, restore_cnt; /* restore_cnt > 0: proofs [restore_lo, restore_lo + restore_cnt) get their own scalars of the shared points back */
+} mina_ipa_rows_options;
+/* nshared = popcount(shared_mask) + (shared_h != 0) + (shared_expand0 != 0 with an expanded slot); with nshared > 0, n_comms <= 64.  Outputs, with
+ * rows = batch * per + nshared: out_points rows * 64, out_scalars rows * 32 (after the shared sums and the restore), out_chals batch * k * 32, out_sigma
+ * batch * 32, out_side batch * nshared * 32 (the per-proof scalars of the shared points) and out_offsets nshared words (their places in a proof's list) --
+ * both may be NULL when nshared = 0 --, out_flags 3 words: [0] 1 iff some input was malformed (non-canonical element, point off the curve), [1] the lane form
+ * the transcripts ran in (16, 8 or 3 lanes per proof), [2] 1 iff the group map ran on the side stream. */
+int mina_selftest_ipa_rows(mina_ctx *ctx, int curve, size_t batch, const mina_ipa_opening *openings, const uint8_t *rand_base /* 32 */,
+                           const uint8_t *sg_rand_base /* 32 */, const mina_ipa_rows_options *options /* may be NULL */, uint8_t *out_points,
+                           uint8_t *out_scalars, uint8_t *out_chals, uint8_t *out_sigma, uint8_t *out_side, uint32_t *out_offsets, uint32_t *out_flags /* 3 */);
+
 /* ---- wire formats of the reference (a2, a3, a4) and the inclusion part of Proof-of-Account (a16) -----------------
  * Host-side, no GPU needed for the parsers.  Layouts: api_wire.hip header / SURVEY.md 8a.  Malformed input -> MINA_ERR_FORMAT. */
 typedef struct {

@@ -532,14 +532,15 @@ extern "C" int mina_accumulator_check_multi(mina_ctx *c, int curve, uint32_t k, 
 }
 
 // ------------------------------------------------------------------------------------------------
-// a8: combined opening check, inputs resident in HBM (structure-of-arrays, see IpaDevIn).  Queued on the current lane, no host
-// synchronisation: d_verdict[0] = 1 iff the folded check holds, d_verdict[1] = malformed-input flag.
-int mb_ipa_batch_check_dev(mina_ctx *c, int curve, mb::IpaShape sh, const mb::IpaDevIn &in, uint32_t *d_verdict, const FoldExport *fx) {
+// The transcript stage of the check: workspaces, the malformed word cleared, phase 1, the group map (beside phase 2 on the lane's second stream where the context
+// has one), phase 2, the sums of the batch-shared scalars.  Leaves the rows on the current lane -- ipa_points / ipa_scalars (batch * per + nshared entries), ipa_chals,
+// ipa_sigma, ipa_shared, ipa_shared_off -- and the malformed-input word at d_verdict[1]; the side stream has joined the lane's stream when it returns.
+// lanes_ran / side_ran (may be null): the lane form the transcripts ran in and whether the group map went to the side stream (mina_selftest_ipa_rows reports them).
+static int ipa_transcript_stage(mina_ctx *c, int curve, const mb::IpaShape &sh, const mb::IpaDevIn &in, uint32_t *d_verdict, int *lanes_ran, bool *side_ran) {
     SrsState &s = c->srs[curve];
     const int FB = base_field_of(curve), FS = scalar_field_of(curve);
     const size_t batch = sh.batch; const uint32_t k = sh.k;
     int rc;
-    if (fx) sh.pow_first = 1;          // partial sums that the caller adds to other shards': no coefficient-1 proof (ctx.h IpaShape::pow_first)
     if (sh.nshared && (sh.ncomms > 64 || sh.nshared > 64)) return fail(MINA_ERR_ARG, "shared entries need <= 64 commitments");
     const size_t npoints = batch * sh.per + sh.nshared;           // per-proof lists, then the batch-shared points once
     if ((rc = c->L->ipa_points.ensure(npoints * sizeof(affine_t)))) return rc;
@@ -585,10 +586,24 @@ int mb_ipa_batch_check_dev(mina_ctx *c, int curve, mb::IpaShape sh, const mb::Ip
         if (side) HIPC(hipEventRecord(L.ev_join, L.aux));
         if ((rc = prepare(std::integral_constant<int, 2>{}))) return rc;
         if (side) HIPC(hipStreamWaitEvent(L.stream, L.ev_join, 0));
+        if (lanes_ran) *lanes_ran = ln;
+        if (side_ran) *side_ran = side;
     }
     }
     HIPC(hipGetLastError());
     if (sh.nshared) { DISPATCH_FIELD(FS, { mb::ipa_shared_tail_kernel<F_><<<sh.nshared, 256, 0, c->L->stream>>>(sh.batch, sh.nshared, sh.per, c->L->ipa_shared.as<uint32_t>(), c->L->ipa_scalars.as<uint32_t>()); }); }
+    return MINA_OK;
+}
+
+// a8: combined opening check, inputs resident in HBM (structure-of-arrays, see IpaDevIn).  Queued on the current lane, no host
+// synchronisation: d_verdict[0] = 1 iff the folded check holds, d_verdict[1] = malformed-input flag.
+int mb_ipa_batch_check_dev(mina_ctx *c, int curve, mb::IpaShape sh, const mb::IpaDevIn &in, uint32_t *d_verdict, const FoldExport *fx) {
+    const int FB = base_field_of(curve), FS = scalar_field_of(curve);
+    const size_t batch = sh.batch; const uint32_t k = sh.k;
+    int rc;
+    if (fx) sh.pow_first = 1;          // partial sums that the caller adds to other shards': no coefficient-1 proof (ctx.h IpaShape::pow_first)
+    if ((rc = ipa_transcript_stage(c, curve, sh, in, d_verdict, nullptr, nullptr))) return rc;
+    const size_t npoints = batch * sh.per + sh.nshared;
     if ((rc = mb_bpoly_fold(c, FS, k, batch, c->L->ipa_chals.as<uint32_t>(), c->L->ipa_sigma.as<uint32_t>(), c->L->ipa_folded.as<uint32_t>()))) return rc;
     if (fx) {                        // the exchange variant over several GPUs: scalars and the variable-base partial go to the caller
         HIPC(hipMemcpyAsync(fx->ipa_scalars, c->L->ipa_folded.p, ((size_t)1 << k) * 32, hipMemcpyDeviceToDevice, c->L->stream));
@@ -718,20 +733,21 @@ int mb_accumulator_check_parts(mina_ctx *c, int curve, uint32_t k, size_t batch,
 
 // ------------------------------------------------------------------------------------------------
 // a8: combined opening check
-extern "C" int mina_ipa_batch_check(mina_ctx *c, int curve, size_t batch, const mina_ipa_opening *op, const uint8_t *rand_base,
-                                    const uint8_t *sg_rand_base, uint8_t *verdict) {
-    if (!c || !op || !rand_base || !sg_rand_base || !verdict) return fail(MINA_ERR_ARG, "null argument");
+// The openings of one call: validated, packed on the host into one staging blob, uploaded to the lane's ipa_in_a.  Fills the plain shape (none of the job's
+// options) and the device pointers.  need_srs_points: the caller goes on to the fold and the fixed-base MSM over g[0..2^k).
+static int ipa_stage_openings(mina_ctx *c, int curve, size_t batch, const mina_ipa_opening *op, const uint8_t *rand_base, const uint8_t *sg_rand_base,
+                              bool need_srs_points, mb::IpaShape &sh, mb::IpaDevIn &in) {
     if (curve != 0 && curve != 1) return fail(MINA_ERR_ARG, "bad curve");
     if (batch == 0 || batch > (1u << 16)) return fail(MINA_ERR_ARG, "bad batch");
     SrsState &s = c->srs[curve];
     if (s.depth == 0) return fail(MINA_ERR_STATE, "SRS not loaded for this curve");
-    const int FB = base_field_of(curve), FS = scalar_field_of(curve);
+    const int FB = base_field_of(curve);
     if (!c->have_pparams[FB]) return fail(MINA_ERR_STATE, "Poseidon constants not installed for the base field");
     const uint32_t k = op[0].k, npts = op[0].n_evalpoints;
     uint32_t m = 0;                                             // commitments per opening in the device layout = the maximum;
     for (size_t b = 0; b < batch; ++b) if (op[b].n_comms > m) m = op[b].n_comms;   // shorter lists are padded with infinity
     if (m > 4096) return fail(MINA_ERR_ARG, "too many commitments in one opening");
-    if (k < 1 || k > 20 || ((size_t)1 << k) > s.depth) return fail(MINA_ERR_ARG, "2^k exceeds the SRS depth");
+    if (k < 1 || k > 20 || (need_srs_points && ((size_t)1 << k) > s.depth)) return fail(MINA_ERR_ARG, "2^k exceeds the SRS depth");
     for (size_t b = 0; b < batch; ++b) {
         const mina_ipa_opening &o = op[b];
         if (o.k != k || o.n_evalpoints != npts) return fail(MINA_ERR_ARG, "openings of one batch must share k and n_evalpoints");
@@ -740,7 +756,7 @@ extern "C" int mina_ipa_batch_check(mina_ctx *c, int curve, size_t batch, const 
     }
     HIPC(hipSetDevice(c->device));
     c->use_lane0();
-    mb::IpaShape sh; sh.batch = (uint32_t)batch; sh.k = k; sh.npts = npts; sh.ncomms = m; sh.per = 2 * k + m + 4;
+    sh.batch = (uint32_t)batch; sh.k = k; sh.npts = npts; sh.ncomms = m; sh.per = 2 * k + m + 4;
 
     // pack (host) -> one staging blob -> HBM
     const size_t o_state = 0, o_cip = o_state + batch * 96, o_lr = o_cip + batch * 32, o_delta = o_lr + batch * 2 * k * 64,
@@ -772,12 +788,107 @@ extern "C" int mina_ipa_batch_check(mina_ctx *c, int curve, size_t batch, const 
     if ((rc = h2d(c, c->L->ipa_in_a, blob, total))) return rc;
     const uint8_t *d = c->L->ipa_in_a.as<uint8_t>();
     auto W = [&](size_t off) { return reinterpret_cast<const uint32_t *>(d + off); };
-    mb::IpaDevIn in{W(o_state), W(o_pos), W(o_cip), W(o_lr), W(o_delta), W(o_sg), W(o_z1), W(o_z2), W(o_pts), W(o_r), W(o_xi), W(o_comms), nullptr, W(o_rb), W(o_sb)};
+    in = mb::IpaDevIn{W(o_state), W(o_pos), W(o_cip), W(o_lr), W(o_delta), W(o_sg), W(o_z1), W(o_z2), W(o_pts), W(o_r), W(o_xi), W(o_comms), nullptr, W(o_rb), W(o_sb)};
+    return MINA_OK;
+}
+
+extern "C" int mina_ipa_batch_check(mina_ctx *c, int curve, size_t batch, const mina_ipa_opening *op, const uint8_t *rand_base,
+                                    const uint8_t *sg_rand_base, uint8_t *verdict) {
+    if (!c || !op || !rand_base || !sg_rand_base || !verdict) return fail(MINA_ERR_ARG, "null argument");
+    mb::IpaShape sh; mb::IpaDevIn in;
+    int rc;
+    if ((rc = ipa_stage_openings(c, curve, batch, op, rand_base, sg_rand_base, true, sh, in))) return rc;
     if ((rc = c->L->ipa_verdict.ensure(8))) return rc;          // [0] verdict, [1] malformed-input flag
     if ((rc = mb_ipa_batch_check_dev(c, curve, sh, in, c->L->ipa_verdict.as<uint32_t>()))) return rc;
     uint32_t v = 0;
     if ((rc = d2h_sync(c, &v, c->L->ipa_verdict, 4))) return rc;
     *verdict = v ? 1 : 0;
+    return MINA_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// mina_selftest_ipa_rows: the transcript stage alone, on the caller's openings and the job's shape options; the rows come back as canonical bytes.  Test-facing
+// (tests/test_gpu_ipa_rows.py holds them against tests/ipa_rows_model.py); nothing on a job's path.
+template <int F>
+__global__ void words_to_mont_kernel(uint32_t n, const uint32_t *__restrict__ in_words, fe_t r2, fe_t *__restrict__ out) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    out[i] = fe_to_mont<F>(mb::load_fe<F>(in_words + (size_t)i * 8), r2);
+}
+
+extern "C" int mina_selftest_ipa_rows(mina_ctx *c, int curve, size_t batch, const mina_ipa_opening *op, const uint8_t *rand_base, const uint8_t *sg_rand_base,
+                                      const mina_ipa_rows_options *opt, uint8_t *out_points, uint8_t *out_scalars, uint8_t *out_chals, uint8_t *out_sigma,
+                                      uint8_t *out_side, uint32_t *out_offsets, uint32_t *out_flags) {
+    if (!c || !op || !rand_base || !sg_rand_base || !out_points || !out_scalars || !out_chals || !out_sigma || !out_flags) return fail(MINA_ERR_ARG, "null argument");
+    if (opt && opt->struct_size != sizeof(mina_ipa_rows_options)) return fail(MINA_ERR_ARG, "mina_ipa_rows_options.struct_size does not match this library");
+    mb::IpaShape sh; mb::IpaDevIn in;
+    int rc;
+    if ((rc = ipa_stage_openings(c, curve, batch, op, rand_base, sg_rand_base, false, sh, in))) return rc;
+    const int FB = base_field_of(curve), FS = scalar_field_of(curve);
+    Lane &L = *c->L;
+    const uint32_t m = sh.ncomms, NO = MINA_IPA_ROWS_NO_SLOT;
+    uint32_t restore_lo = 0, restore_cnt = 0;
+    if (opt) {
+        if (opt->pow_first > 1) return fail(MINA_ERR_ARG, "pow_first is 0 or 1");
+        const bool ovr = opt->override_slot != NO, exp = opt->expand_slot != NO;
+        if (ovr && (opt->override_slot >= m || !opt->comm_override)) return fail(MINA_ERR_ARG, "override_slot beyond the commitments, or no comm_override");
+        if (exp && opt->expand_slot >= m) return fail(MINA_ERR_ARG, "expand_slot beyond the commitments");
+        if (exp && (!opt->expand_point0 || !opt->expand_points || !opt->expand_scalars)) return fail(MINA_ERR_ARG, "null argument");
+        if (ovr && exp && opt->override_slot == opt->expand_slot) return fail(MINA_ERR_ARG, "one slot is both overridden and expanded");
+        if (m < 64 && (opt->shared_mask >> m)) return fail(MINA_ERR_ARG, "shared_mask names a commitment beyond n_comms");
+        if (exp && ((opt->shared_mask >> opt->expand_slot) & 1u)) return fail(MINA_ERR_ARG, "the expanded slot is shared through shared_expand0, not shared_mask");
+        if ((uint64_t)opt->restore_lo + opt->restore_cnt > batch) return fail(MINA_ERR_ARG, "restore range beyond the batch");
+        sh.pow_first = opt->pow_first; sh.override_slot = opt->override_slot; sh.expand_slot = opt->expand_slot;
+        if (exp) sh.per += mb::IPA_EXPAND - 1;
+        sh.shared_lo = (uint32_t)opt->shared_mask; sh.shared_hi = (uint32_t)(opt->shared_mask >> 32);
+        sh.shared_h = opt->shared_h ? 1u : 0u; sh.shared_expand0 = (exp && opt->shared_expand0) ? 1u : 0u;
+        sh.nshared = (uint32_t)__builtin_popcountll(opt->shared_mask) + sh.shared_h + sh.shared_expand0;
+        if (sh.nshared && m > 64) return fail(MINA_ERR_ARG, "shared entries need <= 64 commitments");
+        restore_lo = opt->restore_lo; restore_cnt = opt->restore_cnt;
+        // the job's extra inputs: [override batch*64 | point 0 64 | points batch*7*64 | scalars batch*8*32] -> ipa_in_b; point 0 and the scalars -> Montgomery in ipa_in_c
+        const size_t o_ovr = 0, o_p0 = o_ovr + (ovr ? batch * 64 : 0), o_pts = o_p0 + (exp ? 64 : 0), o_sc = o_pts + (exp ? batch * 7 * 64 : 0), total = o_sc + (exp ? batch * 8 * 32 : 0);
+        if (total) {
+            std::vector<uint8_t> blob(total);
+            if (ovr) memcpy(&blob[o_ovr], opt->comm_override, batch * 64);
+            if (exp) { memcpy(&blob[o_p0], opt->expand_point0, 64); memcpy(&blob[o_pts], opt->expand_points, batch * 7 * 64); memcpy(&blob[o_sc], opt->expand_scalars, batch * 8 * 32); }
+            if ((rc = h2d(c, L.ipa_in_b, blob.data(), total))) return rc;
+            HIPC(hipStreamSynchronize(L.stream));                  // (the blob is pageable host memory of this scope)
+            const uint8_t *d = L.ipa_in_b.as<uint8_t>();
+            if (ovr) in.comm_override = reinterpret_cast<const uint32_t *>(d + o_ovr);
+            if (exp) {
+                const size_t nsc = batch * mb::IPA_EXPAND;
+                if ((rc = L.ipa_in_c.ensure(sizeof(mb::affine_t) + nsc * sizeof(mb::fe_t)))) return rc;
+                mb::affine_t *p0 = L.ipa_in_c.as<mb::affine_t>(); mb::fe_t *sc = reinterpret_cast<mb::fe_t *>(p0 + 1);
+                DISPATCH_FIELD(FB, { points_to_mont_kernel<F_><<<1, 64, 0, L.stream>>>(1, reinterpret_cast<const uint32_t *>(d + o_p0), c->fk[F_].r2, p0); });
+                DISPATCH_FIELD(FS, { words_to_mont_kernel<F_><<<cdiv(nsc, 256), 256, 0, L.stream>>>((uint32_t)nsc, reinterpret_cast<const uint32_t *>(d + o_sc), c->fk[F_].r2, sc); });
+                HIPC(hipGetLastError());
+                in.expand.p0 = p0; in.expand.pts = reinterpret_cast<const uint32_t *>(d + o_pts); in.expand.sc = sc; in.expand.stride = mb::IPA_EXPAND;
+            }
+        }
+    }
+    if (sh.nshared && (!out_side || !out_offsets)) return fail(MINA_ERR_ARG, "null argument");
+    if ((rc = L.ipa_verdict.ensure(8))) return rc;              // [1] malformed-input flag
+    int lanes_ran = 0; bool side_ran = false;
+    c->ipa_rows = nullptr;                                      // the lane's rows are no longer those of the last folded check (mb_ipa_recheck_rows)
+    if ((rc = ipa_transcript_stage(c, curve, sh, in, L.ipa_verdict.as<uint32_t>(), &lanes_ran, &side_ran))) return rc;
+    if (sh.nshared && restore_cnt)
+        mb::ipa_shared_restore_kernel<<<cdiv((size_t)restore_cnt * sh.nshared * 8, 256), 256, 0, L.stream>>>(restore_lo, restore_cnt, sh.nshared, sh.per, L.ipa_shared_off.as<uint32_t>(), L.ipa_shared.as<uint32_t>(), L.ipa_scalars.as<uint32_t>());
+    // everything below is queued on the lane's stream, which the stage left waiting for the side stream: the copies see the group map's points
+    const size_t rows = batch * sh.per + sh.nshared;
+    if ((rc = L.tmp_a.ensure(rows * 64))) return rc;
+    DISPATCH_FIELD(FB, { points_from_mont_kernel<F_><<<cdiv(rows, 256), 256, 0, L.stream>>>((uint32_t)rows, L.ipa_points.as<mb::affine_t>(), L.tmp_a.as<uint32_t>()); });
+    HIPC(hipGetLastError());
+    HIPC(hipMemcpyAsync(out_points, L.tmp_a.p, rows * 64, hipMemcpyDeviceToHost, L.stream));
+    HIPC(hipMemcpyAsync(out_scalars, L.ipa_scalars.p, rows * 32, hipMemcpyDeviceToHost, L.stream));
+    HIPC(hipMemcpyAsync(out_chals, L.ipa_chals.p, batch * sh.k * 32, hipMemcpyDeviceToHost, L.stream));
+    HIPC(hipMemcpyAsync(out_sigma, L.ipa_sigma.p, batch * 32, hipMemcpyDeviceToHost, L.stream));
+    if (sh.nshared) {
+        HIPC(hipMemcpyAsync(out_side, L.ipa_shared.p, batch * sh.nshared * 32, hipMemcpyDeviceToHost, L.stream));
+        HIPC(hipMemcpyAsync(out_offsets, L.ipa_shared_off.p, sh.nshared * 4, hipMemcpyDeviceToHost, L.stream));
+    }
+    uint32_t v[2] = {0, 0};
+    if ((rc = d2h_sync(c, v, L.ipa_verdict, 8))) return rc;
+    out_flags[0] = v[1] ? 1u : 0u; out_flags[1] = (uint32_t)lanes_ran; out_flags[2] = side_ran ? 1u : 0u;
     return MINA_OK;
 }
 

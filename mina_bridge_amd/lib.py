@@ -32,7 +32,7 @@ EXPORTS = [
     "mina_poseidon_set_params", "mina_poseidon_params_parse", "mina_poseidon_load_params", "mina_poseidon_load_params_file", "mina_poseidon_permute", "mina_poseidon_permute_dev", "mina_poseidon_hash",
     "mina_challenge_to_field", "mina_fq_sponge_run", "mina_to_group", "mina_merkle_roots", "mina_merkle_verify_batch",
     "mina_field_mul", "mina_field_inv", "mina_field_sqrt", "mina_selftest_group_law", "mina_selftest_fe29", "mina_selftest_fe32",
-    "mina_accumulator_check_batch", "mina_accumulator_check_dev", "mina_accumulator_check_multi_dev", "mina_accumulator_check_multi", "mina_ipa_batch_check",
+    "mina_accumulator_check_batch", "mina_accumulator_check_dev", "mina_accumulator_check_multi_dev", "mina_accumulator_check_multi", "mina_ipa_batch_check", "mina_selftest_ipa_rows",
     "mina_consensus_project_window", "mina_consensus_relative_min_window_density", "mina_consensus_is_short_range",
     "mina_protocol_state_pack", "mina_protocol_state_hash_batch", "mina_protocol_state_hash_bytes",
     "mina_protocol_state_dedup_dev", "mina_protocol_state_hash_batch_dedup", "mina_ctx_set_state_dedup", "mina_ctx_state_dedup_stats",
@@ -228,6 +228,17 @@ class PicklesStatements(ctypes.Structure):
 
     def strides(self):
         return dict(zip(self.POINTER_FIELDS, (64, 256, self.n_old * 256, self.n_old * 64, 480, 64, 32, self.n_evals * 64, 64, 32, 32, 32)))
+
+IPA_ROWS_NO_SLOT = 0xFFFFFFFF
+
+
+class IpaRowsOptions(ctypes.Structure):
+    """`mina_ipa_rows_options` (include/mina_verify.h): the shape options of mina_selftest_ipa_rows"""
+    _fields_ = [("struct_size", ctypes.c_uint32), ("pow_first", ctypes.c_uint32), ("override_slot", ctypes.c_uint32), ("expand_slot", ctypes.c_uint32),
+                ("comm_override", ctypes.c_void_p), ("expand_point0", ctypes.c_void_p), ("expand_points", ctypes.c_void_p), ("expand_scalars", ctypes.c_void_p),
+                ("shared_mask", ctypes.c_uint64), ("shared_h", ctypes.c_uint32), ("shared_expand0", ctypes.c_uint32),
+                ("restore_lo", ctypes.c_uint32), ("restore_cnt", ctypes.c_uint32)]
+
 
 # mina_selftest_fe29 (include/mina_verify.h MINA_FE29_*): row sizes, flag bits and op codes
 FE29_IN_OPERANDS, FE29_OUT_RESULTS = 8, 4
@@ -982,6 +993,35 @@ class MinaContext:
         v = np.zeros(1, np.uint8)
         self._ck(self._lib.mina_ipa_batch_check(self._h, curve, ctypes.c_size_t(len(arr)), arr, _p(rb), _p(sb), _p(v)), "mina_ipa_batch_check")
         return bool(v[0])
+
+    def selftest_ipa_rows(self, curve: int, openings, rand_base, sg_rand_base, pow_first: int = 0, override_slot=None, comm_override=None, expand_slot=None,
+                          expand_point0=None, expand_points=None, expand_scalars=None, shared_mask: int = 0, shared_h: int = 0, shared_expand0: int = 0,
+                          restore=(0, 0)) -> dict:
+        """the transcript stage of the opening check alone (mina_selftest_ipa_rows): `openings` as for ipa_batch_check, the keywords are the fields of
+        `mina_ipa_rows_options`.  Returns the rows as canonical bytes: points [rows, 64], scalars [rows, 32] (rows = batch * per + nshared), chals [batch, k, 32],
+        sigma [batch, 32], side [batch, nshared, 32], offsets [nshared], and the words malformed, lanes (16 / 8 / 3), side_stream.  Test-facing."""
+        arr, keep = openings if isinstance(openings, tuple) else self.pack_ipa_openings(openings)
+        batch = len(arr)
+        k, m = int(arr[0].k), max(int(o.n_comms) for o in arr)
+        rb, sb = _u8(rand_base), _u8(sg_rand_base)
+        opt = IpaRowsOptions(struct_size=ctypes.sizeof(IpaRowsOptions), pow_first=pow_first, override_slot=IPA_ROWS_NO_SLOT if override_slot is None else override_slot,
+                             expand_slot=IPA_ROWS_NO_SLOT if expand_slot is None else expand_slot, shared_mask=shared_mask, shared_h=shared_h, shared_expand0=shared_expand0,
+                             restore_lo=restore[0], restore_cnt=restore[1])
+        bufs = [None if x is None else _u8(x) for x in (comm_override, expand_point0, expand_points, expand_scalars)]
+        assert bufs[0] is None or bufs[0].size == batch * 64
+        assert expand_slot is None or (bufs[1].size == 64 and bufs[2].size == batch * 7 * 64 and bufs[3].size == batch * 8 * 32)
+        opt.comm_override, opt.expand_point0, opt.expand_points, opt.expand_scalars = (None if b is None else b.ctypes.data for b in bufs)
+        nshared = bin(shared_mask).count("1") + (1 if shared_h else 0) + (1 if shared_expand0 and expand_slot is not None else 0)
+        per = 2 * k + m + 4 + (7 if expand_slot is not None else 0)
+        rows = batch * per + nshared
+        out = {"points": np.empty((rows, 64), np.uint8), "scalars": np.empty((rows, 32), np.uint8), "chals": np.empty((batch, k, 32), np.uint8),
+               "sigma": np.empty((batch, 32), np.uint8), "side": np.empty((batch, nshared, 32), np.uint8), "offsets": np.empty(nshared, np.uint32)}
+        flags = np.zeros(3, np.uint32)
+        self._ck(self._lib.mina_selftest_ipa_rows(self._h, curve, ctypes.c_size_t(batch), arr, _p(rb), _p(sb), ctypes.byref(opt), _p(out["points"]), _p(out["scalars"]),
+                                                  _p(out["chals"]), _p(out["sigma"]), _p(out["side"]) if nshared else None, _p(out["offsets"]) if nshared else None,
+                                                  _p(flags)), "mina_selftest_ipa_rows")
+        out.update(malformed=int(flags[0]), lanes=int(flags[1]), side_stream=int(flags[2]), per=per, nshared=nshared)
+        return out
 
     # -- protocol states / the Proof-of-State job
     def protocol_state_hash_batch(self, records, nfields, want_body: bool = False):

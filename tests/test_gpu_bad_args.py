@@ -208,3 +208,50 @@ def test_exchange_building_blocks_refuse_bad_shapes_and_null_pointers(ctx_srs):
     finally:
         c.synchronize()
         c.dev_free(d)
+
+
+def test_ipa_rows_selftest_refuses_bad_arguments(ctx_srs, oracle):
+    """mina_selftest_ipa_rows: null pointers, a curve that is none, an empty batch, a foreign struct_size, a restore range past the batch, an expanded or overridden
+    slot past the commitments, shared entries over more than 64 commitments or without their output buffers -- MINA_ERR_ARG each, before anything is queued"""
+    import random
+    import mina_bridge_amd as m
+    import ipa_rows_model as M
+    c = ctx_srs
+    lib, L = c._lib, m.lib
+    g = [oracle.bytes_to_point(b) for b in c.srs_get_g(0, 0, 8)]
+    rng = random.Random(1)
+    batch, k, ncomms = 2, 2, 3
+    arr, keep = c.pack_ipa_openings([M.to_abi(M.random_proof(rng, 0, g, k, ncomms, 1)) for _ in range(batch)])
+    big, keep2 = c.pack_ipa_openings([M.to_abi(M.random_proof(rng, 0, g, k, 65, 1)) for _ in range(batch)])
+    rows = batch * (2 * k + ncomms + 4 + 7) + 3
+    buf = {n: np.zeros(sz, np.uint8) for n, sz in (("points", rows * 64), ("scalars", rows * 32), ("chals", batch * k * 32), ("sigma", batch * 32), ("side", batch * 3 * 32))}
+    off, flags, rb = np.zeros(3, np.uint32), np.zeros(3, np.uint32), np.ones(32, np.uint8)
+    pts = np.zeros(batch * 7 * 64, np.uint8)
+    P = lambda a: a.ctypes.data_as(ctypes.c_void_p)      # noqa: E731
+
+    def options(**kw):
+        o = L.IpaRowsOptions(struct_size=ctypes.sizeof(L.IpaRowsOptions), override_slot=L.IPA_ROWS_NO_SLOT, expand_slot=L.IPA_ROWS_NO_SLOT)
+        for name, v in kw.items():
+            setattr(o, name, v)
+        return o
+
+    def call(h=c._h, curve=0, n=batch, ops=arr, rand=rb, sg_rand=rb, opt=None, **out):
+        b = {name: P(a) for name, a in buf.items()}; b.update(offsets=P(off), flags=P(flags)); b.update(out)
+        return lib.mina_selftest_ipa_rows(h, curve, ctypes.c_size_t(n), ops, None if rand is None else P(rand), None if sg_rand is None else P(sg_rand),
+                                          None if opt is None else ctypes.byref(opt), b["points"], b["scalars"], b["chals"], b["sigma"], b["side"], b["offsets"], b["flags"])
+    expand = dict(expand_point0=pts.ctypes.data, expand_points=pts.ctypes.data, expand_scalars=pts.ctypes.data)
+    for kw in ({"h": None}, {"ops": None}, {"rand": None}, {"sg_rand": None}, {"points": None}, {"scalars": None}, {"chals": None}, {"sigma": None}, {"flags": None},
+               {"curve": 2}, {"curve": -1}, {"n": 0}, {"n": (1 << 16) + 1},
+               {"opt": options(struct_size=8)}, {"opt": options(struct_size=ctypes.sizeof(L.IpaRowsOptions) + 8)}, {"opt": options(pow_first=2)},
+               {"opt": options(shared_h=1, restore_lo=batch, restore_cnt=1)}, {"opt": options(shared_h=1, restore_lo=0, restore_cnt=batch + 1)},
+               {"opt": options(shared_h=1, restore_lo=0xFFFFFFFF, restore_cnt=2)},
+               {"opt": options(expand_slot=ncomms, **expand)}, {"opt": options(expand_slot=ncomms + 5, **expand)}, {"opt": options(expand_slot=1)},
+               {"opt": options(override_slot=ncomms, comm_override=pts.ctypes.data)}, {"opt": options(override_slot=1)},
+               {"opt": options(shared_mask=1 << ncomms)}, {"opt": options(shared_mask=1, shared_h=1), "ops": big}, {"opt": options(shared_h=1), "side": None},
+               {"opt": options(shared_mask=2), "offsets": None}):
+        assert call(**kw) == MINA_ERR_ARG, {n: (v if not isinstance(v, ctypes.Structure) else {f: getattr(v, f) for f, _ in v._fields_}) for n, v in kw.items()}
+    # and the entry point still computes, with and without options; the context's ordinary check as well
+    assert call() == 0 and flags[0] == 0 and flags[1] in (16, 8, 3) and buf["sigma"][:32].tolist() == [1] + [0] * 31      # (rand bases 0x0101..: sigma_0 = 1)
+    assert call(opt=options(shared_h=1, restore_lo=1, restore_cnt=1)) == 0 and off[0] == 0
+    one = np.zeros(32, np.uint8); one[0] = 1
+    assert (c.msm_srs(1, one) == c.srs_get_g(1, 0, 1)[0]).all()
