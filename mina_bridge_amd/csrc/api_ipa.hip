@@ -39,7 +39,7 @@ sponge_tape_kernel(uint32_t batch, uint32_t tape_len, uint32_t in_stride_words, 
     constexpr int FS = (CURVE == CURVE_PALLAS) ? FIELD_FQ : FIELD_FP;
     bool writer_; const uint32_t b = coop_sponge_index<LANES>(writer_), qq = coop_elem<LANES>();
     if (b >= batch) return;                                   // whole lane groups leave together
-    DevSponge<FB, LANES> sp; sp.pp = pp; sp.squeezed = 0; sp.count = 0; sp.s = fe_zero();
+    DevSponge<FB, LANES, false> sp; sp.pp = pp; sp.squeezed = 0; sp.count = 0; sp.s = fe_zero();   // the plain rounds: with the second round form beside them the 3-lane tape spills past its scratch budget (test-facing: not on a job's path)
     if (init_state) { sp.s = fe_to_mont<FB>(load_fe<FB>(init_state + (size_t)b * 24 + qq * 8), kb.r2); sp.squeezed = (int)init_pos[2 * b]; sp.count = (int)init_pos[2 * b + 1]; }
     const uint32_t *in = inputs + (size_t)b * in_stride_words;
     uint32_t *out = outputs + (size_t)b * out_stride_words;
@@ -111,7 +111,8 @@ ipa_prepare_kernel(IpaShape sh, FieldK kb, FieldK ks, const PoseidonParams *__re
     uint32_t *xf = xfer ? xfer + (size_t)b * IPA_XFER_WORDS : nullptr;
 
     // ---- Fq-sponge transcript (base field)
-    DevSponge<FB, LANES> sp; sp.pp = pp; sp.squeezed = 0; sp.count = 0;
+    // PHASE 1 -- one or two permutations -- keeps the plain rounds: it runs beside the state hashes at 96 VGPRs (5 waves per SIMD), and the normalised rounds' last round takes 101
+    DevSponge<FB, LANES, PHASE != 1> sp; sp.pp = pp; sp.squeezed = 0; sp.count = 0;
     if (PHASE == 2) {                                         // resume after the first squeeze
         sp.s = load_fe<FB>(xf + coop_elem<LANES>() * 8);
         sp.squeezed = (int)xf[24]; sp.count = (int)xf[25];

@@ -99,7 +99,7 @@ kimchi_fq_kernel(uint32_t batch, uint32_t n_prev, FieldK kb, FieldK ks, const Po
     if (pf_digest && writer) xf[(size_t)b * KC_XF + XF_PFDIGEST] = pf_digest[(size_t)b * pf_stride];     // the statement stage ran that sponge already (api_pickles.hip)
     DevSponge<FB, LANES> fq; sponge_init(fq, pp_b);
     fq.absorb(ix->digest);
-    auto absorb_pts = [&](const uint32_t *p, uint32_t n) {
+    auto absorb_pts = [&](const uint32_t *p, uint32_t n) __attribute__((always_inline)) {   // (left to the inliner's size limit it becomes a call, and `fq`, `ok` and both FieldK go to scratch)
 #pragma unroll 1
         for (uint32_t i = 0; i < n; ++i) { const affine_t P = load_point_checked<FB>(p + (size_t)i * 16, kb, ok); fq.absorb(P.x); fq.absorb(P.y); }
     };

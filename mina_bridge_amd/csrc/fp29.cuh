@@ -115,6 +115,7 @@ struct SPONGE29 {   // the Poseidon lane forms' state bounds between rounds, in 
     static constexpr uint32_t LANES8_STATE_MILLI_P = 4100;
     static constexpr uint32_t LANES16_STATE_MILLI_P = 6100;
     static constexpr uint32_t LANES1_STATE_MILLI_P = 6300;
+    static constexpr uint32_t LANES3N_STATE_MILLI_P = 4200;
 };
 // ---- END PROVEN CONSTANTS
 
@@ -2107,105 +2108,206 @@ template <int F> __device__ __forceinline__ fe29_t fe29_dot3rc_sg(const fe29_t &
     r.v[8] = (uint32_t)col;
     return r;
 }
-template <int F> __device__ __forceinline__ fe29_t fe29_row1_sg(const fe29_t &t, const fe29_t &a0, const fe29_t &b0, const fe29_t &a1, const fe29_t &b1, const fe29_t &c) {
-    uint64_t col, nc, cc; fe29_t r;
-    uint32_t m0, m1, m2, m3, m4, m5, m6, m7, m8;
-    const int32_t n1 = -(int32_t)P29<F>::L1, n2 = -(int32_t)P29<F>::L2, n3 = -(int32_t)P29<F>::L3, n4 = -(int32_t)P29<F>::L4, n8 = -(int32_t)P29<F>::L8;
-    // column 0: 3 + 0 products
-    asm("v_mad_u64_u32 %0, %1, %2, %3, 0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, 1, %0"
-        : "=&v"(col), "=&s"(cc) : "v"(b0.v[0]), "s"(a0.v[0]), "v"(b1.v[0]), "s"(a1.v[0]), "s"(c.v[0]));
-    m0 = (uint32_t)col;
-    // column 1: 5 + 1 products; first: - s_0 p_0 (the low limb of column 0 cancels) and its carry
-    asm("v_mad_i64_i32 %0, %1, %2, -1, %3\n\tv_ashrrev_i64 %0, 29, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, %9, %0\n\tv_mad_u64_u32 %0, %1, %10, %11, %0\n\tv_mad_u64_u32 %0, %1, %12, 1, %0\n\tv_mad_i64_i32 %0, %1, %13, %14, %0"
-        : "=&v"(nc), "=&s"(cc) : "v"(m0), "v"(col), "v"(b0.v[1]), "s"(a0.v[0]), "v"(b0.v[0]), "s"(a0.v[1]), "v"(b1.v[1]), "s"(a1.v[0]), "v"(b1.v[0]), "s"(a1.v[1]), "s"(c.v[1]), "v"(m0), "s"(n1));
-    col = nc;
-    m1 = (uint32_t)col;
-    // column 2: 7 + 2 products; first: - s_1 p_0 (the low limb of column 1 cancels) and its carry
-    asm("v_mad_i64_i32 %0, %1, %2, -1, %3\n\tv_ashrrev_i64 %0, 29, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, %9, %0\n\tv_mad_u64_u32 %0, %1, %10, %11, %0\n\tv_mad_u64_u32 %0, %1, %12, %13, %0\n\tv_mad_u64_u32 %0, %1, %14, %15, %0\n\tv_mad_u64_u32 %0, %1, %16, 1, %0\n\tv_mad_i64_i32 %0, %1, %17, %18, %0\n\tv_mad_i64_i32 %0, %1, %19, %20, %0"
-        : "=&v"(nc), "=&s"(cc) : "v"(m1), "v"(col), "v"(b0.v[2]), "s"(a0.v[0]), "v"(b0.v[1]), "s"(a0.v[1]), "v"(b0.v[0]), "s"(a0.v[2]), "v"(b1.v[2]), "s"(a1.v[0]), "v"(b1.v[1]), "s"(a1.v[1]), "v"(b1.v[0]), "s"(a1.v[2]), "s"(c.v[2]), "v"(m1), "s"(n1), "v"(m0), "s"(n2));
-    col = nc;
-    m2 = (uint32_t)col;
-    // column 3: 9 + 3 products; first: - s_2 p_0 (the low limb of column 2 cancels) and its carry
-    asm("v_mad_i64_i32 %0, %1, %2, -1, %3\n\tv_ashrrev_i64 %0, 29, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, %9, %0\n\tv_mad_u64_u32 %0, %1, %10, %11, %0\n\tv_mad_u64_u32 %0, %1, %12, %13, %0\n\tv_mad_u64_u32 %0, %1, %14, %15, %0\n\tv_mad_u64_u32 %0, %1, %16, %17, %0\n\tv_mad_u64_u32 %0, %1, %18, %19, %0\n\tv_mad_u64_u32 %0, %1, %20, 1, %0\n\tv_mad_i64_i32 %0, %1, %21, %22, %0\n\tv_mad_i64_i32 %0, %1, %23, %24, %0\n\tv_mad_i64_i32 %0, %1, %25, %26, %0"
-        : "=&v"(nc), "=&s"(cc) : "v"(m2), "v"(col), "v"(b0.v[3]), "s"(a0.v[0]), "v"(b0.v[2]), "s"(a0.v[1]), "v"(b0.v[1]), "s"(a0.v[2]), "v"(b0.v[0]), "s"(a0.v[3]), "v"(b1.v[3]), "s"(a1.v[0]), "v"(b1.v[2]), "s"(a1.v[1]), "v"(b1.v[1]), "s"(a1.v[2]), "v"(b1.v[0]), "s"(a1.v[3]), "s"(c.v[3]), "v"(m2), "s"(n1), "v"(m1), "s"(n2), "v"(m0), "s"(n3));
-    col = nc;
-    m3 = (uint32_t)col;
-    // column 4: 11 + 4 products; first: - s_3 p_0 (the low limb of column 3 cancels) and its carry
-    asm("v_mad_i64_i32 %0, %1, %2, -1, %3\n\tv_ashrrev_i64 %0, 29, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, %9, %0\n\tv_mad_u64_u32 %0, %1, %10, %11, %0\n\tv_mad_u64_u32 %0, %1, %12, %13, %0\n\tv_mad_u64_u32 %0, %1, %14, %15, %0\n\tv_mad_u64_u32 %0, %1, %16, %17, %0\n\tv_mad_u64_u32 %0, %1, %18, %19, %0\n\tv_mad_u64_u32 %0, %1, %20, %21, %0\n\tv_mad_u64_u32 %0, %1, %22, %23, %0\n\tv_mad_u64_u32 %0, %1, %24, 1, %0\n\tv_mad_i64_i32 %0, %1, %25, %26, %0\n\tv_mad_i64_i32 %0, %1, %27, %28, %0"
-        : "=&v"(nc), "=&s"(cc) : "v"(m3), "v"(col), "v"(b0.v[4]), "s"(a0.v[0]), "v"(b0.v[3]), "s"(a0.v[1]), "v"(b0.v[2]), "s"(a0.v[2]), "v"(b0.v[1]), "s"(a0.v[3]), "v"(b0.v[0]), "s"(a0.v[4]), "v"(b1.v[4]), "s"(a1.v[0]), "v"(b1.v[3]), "s"(a1.v[1]), "v"(b1.v[2]), "s"(a1.v[2]), "v"(b1.v[1]), "s"(a1.v[3]), "v"(b1.v[0]), "s"(a1.v[4]), "s"(c.v[4]), "v"(m3), "s"(n1), "v"(m2), "s"(n2));
-    asm("v_mad_i64_i32 %0, %1, %2, %3, %0\n\tv_mad_i64_i32 %0, %1, %4, %5, %0"
+template <int F, bool PER_LANE = false> __device__ __forceinline__ fe29_t fe29_row1_sg(const fe29_t &t, const fe29_t &a0, const fe29_t &b0, const fe29_t &a1, const fe29_t &b1, const fe29_t &c) {
+    if constexpr (PER_LANE) {
+        uint64_t col, nc, cc; fe29_t r;
+        uint32_t m0, m1, m2, m3, m4, m5, m6, m7, m8;
+        const int32_t n1 = -(int32_t)P29<F>::L1, n2 = -(int32_t)P29<F>::L2, n3 = -(int32_t)P29<F>::L3, n4 = -(int32_t)P29<F>::L4, n8 = -(int32_t)P29<F>::L8;
+        // column 0: 3 + 0 products
+        asm("v_mad_u64_u32 %0, %1, %2, %3, 0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, 1, %0"
+        : "=&v"(col), "=&s"(cc) : "v"(b0.v[0]), "v"(a0.v[0]), "v"(b1.v[0]), "v"(a1.v[0]), "v"(c.v[0]));
+        m0 = (uint32_t)col;
+        // column 1: 5 + 1 products; first: - s_0 p_0 (the low limb of column 0 cancels) and its carry
+        asm("v_mad_i64_i32 %0, %1, %2, -1, %3\n\tv_ashrrev_i64 %0, 29, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, %9, %0\n\tv_mad_u64_u32 %0, %1, %10, %11, %0\n\tv_mad_u64_u32 %0, %1, %12, 1, %0\n\tv_mad_i64_i32 %0, %1, %13, %14, %0"
+        : "=&v"(nc), "=&s"(cc) : "v"(m0), "v"(col), "v"(b0.v[1]), "v"(a0.v[0]), "v"(b0.v[0]), "v"(a0.v[1]), "v"(b1.v[1]), "v"(a1.v[0]), "v"(b1.v[0]), "v"(a1.v[1]), "v"(c.v[1]), "v"(m0), "s"(n1));
+        col = nc;
+        m1 = (uint32_t)col;
+        // column 2: 7 + 2 products; first: - s_1 p_0 (the low limb of column 1 cancels) and its carry
+        asm("v_mad_i64_i32 %0, %1, %2, -1, %3\n\tv_ashrrev_i64 %0, 29, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, %9, %0\n\tv_mad_u64_u32 %0, %1, %10, %11, %0\n\tv_mad_u64_u32 %0, %1, %12, %13, %0\n\tv_mad_u64_u32 %0, %1, %14, %15, %0\n\tv_mad_u64_u32 %0, %1, %16, 1, %0\n\tv_mad_i64_i32 %0, %1, %17, %18, %0\n\tv_mad_i64_i32 %0, %1, %19, %20, %0"
+        : "=&v"(nc), "=&s"(cc) : "v"(m1), "v"(col), "v"(b0.v[2]), "v"(a0.v[0]), "v"(b0.v[1]), "v"(a0.v[1]), "v"(b0.v[0]), "v"(a0.v[2]), "v"(b1.v[2]), "v"(a1.v[0]), "v"(b1.v[1]), "v"(a1.v[1]), "v"(b1.v[0]), "v"(a1.v[2]), "v"(c.v[2]), "v"(m1), "s"(n1), "v"(m0), "s"(n2));
+        col = nc;
+        m2 = (uint32_t)col;
+        // column 3: 9 + 3 products; first: - s_2 p_0 (the low limb of column 2 cancels) and its carry
+        asm("v_mad_i64_i32 %0, %1, %2, -1, %3\n\tv_ashrrev_i64 %0, 29, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, %9, %0\n\tv_mad_u64_u32 %0, %1, %10, %11, %0\n\tv_mad_u64_u32 %0, %1, %12, %13, %0\n\tv_mad_u64_u32 %0, %1, %14, %15, %0\n\tv_mad_u64_u32 %0, %1, %16, %17, %0\n\tv_mad_u64_u32 %0, %1, %18, %19, %0\n\tv_mad_u64_u32 %0, %1, %20, 1, %0\n\tv_mad_i64_i32 %0, %1, %21, %22, %0\n\tv_mad_i64_i32 %0, %1, %23, %24, %0\n\tv_mad_i64_i32 %0, %1, %25, %26, %0"
+        : "=&v"(nc), "=&s"(cc) : "v"(m2), "v"(col), "v"(b0.v[3]), "v"(a0.v[0]), "v"(b0.v[2]), "v"(a0.v[1]), "v"(b0.v[1]), "v"(a0.v[2]), "v"(b0.v[0]), "v"(a0.v[3]), "v"(b1.v[3]), "v"(a1.v[0]), "v"(b1.v[2]), "v"(a1.v[1]), "v"(b1.v[1]), "v"(a1.v[2]), "v"(b1.v[0]), "v"(a1.v[3]), "v"(c.v[3]), "v"(m2), "s"(n1), "v"(m1), "s"(n2), "v"(m0), "s"(n3));
+        col = nc;
+        m3 = (uint32_t)col;
+        // column 4: 11 + 4 products; first: - s_3 p_0 (the low limb of column 3 cancels) and its carry
+        asm("v_mad_i64_i32 %0, %1, %2, -1, %3\n\tv_ashrrev_i64 %0, 29, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, %9, %0\n\tv_mad_u64_u32 %0, %1, %10, %11, %0\n\tv_mad_u64_u32 %0, %1, %12, %13, %0\n\tv_mad_u64_u32 %0, %1, %14, %15, %0\n\tv_mad_u64_u32 %0, %1, %16, %17, %0\n\tv_mad_u64_u32 %0, %1, %18, %19, %0\n\tv_mad_u64_u32 %0, %1, %20, %21, %0\n\tv_mad_u64_u32 %0, %1, %22, %23, %0\n\tv_mad_u64_u32 %0, %1, %24, 1, %0\n\tv_mad_i64_i32 %0, %1, %25, %26, %0\n\tv_mad_i64_i32 %0, %1, %27, %28, %0"
+        : "=&v"(nc), "=&s"(cc) : "v"(m3), "v"(col), "v"(b0.v[4]), "v"(a0.v[0]), "v"(b0.v[3]), "v"(a0.v[1]), "v"(b0.v[2]), "v"(a0.v[2]), "v"(b0.v[1]), "v"(a0.v[3]), "v"(b0.v[0]), "v"(a0.v[4]), "v"(b1.v[4]), "v"(a1.v[0]), "v"(b1.v[3]), "v"(a1.v[1]), "v"(b1.v[2]), "v"(a1.v[2]), "v"(b1.v[1]), "v"(a1.v[3]), "v"(b1.v[0]), "v"(a1.v[4]), "v"(c.v[4]), "v"(m3), "s"(n1), "v"(m2), "s"(n2));
+        asm("v_mad_i64_i32 %0, %1, %2, %3, %0\n\tv_mad_i64_i32 %0, %1, %4, %5, %0"
         : "+&v"(nc), "=&s"(cc) : "v"(m1), "s"(n3), "v"(m0), "s"(n4));
-    col = nc;
-    m4 = (uint32_t)col;
-    // column 5: 13 + 4 products; first: - s_4 p_0 (the low limb of column 4 cancels) and its carry
-    asm("v_mad_i64_i32 %0, %1, %2, -1, %3\n\tv_ashrrev_i64 %0, 29, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, %9, %0\n\tv_mad_u64_u32 %0, %1, %10, %11, %0\n\tv_mad_u64_u32 %0, %1, %12, %13, %0\n\tv_mad_u64_u32 %0, %1, %14, %15, %0\n\tv_mad_u64_u32 %0, %1, %16, %17, %0\n\tv_mad_u64_u32 %0, %1, %18, %19, %0\n\tv_mad_u64_u32 %0, %1, %20, %21, %0\n\tv_mad_u64_u32 %0, %1, %22, %23, %0\n\tv_mad_u64_u32 %0, %1, %24, %25, %0\n\tv_mad_u64_u32 %0, %1, %26, %27, %0\n\tv_mad_u64_u32 %0, %1, %28, 1, %0"
-        : "=&v"(nc), "=&s"(cc) : "v"(m4), "v"(col), "v"(b0.v[5]), "s"(a0.v[0]), "v"(b0.v[4]), "s"(a0.v[1]), "v"(b0.v[3]), "s"(a0.v[2]), "v"(b0.v[2]), "s"(a0.v[3]), "v"(b0.v[1]), "s"(a0.v[4]), "v"(b0.v[0]), "s"(a0.v[5]), "v"(b1.v[5]), "s"(a1.v[0]), "v"(b1.v[4]), "s"(a1.v[1]), "v"(b1.v[3]), "s"(a1.v[2]), "v"(b1.v[2]), "s"(a1.v[3]), "v"(b1.v[1]), "s"(a1.v[4]), "v"(b1.v[0]), "s"(a1.v[5]), "s"(c.v[5]));
-    asm("v_mad_i64_i32 %0, %1, %2, %3, %0\n\tv_mad_i64_i32 %0, %1, %4, %5, %0\n\tv_mad_i64_i32 %0, %1, %6, %7, %0\n\tv_mad_i64_i32 %0, %1, %8, %9, %0"
+        col = nc;
+        m4 = (uint32_t)col;
+        // column 5: 13 + 4 products; first: - s_4 p_0 (the low limb of column 4 cancels) and its carry
+        asm("v_mad_i64_i32 %0, %1, %2, -1, %3\n\tv_ashrrev_i64 %0, 29, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, %9, %0\n\tv_mad_u64_u32 %0, %1, %10, %11, %0\n\tv_mad_u64_u32 %0, %1, %12, %13, %0\n\tv_mad_u64_u32 %0, %1, %14, %15, %0\n\tv_mad_u64_u32 %0, %1, %16, %17, %0\n\tv_mad_u64_u32 %0, %1, %18, %19, %0\n\tv_mad_u64_u32 %0, %1, %20, %21, %0\n\tv_mad_u64_u32 %0, %1, %22, %23, %0\n\tv_mad_u64_u32 %0, %1, %24, %25, %0\n\tv_mad_u64_u32 %0, %1, %26, %27, %0\n\tv_mad_u64_u32 %0, %1, %28, 1, %0"
+        : "=&v"(nc), "=&s"(cc) : "v"(m4), "v"(col), "v"(b0.v[5]), "v"(a0.v[0]), "v"(b0.v[4]), "v"(a0.v[1]), "v"(b0.v[3]), "v"(a0.v[2]), "v"(b0.v[2]), "v"(a0.v[3]), "v"(b0.v[1]), "v"(a0.v[4]), "v"(b0.v[0]), "v"(a0.v[5]), "v"(b1.v[5]), "v"(a1.v[0]), "v"(b1.v[4]), "v"(a1.v[1]), "v"(b1.v[3]), "v"(a1.v[2]), "v"(b1.v[2]), "v"(a1.v[3]), "v"(b1.v[1]), "v"(a1.v[4]), "v"(b1.v[0]), "v"(a1.v[5]), "v"(c.v[5]));
+        asm("v_mad_i64_i32 %0, %1, %2, %3, %0\n\tv_mad_i64_i32 %0, %1, %4, %5, %0\n\tv_mad_i64_i32 %0, %1, %6, %7, %0\n\tv_mad_i64_i32 %0, %1, %8, %9, %0"
         : "+&v"(nc), "=&s"(cc) : "v"(m4), "s"(n1), "v"(m3), "s"(n2), "v"(m2), "s"(n3), "v"(m1), "s"(n4));
-    col = nc;
-    m5 = (uint32_t)col;
-    // column 6: 15 + 4 products; first: - s_5 p_0 (the low limb of column 5 cancels) and its carry
-    asm("v_mad_i64_i32 %0, %1, %2, -1, %3\n\tv_ashrrev_i64 %0, 29, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, %9, %0\n\tv_mad_u64_u32 %0, %1, %10, %11, %0\n\tv_mad_u64_u32 %0, %1, %12, %13, %0\n\tv_mad_u64_u32 %0, %1, %14, %15, %0\n\tv_mad_u64_u32 %0, %1, %16, %17, %0\n\tv_mad_u64_u32 %0, %1, %18, %19, %0\n\tv_mad_u64_u32 %0, %1, %20, %21, %0\n\tv_mad_u64_u32 %0, %1, %22, %23, %0\n\tv_mad_u64_u32 %0, %1, %24, %25, %0\n\tv_mad_u64_u32 %0, %1, %26, %27, %0\n\tv_mad_u64_u32 %0, %1, %28, %29, %0"
-        : "=&v"(nc), "=&s"(cc) : "v"(m5), "v"(col), "v"(b0.v[6]), "s"(a0.v[0]), "v"(b0.v[5]), "s"(a0.v[1]), "v"(b0.v[4]), "s"(a0.v[2]), "v"(b0.v[3]), "s"(a0.v[3]), "v"(b0.v[2]), "s"(a0.v[4]), "v"(b0.v[1]), "s"(a0.v[5]), "v"(b0.v[0]), "s"(a0.v[6]), "v"(b1.v[6]), "s"(a1.v[0]), "v"(b1.v[5]), "s"(a1.v[1]), "v"(b1.v[4]), "s"(a1.v[2]), "v"(b1.v[3]), "s"(a1.v[3]), "v"(b1.v[2]), "s"(a1.v[4]), "v"(b1.v[1]), "s"(a1.v[5]));
-    asm("v_mad_u64_u32 %0, %1, %2, %3, %0\n\tv_mad_u64_u32 %0, %1, %4, 1, %0\n\tv_mad_i64_i32 %0, %1, %5, %6, %0\n\tv_mad_i64_i32 %0, %1, %7, %8, %0\n\tv_mad_i64_i32 %0, %1, %9, %10, %0\n\tv_mad_i64_i32 %0, %1, %11, %12, %0"
-        : "+&v"(nc), "=&s"(cc) : "v"(b1.v[0]), "s"(a1.v[6]), "s"(c.v[6]), "v"(m5), "s"(n1), "v"(m4), "s"(n2), "v"(m3), "s"(n3), "v"(m2), "s"(n4));
-    col = nc;
-    m6 = (uint32_t)col;
-    // column 7: 17 + 4 products; first: - s_6 p_0 (the low limb of column 6 cancels) and its carry
-    asm("v_mad_i64_i32 %0, %1, %2, -1, %3\n\tv_ashrrev_i64 %0, 29, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, %9, %0\n\tv_mad_u64_u32 %0, %1, %10, %11, %0\n\tv_mad_u64_u32 %0, %1, %12, %13, %0\n\tv_mad_u64_u32 %0, %1, %14, %15, %0\n\tv_mad_u64_u32 %0, %1, %16, %17, %0\n\tv_mad_u64_u32 %0, %1, %18, %19, %0\n\tv_mad_u64_u32 %0, %1, %20, %21, %0\n\tv_mad_u64_u32 %0, %1, %22, %23, %0\n\tv_mad_u64_u32 %0, %1, %24, %25, %0\n\tv_mad_u64_u32 %0, %1, %26, %27, %0\n\tv_mad_u64_u32 %0, %1, %28, %29, %0"
-        : "=&v"(nc), "=&s"(cc) : "v"(m6), "v"(col), "v"(b0.v[7]), "s"(a0.v[0]), "v"(b0.v[6]), "s"(a0.v[1]), "v"(b0.v[5]), "s"(a0.v[2]), "v"(b0.v[4]), "s"(a0.v[3]), "v"(b0.v[3]), "s"(a0.v[4]), "v"(b0.v[2]), "s"(a0.v[5]), "v"(b0.v[1]), "s"(a0.v[6]), "v"(b0.v[0]), "s"(a0.v[7]), "v"(b1.v[7]), "s"(a1.v[0]), "v"(b1.v[6]), "s"(a1.v[1]), "v"(b1.v[5]), "s"(a1.v[2]), "v"(b1.v[4]), "s"(a1.v[3]), "v"(b1.v[3]), "s"(a1.v[4]));
-    asm("v_mad_u64_u32 %0, %1, %2, %3, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, 1, %0\n\tv_mad_i64_i32 %0, %1, %9, %10, %0\n\tv_mad_i64_i32 %0, %1, %11, %12, %0\n\tv_mad_i64_i32 %0, %1, %13, %14, %0\n\tv_mad_i64_i32 %0, %1, %15, %16, %0"
-        : "+&v"(nc), "=&s"(cc) : "v"(b1.v[2]), "s"(a1.v[5]), "v"(b1.v[1]), "s"(a1.v[6]), "v"(b1.v[0]), "s"(a1.v[7]), "s"(c.v[7]), "v"(m6), "s"(n1), "v"(m5), "s"(n2), "v"(m4), "s"(n3), "v"(m3), "s"(n4));
-    col = nc;
-    m7 = (uint32_t)col;
-    // column 8: 19 + 5 products; first: - s_7 p_0 (the low limb of column 7 cancels) and its carry
-    asm("v_mad_i64_i32 %0, %1, %2, -1, %3\n\tv_ashrrev_i64 %0, 29, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, %9, %0\n\tv_mad_u64_u32 %0, %1, %10, %11, %0\n\tv_mad_u64_u32 %0, %1, %12, %13, %0\n\tv_mad_u64_u32 %0, %1, %14, %15, %0\n\tv_mad_u64_u32 %0, %1, %16, %17, %0\n\tv_mad_u64_u32 %0, %1, %18, %19, %0\n\tv_mad_u64_u32 %0, %1, %20, %21, %0\n\tv_mad_u64_u32 %0, %1, %22, %23, %0\n\tv_mad_u64_u32 %0, %1, %24, %25, %0\n\tv_mad_u64_u32 %0, %1, %26, %27, %0\n\tv_mad_u64_u32 %0, %1, %28, %29, %0"
-        : "=&v"(nc), "=&s"(cc) : "v"(m7), "v"(col), "v"(b0.v[8]), "s"(a0.v[0]), "v"(b0.v[7]), "s"(a0.v[1]), "v"(b0.v[6]), "s"(a0.v[2]), "v"(b0.v[5]), "s"(a0.v[3]), "v"(b0.v[4]), "s"(a0.v[4]), "v"(b0.v[3]), "s"(a0.v[5]), "v"(b0.v[2]), "s"(a0.v[6]), "v"(b0.v[1]), "s"(a0.v[7]), "v"(b0.v[0]), "s"(a0.v[8]), "v"(b1.v[8]), "s"(a1.v[0]), "v"(b1.v[7]), "s"(a1.v[1]), "v"(b1.v[6]), "s"(a1.v[2]), "v"(b1.v[5]), "s"(a1.v[3]));
-    asm("v_mad_u64_u32 %0, %1, %2, %3, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, %9, %0\n\tv_mad_u64_u32 %0, %1, %10, %11, %0\n\tv_mad_u64_u32 %0, %1, %12, 1, %0\n\tv_mad_i64_i32 %0, %1, %13, %14, %0\n\tv_mad_i64_i32 %0, %1, %15, %16, %0\n\tv_mad_i64_i32 %0, %1, %17, %18, %0\n\tv_mad_i64_i32 %0, %1, %19, %20, %0\n\tv_mad_i64_i32 %0, %1, %21, %22, %0"
-        : "+&v"(nc), "=&s"(cc) : "v"(b1.v[4]), "s"(a1.v[4]), "v"(b1.v[3]), "s"(a1.v[5]), "v"(b1.v[2]), "s"(a1.v[6]), "v"(b1.v[1]), "s"(a1.v[7]), "v"(b1.v[0]), "s"(a1.v[8]), "s"(c.v[8]), "v"(m7), "s"(n1), "v"(m6), "s"(n2), "v"(m5), "s"(n3), "v"(m4), "s"(n4), "v"(m0), "s"(n8));
-    col = nc;
-    m8 = ((uint32_t)col & M29) | 0xC0000000u;        // (col & M29) - 2^30: the one digit with a fixed sign
-    // column 9: 17 + 5 products; first: - s_8 p_0 (the low limb of column 8 cancels) and its carry
-    asm("v_mad_i64_i32 %0, %1, %2, -1, %3\n\tv_ashrrev_i64 %0, 29, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, %9, %0\n\tv_mad_u64_u32 %0, %1, %10, %11, %0\n\tv_mad_u64_u32 %0, %1, %12, %13, %0\n\tv_mad_u64_u32 %0, %1, %14, %15, %0\n\tv_mad_u64_u32 %0, %1, %16, %17, %0\n\tv_mad_u64_u32 %0, %1, %18, %19, %0\n\tv_mad_u64_u32 %0, %1, %20, %21, %0\n\tv_mad_u64_u32 %0, %1, %22, %23, %0\n\tv_mad_u64_u32 %0, %1, %24, %25, %0\n\tv_mad_u64_u32 %0, %1, %26, %27, %0\n\tv_mad_u64_u32 %0, %1, %28, %29, %0"
-        : "=&v"(nc), "=&s"(cc) : "v"(m8), "v"(col), "v"(b0.v[8]), "s"(a0.v[1]), "v"(b0.v[7]), "s"(a0.v[2]), "v"(b0.v[6]), "s"(a0.v[3]), "v"(b0.v[5]), "s"(a0.v[4]), "v"(b0.v[4]), "s"(a0.v[5]), "v"(b0.v[3]), "s"(a0.v[6]), "v"(b0.v[2]), "s"(a0.v[7]), "v"(b0.v[1]), "s"(a0.v[8]), "v"(b1.v[8]), "s"(a1.v[1]), "v"(b1.v[7]), "s"(a1.v[2]), "v"(b1.v[6]), "s"(a1.v[3]), "v"(b1.v[5]), "s"(a1.v[4]), "v"(b1.v[4]), "s"(a1.v[5]));
-    asm("v_mad_u64_u32 %0, %1, %2, %3, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, 1, %0\n\tv_mad_i64_i32 %0, %1, %9, %10, %0\n\tv_mad_i64_i32 %0, %1, %11, %12, %0\n\tv_mad_i64_i32 %0, %1, %13, %14, %0\n\tv_mad_i64_i32 %0, %1, %15, %16, %0\n\tv_mad_i64_i32 %0, %1, %17, %18, %0"
-        : "+&v"(nc), "=&s"(cc) : "v"(b1.v[3]), "s"(a1.v[6]), "v"(b1.v[2]), "s"(a1.v[7]), "v"(b1.v[1]), "s"(a1.v[8]), "v"(t.v[0]), "v"(m8), "s"(n1), "v"(m7), "s"(n2), "v"(m6), "s"(n3), "v"(m5), "s"(n4), "v"(m1), "s"(n8));
-    col = nc;
-    r.v[0] = (uint32_t)col & M29; col = (uint64_t)((int64_t)col >> 29);
-    // column 10: 15 + 4 products
-    asm("v_mad_u64_u32 %0, %1, %2, %3, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, %9, %0\n\tv_mad_u64_u32 %0, %1, %10, %11, %0\n\tv_mad_u64_u32 %0, %1, %12, %13, %0\n\tv_mad_u64_u32 %0, %1, %14, %15, %0\n\tv_mad_u64_u32 %0, %1, %16, %17, %0\n\tv_mad_u64_u32 %0, %1, %18, %19, %0\n\tv_mad_u64_u32 %0, %1, %20, %21, %0\n\tv_mad_u64_u32 %0, %1, %22, %23, %0\n\tv_mad_u64_u32 %0, %1, %24, %25, %0\n\tv_mad_u64_u32 %0, %1, %26, %27, %0\n\tv_mad_u64_u32 %0, %1, %28, %29, %0"
-        : "+&v"(col), "=&s"(cc) : "v"(b0.v[8]), "s"(a0.v[2]), "v"(b0.v[7]), "s"(a0.v[3]), "v"(b0.v[6]), "s"(a0.v[4]), "v"(b0.v[5]), "s"(a0.v[5]), "v"(b0.v[4]), "s"(a0.v[6]), "v"(b0.v[3]), "s"(a0.v[7]), "v"(b0.v[2]), "s"(a0.v[8]), "v"(b1.v[8]), "s"(a1.v[2]), "v"(b1.v[7]), "s"(a1.v[3]), "v"(b1.v[6]), "s"(a1.v[4]), "v"(b1.v[5]), "s"(a1.v[5]), "v"(b1.v[4]), "s"(a1.v[6]), "v"(b1.v[3]), "s"(a1.v[7]), "v"(b1.v[2]), "s"(a1.v[8]));
-    asm("v_mad_u64_u32 %0, %1, %2, 1, %0\n\tv_mad_i64_i32 %0, %1, %3, %4, %0\n\tv_mad_i64_i32 %0, %1, %5, %6, %0\n\tv_mad_i64_i32 %0, %1, %7, %8, %0\n\tv_mad_i64_i32 %0, %1, %9, %10, %0"
+        col = nc;
+        m5 = (uint32_t)col;
+        // column 6: 15 + 4 products; first: - s_5 p_0 (the low limb of column 5 cancels) and its carry
+        asm("v_mad_i64_i32 %0, %1, %2, -1, %3\n\tv_ashrrev_i64 %0, 29, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, %9, %0\n\tv_mad_u64_u32 %0, %1, %10, %11, %0\n\tv_mad_u64_u32 %0, %1, %12, %13, %0\n\tv_mad_u64_u32 %0, %1, %14, %15, %0\n\tv_mad_u64_u32 %0, %1, %16, %17, %0\n\tv_mad_u64_u32 %0, %1, %18, %19, %0\n\tv_mad_u64_u32 %0, %1, %20, %21, %0\n\tv_mad_u64_u32 %0, %1, %22, %23, %0\n\tv_mad_u64_u32 %0, %1, %24, %25, %0\n\tv_mad_u64_u32 %0, %1, %26, %27, %0\n\tv_mad_u64_u32 %0, %1, %28, %29, %0"
+        : "=&v"(nc), "=&s"(cc) : "v"(m5), "v"(col), "v"(b0.v[6]), "v"(a0.v[0]), "v"(b0.v[5]), "v"(a0.v[1]), "v"(b0.v[4]), "v"(a0.v[2]), "v"(b0.v[3]), "v"(a0.v[3]), "v"(b0.v[2]), "v"(a0.v[4]), "v"(b0.v[1]), "v"(a0.v[5]), "v"(b0.v[0]), "v"(a0.v[6]), "v"(b1.v[6]), "v"(a1.v[0]), "v"(b1.v[5]), "v"(a1.v[1]), "v"(b1.v[4]), "v"(a1.v[2]), "v"(b1.v[3]), "v"(a1.v[3]), "v"(b1.v[2]), "v"(a1.v[4]), "v"(b1.v[1]), "v"(a1.v[5]));
+        asm("v_mad_u64_u32 %0, %1, %2, %3, %0\n\tv_mad_u64_u32 %0, %1, %4, 1, %0\n\tv_mad_i64_i32 %0, %1, %5, %6, %0\n\tv_mad_i64_i32 %0, %1, %7, %8, %0\n\tv_mad_i64_i32 %0, %1, %9, %10, %0\n\tv_mad_i64_i32 %0, %1, %11, %12, %0"
+        : "+&v"(nc), "=&s"(cc) : "v"(b1.v[0]), "v"(a1.v[6]), "v"(c.v[6]), "v"(m5), "s"(n1), "v"(m4), "s"(n2), "v"(m3), "s"(n3), "v"(m2), "s"(n4));
+        col = nc;
+        m6 = (uint32_t)col;
+        // column 7: 17 + 4 products; first: - s_6 p_0 (the low limb of column 6 cancels) and its carry
+        asm("v_mad_i64_i32 %0, %1, %2, -1, %3\n\tv_ashrrev_i64 %0, 29, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, %9, %0\n\tv_mad_u64_u32 %0, %1, %10, %11, %0\n\tv_mad_u64_u32 %0, %1, %12, %13, %0\n\tv_mad_u64_u32 %0, %1, %14, %15, %0\n\tv_mad_u64_u32 %0, %1, %16, %17, %0\n\tv_mad_u64_u32 %0, %1, %18, %19, %0\n\tv_mad_u64_u32 %0, %1, %20, %21, %0\n\tv_mad_u64_u32 %0, %1, %22, %23, %0\n\tv_mad_u64_u32 %0, %1, %24, %25, %0\n\tv_mad_u64_u32 %0, %1, %26, %27, %0\n\tv_mad_u64_u32 %0, %1, %28, %29, %0"
+        : "=&v"(nc), "=&s"(cc) : "v"(m6), "v"(col), "v"(b0.v[7]), "v"(a0.v[0]), "v"(b0.v[6]), "v"(a0.v[1]), "v"(b0.v[5]), "v"(a0.v[2]), "v"(b0.v[4]), "v"(a0.v[3]), "v"(b0.v[3]), "v"(a0.v[4]), "v"(b0.v[2]), "v"(a0.v[5]), "v"(b0.v[1]), "v"(a0.v[6]), "v"(b0.v[0]), "v"(a0.v[7]), "v"(b1.v[7]), "v"(a1.v[0]), "v"(b1.v[6]), "v"(a1.v[1]), "v"(b1.v[5]), "v"(a1.v[2]), "v"(b1.v[4]), "v"(a1.v[3]), "v"(b1.v[3]), "v"(a1.v[4]));
+        asm("v_mad_u64_u32 %0, %1, %2, %3, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, 1, %0\n\tv_mad_i64_i32 %0, %1, %9, %10, %0\n\tv_mad_i64_i32 %0, %1, %11, %12, %0\n\tv_mad_i64_i32 %0, %1, %13, %14, %0\n\tv_mad_i64_i32 %0, %1, %15, %16, %0"
+        : "+&v"(nc), "=&s"(cc) : "v"(b1.v[2]), "v"(a1.v[5]), "v"(b1.v[1]), "v"(a1.v[6]), "v"(b1.v[0]), "v"(a1.v[7]), "v"(c.v[7]), "v"(m6), "s"(n1), "v"(m5), "s"(n2), "v"(m4), "s"(n3), "v"(m3), "s"(n4));
+        col = nc;
+        m7 = (uint32_t)col;
+        // column 8: 19 + 5 products; first: - s_7 p_0 (the low limb of column 7 cancels) and its carry
+        asm("v_mad_i64_i32 %0, %1, %2, -1, %3\n\tv_ashrrev_i64 %0, 29, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, %9, %0\n\tv_mad_u64_u32 %0, %1, %10, %11, %0\n\tv_mad_u64_u32 %0, %1, %12, %13, %0\n\tv_mad_u64_u32 %0, %1, %14, %15, %0\n\tv_mad_u64_u32 %0, %1, %16, %17, %0\n\tv_mad_u64_u32 %0, %1, %18, %19, %0\n\tv_mad_u64_u32 %0, %1, %20, %21, %0\n\tv_mad_u64_u32 %0, %1, %22, %23, %0\n\tv_mad_u64_u32 %0, %1, %24, %25, %0\n\tv_mad_u64_u32 %0, %1, %26, %27, %0\n\tv_mad_u64_u32 %0, %1, %28, %29, %0"
+        : "=&v"(nc), "=&s"(cc) : "v"(m7), "v"(col), "v"(b0.v[8]), "v"(a0.v[0]), "v"(b0.v[7]), "v"(a0.v[1]), "v"(b0.v[6]), "v"(a0.v[2]), "v"(b0.v[5]), "v"(a0.v[3]), "v"(b0.v[4]), "v"(a0.v[4]), "v"(b0.v[3]), "v"(a0.v[5]), "v"(b0.v[2]), "v"(a0.v[6]), "v"(b0.v[1]), "v"(a0.v[7]), "v"(b0.v[0]), "v"(a0.v[8]), "v"(b1.v[8]), "v"(a1.v[0]), "v"(b1.v[7]), "v"(a1.v[1]), "v"(b1.v[6]), "v"(a1.v[2]), "v"(b1.v[5]), "v"(a1.v[3]));
+        asm("v_mad_u64_u32 %0, %1, %2, %3, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, %9, %0\n\tv_mad_u64_u32 %0, %1, %10, %11, %0\n\tv_mad_u64_u32 %0, %1, %12, 1, %0\n\tv_mad_i64_i32 %0, %1, %13, %14, %0\n\tv_mad_i64_i32 %0, %1, %15, %16, %0\n\tv_mad_i64_i32 %0, %1, %17, %18, %0\n\tv_mad_i64_i32 %0, %1, %19, %20, %0\n\tv_mad_i64_i32 %0, %1, %21, %22, %0"
+        : "+&v"(nc), "=&s"(cc) : "v"(b1.v[4]), "v"(a1.v[4]), "v"(b1.v[3]), "v"(a1.v[5]), "v"(b1.v[2]), "v"(a1.v[6]), "v"(b1.v[1]), "v"(a1.v[7]), "v"(b1.v[0]), "v"(a1.v[8]), "v"(c.v[8]), "v"(m7), "s"(n1), "v"(m6), "s"(n2), "v"(m5), "s"(n3), "v"(m4), "s"(n4), "v"(m0), "s"(n8));
+        col = nc;
+        m8 = ((uint32_t)col & M29) | 0xC0000000u;        // (col & M29) - 2^30: the one digit with a fixed sign
+        // column 9: 17 + 5 products; first: - s_8 p_0 (the low limb of column 8 cancels) and its carry
+        asm("v_mad_i64_i32 %0, %1, %2, -1, %3\n\tv_ashrrev_i64 %0, 29, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, %9, %0\n\tv_mad_u64_u32 %0, %1, %10, %11, %0\n\tv_mad_u64_u32 %0, %1, %12, %13, %0\n\tv_mad_u64_u32 %0, %1, %14, %15, %0\n\tv_mad_u64_u32 %0, %1, %16, %17, %0\n\tv_mad_u64_u32 %0, %1, %18, %19, %0\n\tv_mad_u64_u32 %0, %1, %20, %21, %0\n\tv_mad_u64_u32 %0, %1, %22, %23, %0\n\tv_mad_u64_u32 %0, %1, %24, %25, %0\n\tv_mad_u64_u32 %0, %1, %26, %27, %0\n\tv_mad_u64_u32 %0, %1, %28, %29, %0"
+        : "=&v"(nc), "=&s"(cc) : "v"(m8), "v"(col), "v"(b0.v[8]), "v"(a0.v[1]), "v"(b0.v[7]), "v"(a0.v[2]), "v"(b0.v[6]), "v"(a0.v[3]), "v"(b0.v[5]), "v"(a0.v[4]), "v"(b0.v[4]), "v"(a0.v[5]), "v"(b0.v[3]), "v"(a0.v[6]), "v"(b0.v[2]), "v"(a0.v[7]), "v"(b0.v[1]), "v"(a0.v[8]), "v"(b1.v[8]), "v"(a1.v[1]), "v"(b1.v[7]), "v"(a1.v[2]), "v"(b1.v[6]), "v"(a1.v[3]), "v"(b1.v[5]), "v"(a1.v[4]), "v"(b1.v[4]), "v"(a1.v[5]));
+        asm("v_mad_u64_u32 %0, %1, %2, %3, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, 1, %0\n\tv_mad_i64_i32 %0, %1, %9, %10, %0\n\tv_mad_i64_i32 %0, %1, %11, %12, %0\n\tv_mad_i64_i32 %0, %1, %13, %14, %0\n\tv_mad_i64_i32 %0, %1, %15, %16, %0\n\tv_mad_i64_i32 %0, %1, %17, %18, %0"
+        : "+&v"(nc), "=&s"(cc) : "v"(b1.v[3]), "v"(a1.v[6]), "v"(b1.v[2]), "v"(a1.v[7]), "v"(b1.v[1]), "v"(a1.v[8]), "v"(t.v[0]), "v"(m8), "s"(n1), "v"(m7), "s"(n2), "v"(m6), "s"(n3), "v"(m5), "s"(n4), "v"(m1), "s"(n8));
+        col = nc;
+        r.v[0] = (uint32_t)col & M29; col = (uint64_t)((int64_t)col >> 29);
+        // column 10: 15 + 4 products
+        asm("v_mad_u64_u32 %0, %1, %2, %3, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, %9, %0\n\tv_mad_u64_u32 %0, %1, %10, %11, %0\n\tv_mad_u64_u32 %0, %1, %12, %13, %0\n\tv_mad_u64_u32 %0, %1, %14, %15, %0\n\tv_mad_u64_u32 %0, %1, %16, %17, %0\n\tv_mad_u64_u32 %0, %1, %18, %19, %0\n\tv_mad_u64_u32 %0, %1, %20, %21, %0\n\tv_mad_u64_u32 %0, %1, %22, %23, %0\n\tv_mad_u64_u32 %0, %1, %24, %25, %0\n\tv_mad_u64_u32 %0, %1, %26, %27, %0\n\tv_mad_u64_u32 %0, %1, %28, %29, %0"
+        : "+&v"(col), "=&s"(cc) : "v"(b0.v[8]), "v"(a0.v[2]), "v"(b0.v[7]), "v"(a0.v[3]), "v"(b0.v[6]), "v"(a0.v[4]), "v"(b0.v[5]), "v"(a0.v[5]), "v"(b0.v[4]), "v"(a0.v[6]), "v"(b0.v[3]), "v"(a0.v[7]), "v"(b0.v[2]), "v"(a0.v[8]), "v"(b1.v[8]), "v"(a1.v[2]), "v"(b1.v[7]), "v"(a1.v[3]), "v"(b1.v[6]), "v"(a1.v[4]), "v"(b1.v[5]), "v"(a1.v[5]), "v"(b1.v[4]), "v"(a1.v[6]), "v"(b1.v[3]), "v"(a1.v[7]), "v"(b1.v[2]), "v"(a1.v[8]));
+        asm("v_mad_u64_u32 %0, %1, %2, 1, %0\n\tv_mad_i64_i32 %0, %1, %3, %4, %0\n\tv_mad_i64_i32 %0, %1, %5, %6, %0\n\tv_mad_i64_i32 %0, %1, %7, %8, %0\n\tv_mad_i64_i32 %0, %1, %9, %10, %0"
         : "+&v"(col), "=&s"(cc) : "v"(t.v[1]), "v"(m8), "s"(n2), "v"(m7), "s"(n3), "v"(m6), "s"(n4), "v"(m2), "s"(n8));
-    r.v[1] = (uint32_t)col & M29; col = (uint64_t)((int64_t)col >> 29);
-    // column 11: 13 + 3 products
-    asm("v_mad_u64_u32 %0, %1, %2, %3, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, %9, %0\n\tv_mad_u64_u32 %0, %1, %10, %11, %0\n\tv_mad_u64_u32 %0, %1, %12, %13, %0\n\tv_mad_u64_u32 %0, %1, %14, %15, %0\n\tv_mad_u64_u32 %0, %1, %16, %17, %0\n\tv_mad_u64_u32 %0, %1, %18, %19, %0\n\tv_mad_u64_u32 %0, %1, %20, %21, %0\n\tv_mad_u64_u32 %0, %1, %22, %23, %0\n\tv_mad_u64_u32 %0, %1, %24, %25, %0\n\tv_mad_u64_u32 %0, %1, %26, 1, %0\n\tv_mad_i64_i32 %0, %1, %27, %28, %0"
-        : "+&v"(col), "=&s"(cc) : "v"(b0.v[8]), "s"(a0.v[3]), "v"(b0.v[7]), "s"(a0.v[4]), "v"(b0.v[6]), "s"(a0.v[5]), "v"(b0.v[5]), "s"(a0.v[6]), "v"(b0.v[4]), "s"(a0.v[7]), "v"(b0.v[3]), "s"(a0.v[8]), "v"(b1.v[8]), "s"(a1.v[3]), "v"(b1.v[7]), "s"(a1.v[4]), "v"(b1.v[6]), "s"(a1.v[5]), "v"(b1.v[5]), "s"(a1.v[6]), "v"(b1.v[4]), "s"(a1.v[7]), "v"(b1.v[3]), "s"(a1.v[8]), "v"(t.v[2]), "v"(m8), "s"(n3));
-    asm("v_mad_i64_i32 %0, %1, %2, %3, %0\n\tv_mad_i64_i32 %0, %1, %4, %5, %0"
+        r.v[1] = (uint32_t)col & M29; col = (uint64_t)((int64_t)col >> 29);
+        // column 11: 13 + 3 products
+        asm("v_mad_u64_u32 %0, %1, %2, %3, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, %9, %0\n\tv_mad_u64_u32 %0, %1, %10, %11, %0\n\tv_mad_u64_u32 %0, %1, %12, %13, %0\n\tv_mad_u64_u32 %0, %1, %14, %15, %0\n\tv_mad_u64_u32 %0, %1, %16, %17, %0\n\tv_mad_u64_u32 %0, %1, %18, %19, %0\n\tv_mad_u64_u32 %0, %1, %20, %21, %0\n\tv_mad_u64_u32 %0, %1, %22, %23, %0\n\tv_mad_u64_u32 %0, %1, %24, %25, %0\n\tv_mad_u64_u32 %0, %1, %26, 1, %0\n\tv_mad_i64_i32 %0, %1, %27, %28, %0"
+        : "+&v"(col), "=&s"(cc) : "v"(b0.v[8]), "v"(a0.v[3]), "v"(b0.v[7]), "v"(a0.v[4]), "v"(b0.v[6]), "v"(a0.v[5]), "v"(b0.v[5]), "v"(a0.v[6]), "v"(b0.v[4]), "v"(a0.v[7]), "v"(b0.v[3]), "v"(a0.v[8]), "v"(b1.v[8]), "v"(a1.v[3]), "v"(b1.v[7]), "v"(a1.v[4]), "v"(b1.v[6]), "v"(a1.v[5]), "v"(b1.v[5]), "v"(a1.v[6]), "v"(b1.v[4]), "v"(a1.v[7]), "v"(b1.v[3]), "v"(a1.v[8]), "v"(t.v[2]), "v"(m8), "s"(n3));
+        asm("v_mad_i64_i32 %0, %1, %2, %3, %0\n\tv_mad_i64_i32 %0, %1, %4, %5, %0"
         : "+&v"(col), "=&s"(cc) : "v"(m7), "s"(n4), "v"(m3), "s"(n8));
-    r.v[2] = (uint32_t)col & M29; col = (uint64_t)((int64_t)col >> 29);
-    // column 12: 11 + 2 products
-    asm("v_mad_u64_u32 %0, %1, %2, %3, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, %9, %0\n\tv_mad_u64_u32 %0, %1, %10, %11, %0\n\tv_mad_u64_u32 %0, %1, %12, %13, %0\n\tv_mad_u64_u32 %0, %1, %14, %15, %0\n\tv_mad_u64_u32 %0, %1, %16, %17, %0\n\tv_mad_u64_u32 %0, %1, %18, %19, %0\n\tv_mad_u64_u32 %0, %1, %20, %21, %0\n\tv_mad_u64_u32 %0, %1, %22, 1, %0\n\tv_mad_i64_i32 %0, %1, %23, %24, %0\n\tv_mad_i64_i32 %0, %1, %25, %26, %0"
+        r.v[2] = (uint32_t)col & M29; col = (uint64_t)((int64_t)col >> 29);
+        // column 12: 11 + 2 products
+        asm("v_mad_u64_u32 %0, %1, %2, %3, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, %9, %0\n\tv_mad_u64_u32 %0, %1, %10, %11, %0\n\tv_mad_u64_u32 %0, %1, %12, %13, %0\n\tv_mad_u64_u32 %0, %1, %14, %15, %0\n\tv_mad_u64_u32 %0, %1, %16, %17, %0\n\tv_mad_u64_u32 %0, %1, %18, %19, %0\n\tv_mad_u64_u32 %0, %1, %20, %21, %0\n\tv_mad_u64_u32 %0, %1, %22, 1, %0\n\tv_mad_i64_i32 %0, %1, %23, %24, %0\n\tv_mad_i64_i32 %0, %1, %25, %26, %0"
+        : "+&v"(col), "=&s"(cc) : "v"(b0.v[8]), "v"(a0.v[4]), "v"(b0.v[7]), "v"(a0.v[5]), "v"(b0.v[6]), "v"(a0.v[6]), "v"(b0.v[5]), "v"(a0.v[7]), "v"(b0.v[4]), "v"(a0.v[8]), "v"(b1.v[8]), "v"(a1.v[4]), "v"(b1.v[7]), "v"(a1.v[5]), "v"(b1.v[6]), "v"(a1.v[6]), "v"(b1.v[5]), "v"(a1.v[7]), "v"(b1.v[4]), "v"(a1.v[8]), "v"(t.v[3]), "v"(m8), "s"(n4), "v"(m4), "s"(n8));
+        r.v[3] = (uint32_t)col & M29; col = (uint64_t)((int64_t)col >> 29);
+        // column 13: 9 + 1 products
+        asm("v_mad_u64_u32 %0, %1, %2, %3, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, %9, %0\n\tv_mad_u64_u32 %0, %1, %10, %11, %0\n\tv_mad_u64_u32 %0, %1, %12, %13, %0\n\tv_mad_u64_u32 %0, %1, %14, %15, %0\n\tv_mad_u64_u32 %0, %1, %16, %17, %0\n\tv_mad_u64_u32 %0, %1, %18, 1, %0\n\tv_mad_i64_i32 %0, %1, %19, %20, %0"
+        : "+&v"(col), "=&s"(cc) : "v"(b0.v[8]), "v"(a0.v[5]), "v"(b0.v[7]), "v"(a0.v[6]), "v"(b0.v[6]), "v"(a0.v[7]), "v"(b0.v[5]), "v"(a0.v[8]), "v"(b1.v[8]), "v"(a1.v[5]), "v"(b1.v[7]), "v"(a1.v[6]), "v"(b1.v[6]), "v"(a1.v[7]), "v"(b1.v[5]), "v"(a1.v[8]), "v"(t.v[4]), "v"(m5), "s"(n8));
+        r.v[4] = (uint32_t)col & M29; col = (uint64_t)((int64_t)col >> 29);
+        // column 14: 7 + 1 products
+        asm("v_mad_u64_u32 %0, %1, %2, %3, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, %9, %0\n\tv_mad_u64_u32 %0, %1, %10, %11, %0\n\tv_mad_u64_u32 %0, %1, %12, %13, %0\n\tv_mad_u64_u32 %0, %1, %14, 1, %0\n\tv_mad_i64_i32 %0, %1, %15, %16, %0"
+        : "+&v"(col), "=&s"(cc) : "v"(b0.v[8]), "v"(a0.v[6]), "v"(b0.v[7]), "v"(a0.v[7]), "v"(b0.v[6]), "v"(a0.v[8]), "v"(b1.v[8]), "v"(a1.v[6]), "v"(b1.v[7]), "v"(a1.v[7]), "v"(b1.v[6]), "v"(a1.v[8]), "v"(t.v[5]), "v"(m6), "s"(n8));
+        r.v[5] = (uint32_t)col & M29; col = (uint64_t)((int64_t)col >> 29);
+        // column 15: 5 + 1 products
+        asm("v_mad_u64_u32 %0, %1, %2, %3, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, %9, %0\n\tv_mad_u64_u32 %0, %1, %10, 1, %0\n\tv_mad_i64_i32 %0, %1, %11, %12, %0"
+        : "+&v"(col), "=&s"(cc) : "v"(b0.v[8]), "v"(a0.v[7]), "v"(b0.v[7]), "v"(a0.v[8]), "v"(b1.v[8]), "v"(a1.v[7]), "v"(b1.v[7]), "v"(a1.v[8]), "v"(t.v[6]), "v"(m7), "s"(n8));
+        r.v[6] = (uint32_t)col & M29; col = (uint64_t)((int64_t)col >> 29);
+        // column 16: 3 + 1 products
+        asm("v_mad_u64_u32 %0, %1, %2, %3, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, 1, %0\n\tv_mad_i64_i32 %0, %1, %7, %8, %0"
+        : "+&v"(col), "=&s"(cc) : "v"(b0.v[8]), "v"(a0.v[8]), "v"(b1.v[8]), "v"(a1.v[8]), "v"(t.v[7]), "v"(m8), "s"(n8));
+        r.v[7] = (uint32_t)col & M29; col = (uint64_t)((int64_t)col >> 29);
+        r.v[8] = (uint32_t)col + t.v[8];
+        return r;
+    } else {
+        uint64_t col, nc, cc; fe29_t r;
+        uint32_t m0, m1, m2, m3, m4, m5, m6, m7, m8;
+        const int32_t n1 = -(int32_t)P29<F>::L1, n2 = -(int32_t)P29<F>::L2, n3 = -(int32_t)P29<F>::L3, n4 = -(int32_t)P29<F>::L4, n8 = -(int32_t)P29<F>::L8;
+        // column 0: 3 + 0 products
+        asm("v_mad_u64_u32 %0, %1, %2, %3, 0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, 1, %0"
+        : "=&v"(col), "=&s"(cc) : "v"(b0.v[0]), "s"(a0.v[0]), "v"(b1.v[0]), "s"(a1.v[0]), "s"(c.v[0]));
+        m0 = (uint32_t)col;
+        // column 1: 5 + 1 products; first: - s_0 p_0 (the low limb of column 0 cancels) and its carry
+        asm("v_mad_i64_i32 %0, %1, %2, -1, %3\n\tv_ashrrev_i64 %0, 29, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, %9, %0\n\tv_mad_u64_u32 %0, %1, %10, %11, %0\n\tv_mad_u64_u32 %0, %1, %12, 1, %0\n\tv_mad_i64_i32 %0, %1, %13, %14, %0"
+        : "=&v"(nc), "=&s"(cc) : "v"(m0), "v"(col), "v"(b0.v[1]), "s"(a0.v[0]), "v"(b0.v[0]), "s"(a0.v[1]), "v"(b1.v[1]), "s"(a1.v[0]), "v"(b1.v[0]), "s"(a1.v[1]), "s"(c.v[1]), "v"(m0), "s"(n1));
+        col = nc;
+        m1 = (uint32_t)col;
+        // column 2: 7 + 2 products; first: - s_1 p_0 (the low limb of column 1 cancels) and its carry
+        asm("v_mad_i64_i32 %0, %1, %2, -1, %3\n\tv_ashrrev_i64 %0, 29, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, %9, %0\n\tv_mad_u64_u32 %0, %1, %10, %11, %0\n\tv_mad_u64_u32 %0, %1, %12, %13, %0\n\tv_mad_u64_u32 %0, %1, %14, %15, %0\n\tv_mad_u64_u32 %0, %1, %16, 1, %0\n\tv_mad_i64_i32 %0, %1, %17, %18, %0\n\tv_mad_i64_i32 %0, %1, %19, %20, %0"
+        : "=&v"(nc), "=&s"(cc) : "v"(m1), "v"(col), "v"(b0.v[2]), "s"(a0.v[0]), "v"(b0.v[1]), "s"(a0.v[1]), "v"(b0.v[0]), "s"(a0.v[2]), "v"(b1.v[2]), "s"(a1.v[0]), "v"(b1.v[1]), "s"(a1.v[1]), "v"(b1.v[0]), "s"(a1.v[2]), "s"(c.v[2]), "v"(m1), "s"(n1), "v"(m0), "s"(n2));
+        col = nc;
+        m2 = (uint32_t)col;
+        // column 3: 9 + 3 products; first: - s_2 p_0 (the low limb of column 2 cancels) and its carry
+        asm("v_mad_i64_i32 %0, %1, %2, -1, %3\n\tv_ashrrev_i64 %0, 29, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, %9, %0\n\tv_mad_u64_u32 %0, %1, %10, %11, %0\n\tv_mad_u64_u32 %0, %1, %12, %13, %0\n\tv_mad_u64_u32 %0, %1, %14, %15, %0\n\tv_mad_u64_u32 %0, %1, %16, %17, %0\n\tv_mad_u64_u32 %0, %1, %18, %19, %0\n\tv_mad_u64_u32 %0, %1, %20, 1, %0\n\tv_mad_i64_i32 %0, %1, %21, %22, %0\n\tv_mad_i64_i32 %0, %1, %23, %24, %0\n\tv_mad_i64_i32 %0, %1, %25, %26, %0"
+        : "=&v"(nc), "=&s"(cc) : "v"(m2), "v"(col), "v"(b0.v[3]), "s"(a0.v[0]), "v"(b0.v[2]), "s"(a0.v[1]), "v"(b0.v[1]), "s"(a0.v[2]), "v"(b0.v[0]), "s"(a0.v[3]), "v"(b1.v[3]), "s"(a1.v[0]), "v"(b1.v[2]), "s"(a1.v[1]), "v"(b1.v[1]), "s"(a1.v[2]), "v"(b1.v[0]), "s"(a1.v[3]), "s"(c.v[3]), "v"(m2), "s"(n1), "v"(m1), "s"(n2), "v"(m0), "s"(n3));
+        col = nc;
+        m3 = (uint32_t)col;
+        // column 4: 11 + 4 products; first: - s_3 p_0 (the low limb of column 3 cancels) and its carry
+        asm("v_mad_i64_i32 %0, %1, %2, -1, %3\n\tv_ashrrev_i64 %0, 29, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, %9, %0\n\tv_mad_u64_u32 %0, %1, %10, %11, %0\n\tv_mad_u64_u32 %0, %1, %12, %13, %0\n\tv_mad_u64_u32 %0, %1, %14, %15, %0\n\tv_mad_u64_u32 %0, %1, %16, %17, %0\n\tv_mad_u64_u32 %0, %1, %18, %19, %0\n\tv_mad_u64_u32 %0, %1, %20, %21, %0\n\tv_mad_u64_u32 %0, %1, %22, %23, %0\n\tv_mad_u64_u32 %0, %1, %24, 1, %0\n\tv_mad_i64_i32 %0, %1, %25, %26, %0\n\tv_mad_i64_i32 %0, %1, %27, %28, %0"
+        : "=&v"(nc), "=&s"(cc) : "v"(m3), "v"(col), "v"(b0.v[4]), "s"(a0.v[0]), "v"(b0.v[3]), "s"(a0.v[1]), "v"(b0.v[2]), "s"(a0.v[2]), "v"(b0.v[1]), "s"(a0.v[3]), "v"(b0.v[0]), "s"(a0.v[4]), "v"(b1.v[4]), "s"(a1.v[0]), "v"(b1.v[3]), "s"(a1.v[1]), "v"(b1.v[2]), "s"(a1.v[2]), "v"(b1.v[1]), "s"(a1.v[3]), "v"(b1.v[0]), "s"(a1.v[4]), "s"(c.v[4]), "v"(m3), "s"(n1), "v"(m2), "s"(n2));
+        asm("v_mad_i64_i32 %0, %1, %2, %3, %0\n\tv_mad_i64_i32 %0, %1, %4, %5, %0"
+        : "+&v"(nc), "=&s"(cc) : "v"(m1), "s"(n3), "v"(m0), "s"(n4));
+        col = nc;
+        m4 = (uint32_t)col;
+        // column 5: 13 + 4 products; first: - s_4 p_0 (the low limb of column 4 cancels) and its carry
+        asm("v_mad_i64_i32 %0, %1, %2, -1, %3\n\tv_ashrrev_i64 %0, 29, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, %9, %0\n\tv_mad_u64_u32 %0, %1, %10, %11, %0\n\tv_mad_u64_u32 %0, %1, %12, %13, %0\n\tv_mad_u64_u32 %0, %1, %14, %15, %0\n\tv_mad_u64_u32 %0, %1, %16, %17, %0\n\tv_mad_u64_u32 %0, %1, %18, %19, %0\n\tv_mad_u64_u32 %0, %1, %20, %21, %0\n\tv_mad_u64_u32 %0, %1, %22, %23, %0\n\tv_mad_u64_u32 %0, %1, %24, %25, %0\n\tv_mad_u64_u32 %0, %1, %26, %27, %0\n\tv_mad_u64_u32 %0, %1, %28, 1, %0"
+        : "=&v"(nc), "=&s"(cc) : "v"(m4), "v"(col), "v"(b0.v[5]), "s"(a0.v[0]), "v"(b0.v[4]), "s"(a0.v[1]), "v"(b0.v[3]), "s"(a0.v[2]), "v"(b0.v[2]), "s"(a0.v[3]), "v"(b0.v[1]), "s"(a0.v[4]), "v"(b0.v[0]), "s"(a0.v[5]), "v"(b1.v[5]), "s"(a1.v[0]), "v"(b1.v[4]), "s"(a1.v[1]), "v"(b1.v[3]), "s"(a1.v[2]), "v"(b1.v[2]), "s"(a1.v[3]), "v"(b1.v[1]), "s"(a1.v[4]), "v"(b1.v[0]), "s"(a1.v[5]), "s"(c.v[5]));
+        asm("v_mad_i64_i32 %0, %1, %2, %3, %0\n\tv_mad_i64_i32 %0, %1, %4, %5, %0\n\tv_mad_i64_i32 %0, %1, %6, %7, %0\n\tv_mad_i64_i32 %0, %1, %8, %9, %0"
+        : "+&v"(nc), "=&s"(cc) : "v"(m4), "s"(n1), "v"(m3), "s"(n2), "v"(m2), "s"(n3), "v"(m1), "s"(n4));
+        col = nc;
+        m5 = (uint32_t)col;
+        // column 6: 15 + 4 products; first: - s_5 p_0 (the low limb of column 5 cancels) and its carry
+        asm("v_mad_i64_i32 %0, %1, %2, -1, %3\n\tv_ashrrev_i64 %0, 29, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, %9, %0\n\tv_mad_u64_u32 %0, %1, %10, %11, %0\n\tv_mad_u64_u32 %0, %1, %12, %13, %0\n\tv_mad_u64_u32 %0, %1, %14, %15, %0\n\tv_mad_u64_u32 %0, %1, %16, %17, %0\n\tv_mad_u64_u32 %0, %1, %18, %19, %0\n\tv_mad_u64_u32 %0, %1, %20, %21, %0\n\tv_mad_u64_u32 %0, %1, %22, %23, %0\n\tv_mad_u64_u32 %0, %1, %24, %25, %0\n\tv_mad_u64_u32 %0, %1, %26, %27, %0\n\tv_mad_u64_u32 %0, %1, %28, %29, %0"
+        : "=&v"(nc), "=&s"(cc) : "v"(m5), "v"(col), "v"(b0.v[6]), "s"(a0.v[0]), "v"(b0.v[5]), "s"(a0.v[1]), "v"(b0.v[4]), "s"(a0.v[2]), "v"(b0.v[3]), "s"(a0.v[3]), "v"(b0.v[2]), "s"(a0.v[4]), "v"(b0.v[1]), "s"(a0.v[5]), "v"(b0.v[0]), "s"(a0.v[6]), "v"(b1.v[6]), "s"(a1.v[0]), "v"(b1.v[5]), "s"(a1.v[1]), "v"(b1.v[4]), "s"(a1.v[2]), "v"(b1.v[3]), "s"(a1.v[3]), "v"(b1.v[2]), "s"(a1.v[4]), "v"(b1.v[1]), "s"(a1.v[5]));
+        asm("v_mad_u64_u32 %0, %1, %2, %3, %0\n\tv_mad_u64_u32 %0, %1, %4, 1, %0\n\tv_mad_i64_i32 %0, %1, %5, %6, %0\n\tv_mad_i64_i32 %0, %1, %7, %8, %0\n\tv_mad_i64_i32 %0, %1, %9, %10, %0\n\tv_mad_i64_i32 %0, %1, %11, %12, %0"
+        : "+&v"(nc), "=&s"(cc) : "v"(b1.v[0]), "s"(a1.v[6]), "s"(c.v[6]), "v"(m5), "s"(n1), "v"(m4), "s"(n2), "v"(m3), "s"(n3), "v"(m2), "s"(n4));
+        col = nc;
+        m6 = (uint32_t)col;
+        // column 7: 17 + 4 products; first: - s_6 p_0 (the low limb of column 6 cancels) and its carry
+        asm("v_mad_i64_i32 %0, %1, %2, -1, %3\n\tv_ashrrev_i64 %0, 29, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, %9, %0\n\tv_mad_u64_u32 %0, %1, %10, %11, %0\n\tv_mad_u64_u32 %0, %1, %12, %13, %0\n\tv_mad_u64_u32 %0, %1, %14, %15, %0\n\tv_mad_u64_u32 %0, %1, %16, %17, %0\n\tv_mad_u64_u32 %0, %1, %18, %19, %0\n\tv_mad_u64_u32 %0, %1, %20, %21, %0\n\tv_mad_u64_u32 %0, %1, %22, %23, %0\n\tv_mad_u64_u32 %0, %1, %24, %25, %0\n\tv_mad_u64_u32 %0, %1, %26, %27, %0\n\tv_mad_u64_u32 %0, %1, %28, %29, %0"
+        : "=&v"(nc), "=&s"(cc) : "v"(m6), "v"(col), "v"(b0.v[7]), "s"(a0.v[0]), "v"(b0.v[6]), "s"(a0.v[1]), "v"(b0.v[5]), "s"(a0.v[2]), "v"(b0.v[4]), "s"(a0.v[3]), "v"(b0.v[3]), "s"(a0.v[4]), "v"(b0.v[2]), "s"(a0.v[5]), "v"(b0.v[1]), "s"(a0.v[6]), "v"(b0.v[0]), "s"(a0.v[7]), "v"(b1.v[7]), "s"(a1.v[0]), "v"(b1.v[6]), "s"(a1.v[1]), "v"(b1.v[5]), "s"(a1.v[2]), "v"(b1.v[4]), "s"(a1.v[3]), "v"(b1.v[3]), "s"(a1.v[4]));
+        asm("v_mad_u64_u32 %0, %1, %2, %3, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, 1, %0\n\tv_mad_i64_i32 %0, %1, %9, %10, %0\n\tv_mad_i64_i32 %0, %1, %11, %12, %0\n\tv_mad_i64_i32 %0, %1, %13, %14, %0\n\tv_mad_i64_i32 %0, %1, %15, %16, %0"
+        : "+&v"(nc), "=&s"(cc) : "v"(b1.v[2]), "s"(a1.v[5]), "v"(b1.v[1]), "s"(a1.v[6]), "v"(b1.v[0]), "s"(a1.v[7]), "s"(c.v[7]), "v"(m6), "s"(n1), "v"(m5), "s"(n2), "v"(m4), "s"(n3), "v"(m3), "s"(n4));
+        col = nc;
+        m7 = (uint32_t)col;
+        // column 8: 19 + 5 products; first: - s_7 p_0 (the low limb of column 7 cancels) and its carry
+        asm("v_mad_i64_i32 %0, %1, %2, -1, %3\n\tv_ashrrev_i64 %0, 29, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, %9, %0\n\tv_mad_u64_u32 %0, %1, %10, %11, %0\n\tv_mad_u64_u32 %0, %1, %12, %13, %0\n\tv_mad_u64_u32 %0, %1, %14, %15, %0\n\tv_mad_u64_u32 %0, %1, %16, %17, %0\n\tv_mad_u64_u32 %0, %1, %18, %19, %0\n\tv_mad_u64_u32 %0, %1, %20, %21, %0\n\tv_mad_u64_u32 %0, %1, %22, %23, %0\n\tv_mad_u64_u32 %0, %1, %24, %25, %0\n\tv_mad_u64_u32 %0, %1, %26, %27, %0\n\tv_mad_u64_u32 %0, %1, %28, %29, %0"
+        : "=&v"(nc), "=&s"(cc) : "v"(m7), "v"(col), "v"(b0.v[8]), "s"(a0.v[0]), "v"(b0.v[7]), "s"(a0.v[1]), "v"(b0.v[6]), "s"(a0.v[2]), "v"(b0.v[5]), "s"(a0.v[3]), "v"(b0.v[4]), "s"(a0.v[4]), "v"(b0.v[3]), "s"(a0.v[5]), "v"(b0.v[2]), "s"(a0.v[6]), "v"(b0.v[1]), "s"(a0.v[7]), "v"(b0.v[0]), "s"(a0.v[8]), "v"(b1.v[8]), "s"(a1.v[0]), "v"(b1.v[7]), "s"(a1.v[1]), "v"(b1.v[6]), "s"(a1.v[2]), "v"(b1.v[5]), "s"(a1.v[3]));
+        asm("v_mad_u64_u32 %0, %1, %2, %3, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, %9, %0\n\tv_mad_u64_u32 %0, %1, %10, %11, %0\n\tv_mad_u64_u32 %0, %1, %12, 1, %0\n\tv_mad_i64_i32 %0, %1, %13, %14, %0\n\tv_mad_i64_i32 %0, %1, %15, %16, %0\n\tv_mad_i64_i32 %0, %1, %17, %18, %0\n\tv_mad_i64_i32 %0, %1, %19, %20, %0\n\tv_mad_i64_i32 %0, %1, %21, %22, %0"
+        : "+&v"(nc), "=&s"(cc) : "v"(b1.v[4]), "s"(a1.v[4]), "v"(b1.v[3]), "s"(a1.v[5]), "v"(b1.v[2]), "s"(a1.v[6]), "v"(b1.v[1]), "s"(a1.v[7]), "v"(b1.v[0]), "s"(a1.v[8]), "s"(c.v[8]), "v"(m7), "s"(n1), "v"(m6), "s"(n2), "v"(m5), "s"(n3), "v"(m4), "s"(n4), "v"(m0), "s"(n8));
+        col = nc;
+        m8 = ((uint32_t)col & M29) | 0xC0000000u;        // (col & M29) - 2^30: the one digit with a fixed sign
+        // column 9: 17 + 5 products; first: - s_8 p_0 (the low limb of column 8 cancels) and its carry
+        asm("v_mad_i64_i32 %0, %1, %2, -1, %3\n\tv_ashrrev_i64 %0, 29, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, %9, %0\n\tv_mad_u64_u32 %0, %1, %10, %11, %0\n\tv_mad_u64_u32 %0, %1, %12, %13, %0\n\tv_mad_u64_u32 %0, %1, %14, %15, %0\n\tv_mad_u64_u32 %0, %1, %16, %17, %0\n\tv_mad_u64_u32 %0, %1, %18, %19, %0\n\tv_mad_u64_u32 %0, %1, %20, %21, %0\n\tv_mad_u64_u32 %0, %1, %22, %23, %0\n\tv_mad_u64_u32 %0, %1, %24, %25, %0\n\tv_mad_u64_u32 %0, %1, %26, %27, %0\n\tv_mad_u64_u32 %0, %1, %28, %29, %0"
+        : "=&v"(nc), "=&s"(cc) : "v"(m8), "v"(col), "v"(b0.v[8]), "s"(a0.v[1]), "v"(b0.v[7]), "s"(a0.v[2]), "v"(b0.v[6]), "s"(a0.v[3]), "v"(b0.v[5]), "s"(a0.v[4]), "v"(b0.v[4]), "s"(a0.v[5]), "v"(b0.v[3]), "s"(a0.v[6]), "v"(b0.v[2]), "s"(a0.v[7]), "v"(b0.v[1]), "s"(a0.v[8]), "v"(b1.v[8]), "s"(a1.v[1]), "v"(b1.v[7]), "s"(a1.v[2]), "v"(b1.v[6]), "s"(a1.v[3]), "v"(b1.v[5]), "s"(a1.v[4]), "v"(b1.v[4]), "s"(a1.v[5]));
+        asm("v_mad_u64_u32 %0, %1, %2, %3, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, 1, %0\n\tv_mad_i64_i32 %0, %1, %9, %10, %0\n\tv_mad_i64_i32 %0, %1, %11, %12, %0\n\tv_mad_i64_i32 %0, %1, %13, %14, %0\n\tv_mad_i64_i32 %0, %1, %15, %16, %0\n\tv_mad_i64_i32 %0, %1, %17, %18, %0"
+        : "+&v"(nc), "=&s"(cc) : "v"(b1.v[3]), "s"(a1.v[6]), "v"(b1.v[2]), "s"(a1.v[7]), "v"(b1.v[1]), "s"(a1.v[8]), "v"(t.v[0]), "v"(m8), "s"(n1), "v"(m7), "s"(n2), "v"(m6), "s"(n3), "v"(m5), "s"(n4), "v"(m1), "s"(n8));
+        col = nc;
+        r.v[0] = (uint32_t)col & M29; col = (uint64_t)((int64_t)col >> 29);
+        // column 10: 15 + 4 products
+        asm("v_mad_u64_u32 %0, %1, %2, %3, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, %9, %0\n\tv_mad_u64_u32 %0, %1, %10, %11, %0\n\tv_mad_u64_u32 %0, %1, %12, %13, %0\n\tv_mad_u64_u32 %0, %1, %14, %15, %0\n\tv_mad_u64_u32 %0, %1, %16, %17, %0\n\tv_mad_u64_u32 %0, %1, %18, %19, %0\n\tv_mad_u64_u32 %0, %1, %20, %21, %0\n\tv_mad_u64_u32 %0, %1, %22, %23, %0\n\tv_mad_u64_u32 %0, %1, %24, %25, %0\n\tv_mad_u64_u32 %0, %1, %26, %27, %0\n\tv_mad_u64_u32 %0, %1, %28, %29, %0"
+        : "+&v"(col), "=&s"(cc) : "v"(b0.v[8]), "s"(a0.v[2]), "v"(b0.v[7]), "s"(a0.v[3]), "v"(b0.v[6]), "s"(a0.v[4]), "v"(b0.v[5]), "s"(a0.v[5]), "v"(b0.v[4]), "s"(a0.v[6]), "v"(b0.v[3]), "s"(a0.v[7]), "v"(b0.v[2]), "s"(a0.v[8]), "v"(b1.v[8]), "s"(a1.v[2]), "v"(b1.v[7]), "s"(a1.v[3]), "v"(b1.v[6]), "s"(a1.v[4]), "v"(b1.v[5]), "s"(a1.v[5]), "v"(b1.v[4]), "s"(a1.v[6]), "v"(b1.v[3]), "s"(a1.v[7]), "v"(b1.v[2]), "s"(a1.v[8]));
+        asm("v_mad_u64_u32 %0, %1, %2, 1, %0\n\tv_mad_i64_i32 %0, %1, %3, %4, %0\n\tv_mad_i64_i32 %0, %1, %5, %6, %0\n\tv_mad_i64_i32 %0, %1, %7, %8, %0\n\tv_mad_i64_i32 %0, %1, %9, %10, %0"
+        : "+&v"(col), "=&s"(cc) : "v"(t.v[1]), "v"(m8), "s"(n2), "v"(m7), "s"(n3), "v"(m6), "s"(n4), "v"(m2), "s"(n8));
+        r.v[1] = (uint32_t)col & M29; col = (uint64_t)((int64_t)col >> 29);
+        // column 11: 13 + 3 products
+        asm("v_mad_u64_u32 %0, %1, %2, %3, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, %9, %0\n\tv_mad_u64_u32 %0, %1, %10, %11, %0\n\tv_mad_u64_u32 %0, %1, %12, %13, %0\n\tv_mad_u64_u32 %0, %1, %14, %15, %0\n\tv_mad_u64_u32 %0, %1, %16, %17, %0\n\tv_mad_u64_u32 %0, %1, %18, %19, %0\n\tv_mad_u64_u32 %0, %1, %20, %21, %0\n\tv_mad_u64_u32 %0, %1, %22, %23, %0\n\tv_mad_u64_u32 %0, %1, %24, %25, %0\n\tv_mad_u64_u32 %0, %1, %26, 1, %0\n\tv_mad_i64_i32 %0, %1, %27, %28, %0"
+        : "+&v"(col), "=&s"(cc) : "v"(b0.v[8]), "s"(a0.v[3]), "v"(b0.v[7]), "s"(a0.v[4]), "v"(b0.v[6]), "s"(a0.v[5]), "v"(b0.v[5]), "s"(a0.v[6]), "v"(b0.v[4]), "s"(a0.v[7]), "v"(b0.v[3]), "s"(a0.v[8]), "v"(b1.v[8]), "s"(a1.v[3]), "v"(b1.v[7]), "s"(a1.v[4]), "v"(b1.v[6]), "s"(a1.v[5]), "v"(b1.v[5]), "s"(a1.v[6]), "v"(b1.v[4]), "s"(a1.v[7]), "v"(b1.v[3]), "s"(a1.v[8]), "v"(t.v[2]), "v"(m8), "s"(n3));
+        asm("v_mad_i64_i32 %0, %1, %2, %3, %0\n\tv_mad_i64_i32 %0, %1, %4, %5, %0"
+        : "+&v"(col), "=&s"(cc) : "v"(m7), "s"(n4), "v"(m3), "s"(n8));
+        r.v[2] = (uint32_t)col & M29; col = (uint64_t)((int64_t)col >> 29);
+        // column 12: 11 + 2 products
+        asm("v_mad_u64_u32 %0, %1, %2, %3, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, %9, %0\n\tv_mad_u64_u32 %0, %1, %10, %11, %0\n\tv_mad_u64_u32 %0, %1, %12, %13, %0\n\tv_mad_u64_u32 %0, %1, %14, %15, %0\n\tv_mad_u64_u32 %0, %1, %16, %17, %0\n\tv_mad_u64_u32 %0, %1, %18, %19, %0\n\tv_mad_u64_u32 %0, %1, %20, %21, %0\n\tv_mad_u64_u32 %0, %1, %22, 1, %0\n\tv_mad_i64_i32 %0, %1, %23, %24, %0\n\tv_mad_i64_i32 %0, %1, %25, %26, %0"
         : "+&v"(col), "=&s"(cc) : "v"(b0.v[8]), "s"(a0.v[4]), "v"(b0.v[7]), "s"(a0.v[5]), "v"(b0.v[6]), "s"(a0.v[6]), "v"(b0.v[5]), "s"(a0.v[7]), "v"(b0.v[4]), "s"(a0.v[8]), "v"(b1.v[8]), "s"(a1.v[4]), "v"(b1.v[7]), "s"(a1.v[5]), "v"(b1.v[6]), "s"(a1.v[6]), "v"(b1.v[5]), "s"(a1.v[7]), "v"(b1.v[4]), "s"(a1.v[8]), "v"(t.v[3]), "v"(m8), "s"(n4), "v"(m4), "s"(n8));
-    r.v[3] = (uint32_t)col & M29; col = (uint64_t)((int64_t)col >> 29);
-    // column 13: 9 + 1 products
-    asm("v_mad_u64_u32 %0, %1, %2, %3, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, %9, %0\n\tv_mad_u64_u32 %0, %1, %10, %11, %0\n\tv_mad_u64_u32 %0, %1, %12, %13, %0\n\tv_mad_u64_u32 %0, %1, %14, %15, %0\n\tv_mad_u64_u32 %0, %1, %16, %17, %0\n\tv_mad_u64_u32 %0, %1, %18, 1, %0\n\tv_mad_i64_i32 %0, %1, %19, %20, %0"
+        r.v[3] = (uint32_t)col & M29; col = (uint64_t)((int64_t)col >> 29);
+        // column 13: 9 + 1 products
+        asm("v_mad_u64_u32 %0, %1, %2, %3, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, %9, %0\n\tv_mad_u64_u32 %0, %1, %10, %11, %0\n\tv_mad_u64_u32 %0, %1, %12, %13, %0\n\tv_mad_u64_u32 %0, %1, %14, %15, %0\n\tv_mad_u64_u32 %0, %1, %16, %17, %0\n\tv_mad_u64_u32 %0, %1, %18, 1, %0\n\tv_mad_i64_i32 %0, %1, %19, %20, %0"
         : "+&v"(col), "=&s"(cc) : "v"(b0.v[8]), "s"(a0.v[5]), "v"(b0.v[7]), "s"(a0.v[6]), "v"(b0.v[6]), "s"(a0.v[7]), "v"(b0.v[5]), "s"(a0.v[8]), "v"(b1.v[8]), "s"(a1.v[5]), "v"(b1.v[7]), "s"(a1.v[6]), "v"(b1.v[6]), "s"(a1.v[7]), "v"(b1.v[5]), "s"(a1.v[8]), "v"(t.v[4]), "v"(m5), "s"(n8));
-    r.v[4] = (uint32_t)col & M29; col = (uint64_t)((int64_t)col >> 29);
-    // column 14: 7 + 1 products
-    asm("v_mad_u64_u32 %0, %1, %2, %3, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, %9, %0\n\tv_mad_u64_u32 %0, %1, %10, %11, %0\n\tv_mad_u64_u32 %0, %1, %12, %13, %0\n\tv_mad_u64_u32 %0, %1, %14, 1, %0\n\tv_mad_i64_i32 %0, %1, %15, %16, %0"
+        r.v[4] = (uint32_t)col & M29; col = (uint64_t)((int64_t)col >> 29);
+        // column 14: 7 + 1 products
+        asm("v_mad_u64_u32 %0, %1, %2, %3, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, %9, %0\n\tv_mad_u64_u32 %0, %1, %10, %11, %0\n\tv_mad_u64_u32 %0, %1, %12, %13, %0\n\tv_mad_u64_u32 %0, %1, %14, 1, %0\n\tv_mad_i64_i32 %0, %1, %15, %16, %0"
         : "+&v"(col), "=&s"(cc) : "v"(b0.v[8]), "s"(a0.v[6]), "v"(b0.v[7]), "s"(a0.v[7]), "v"(b0.v[6]), "s"(a0.v[8]), "v"(b1.v[8]), "s"(a1.v[6]), "v"(b1.v[7]), "s"(a1.v[7]), "v"(b1.v[6]), "s"(a1.v[8]), "v"(t.v[5]), "v"(m6), "s"(n8));
-    r.v[5] = (uint32_t)col & M29; col = (uint64_t)((int64_t)col >> 29);
-    // column 15: 5 + 1 products
-    asm("v_mad_u64_u32 %0, %1, %2, %3, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, %9, %0\n\tv_mad_u64_u32 %0, %1, %10, 1, %0\n\tv_mad_i64_i32 %0, %1, %11, %12, %0"
+        r.v[5] = (uint32_t)col & M29; col = (uint64_t)((int64_t)col >> 29);
+        // column 15: 5 + 1 products
+        asm("v_mad_u64_u32 %0, %1, %2, %3, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, %7, %0\n\tv_mad_u64_u32 %0, %1, %8, %9, %0\n\tv_mad_u64_u32 %0, %1, %10, 1, %0\n\tv_mad_i64_i32 %0, %1, %11, %12, %0"
         : "+&v"(col), "=&s"(cc) : "v"(b0.v[8]), "s"(a0.v[7]), "v"(b0.v[7]), "s"(a0.v[8]), "v"(b1.v[8]), "s"(a1.v[7]), "v"(b1.v[7]), "s"(a1.v[8]), "v"(t.v[6]), "v"(m7), "s"(n8));
-    r.v[6] = (uint32_t)col & M29; col = (uint64_t)((int64_t)col >> 29);
-    // column 16: 3 + 1 products
-    asm("v_mad_u64_u32 %0, %1, %2, %3, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, 1, %0\n\tv_mad_i64_i32 %0, %1, %7, %8, %0"
+        r.v[6] = (uint32_t)col & M29; col = (uint64_t)((int64_t)col >> 29);
+        // column 16: 3 + 1 products
+        asm("v_mad_u64_u32 %0, %1, %2, %3, %0\n\tv_mad_u64_u32 %0, %1, %4, %5, %0\n\tv_mad_u64_u32 %0, %1, %6, 1, %0\n\tv_mad_i64_i32 %0, %1, %7, %8, %0"
         : "+&v"(col), "=&s"(cc) : "v"(b0.v[8]), "s"(a0.v[8]), "v"(b1.v[8]), "s"(a1.v[8]), "v"(t.v[7]), "v"(m8), "s"(n8));
-    r.v[7] = (uint32_t)col & M29; col = (uint64_t)((int64_t)col >> 29);
-    r.v[8] = (uint32_t)col + t.v[8];
-    return r;
+        r.v[7] = (uint32_t)col & M29; col = (uint64_t)((int64_t)col >> 29);
+        r.v[8] = (uint32_t)col + t.v[8];
+        return r;
+    }
 }
 // ---- END GENERATED
 #endif

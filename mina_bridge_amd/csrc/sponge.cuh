@@ -283,6 +283,46 @@ __device__ __forceinline__ void poseidon_rounds_tri(fe29_t &x, const PoseidonPar
     (void)x; (void)q; (void)tp;                                      // device-only (the host pass never calls it)
 #endif
 }
+// The same 55 rounds on the single-lane form's diagonal-normalised rows (PoseidonRows1 above; needs q1->ok): lane e carries u_e = d_e s_e and runs ROW e, so its
+// own x^7 enters unmultiplied (9 multiply-accumulates by 1 in place of a product's 81) and only the two fetched x^7 are multiplied: a[0] against the next lane's,
+// a[1] against the previous lane's, which is the order the rows are stored in.  A lane-round is 2 x 99 + 2 x 135 + 234 = 702 multiply-accumulates instead of 774,
+// with the same 18 ds_bpermute.  Round 54 takes the full matrix (d' = 1), so a permutation maps the same unscaled state to the same unscaled state as the plain
+// rounds do -- x comes in and goes out exactly as for poseidon_rounds_tri.  The row differs from lane to lane, so its 27 words sit in VGPRs (fp29.cuh
+// fe29_row1_sg<F, true>) -- the registers that hold ms / mn / mp in the plain rounds -- and are loaded a whole S-box ahead of their use, as the round constant is there.
+// Values in units of p (tools/fe29_bounds.py prove_sponge_rounds, "3-lane normalised"): from x below SPONGE29::LANES3N_STATE_MILLI_P / 1000 = 4.2 (the state enters
+// through the strict `enter` product, below 1.01): x^2 < 2.14, x^7 < 2.07, a normalised row < 4.10, the last row < 2.05.
+template <int F>
+__device__ __forceinline__ void poseidon_rounds_tri_norm(fe29_t &x, const PoseidonRows1 *__restrict__ q1, const TriPos &tp) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint32_t en = tp.e == 2u ? 0u : tp.e + 1u, ep = tp.e == 0u ? 2u : tp.e - 1u;
+    fe29_t an = q1->row[0][tp.e].a[0], ap = q1->row[0][tp.e].a[1], rc = q1->row[0][tp.e].rc;
+#pragma unroll 1
+    for (int r = 0; r < 54; ++r) {
+        const fe29_t x2 = fe29_sqr_sg<F>(x);
+        const fe29_t x4 = fe29_sqr_sg<F>(x2);
+        const fe29_t t = fe29_mul_sg<F>(fe29_mul_sg<F>(x4, x2), x);
+        const fe29_t tn = tri_bcast29(t, tp.base + en), tq = tri_bcast29(t, tp.base + ep);
+        x = fe29_row1_sg<F, true>(t, an, tn, ap, tq, rc);
+        const PoseidonRow1 *__restrict__ nx = &q1->row[r < 53 ? r + 1 : 53][tp.e];     // the NEXT round's row, a whole S-box ahead of its use
+        an = nx->a[0]; ap = nx->a[1]; rc = nx->rc;
+    }
+    // round 54: the full row, 36 words where a normalised row is 27.  They are loaded behind x^6, under the last product of the S-box, where x^2 and x^4 are dead:
+    // the lane's element passes through an empty asm together with a limb of x^6, so neither the loads nor their four addresses can be made earlier.  Loaded ahead
+    // of the S-box -- or their loop-invariant addresses formed ahead of the loop -- this one round set the register count of every kernel that runs it (+ 9 to + 12)
+    const fe29_t x2 = fe29_sqr_sg<F>(x);
+    const fe29_t x4 = fe29_sqr_sg<F>(x2);
+    fe29_t x6 = fe29_mul_sg<F>(x4, x2);
+    uint32_t e = tp.e;
+    asm volatile("" : "+v"(e), "+v"(x6.v[0]));
+    const uint32_t ln = e == 2u ? 0u : e + 1u, lp = e == 0u ? 2u : e - 1u;
+    const fe29_t ms = q1->last[e][e], mn = q1->last[e][ln], mp = q1->last[e][lp], lrc = q1->last_rc[e];
+    const fe29_t t = fe29_mul_sg<F>(x6, x);
+    const fe29_t tn = tri_bcast29(t, tp.base + en), tq = tri_bcast29(t, tp.base + ep);
+    x = fe29_dot3rc_sg<F>(ms, t, mn, tn, mp, tq, lrc);
+#else
+    (void)x; (void)q1; (void)tp;                                     // device-only (the host pass never calls it)
+#endif
+}
 // One lane per sponge (pstate_hash1_kernel): the 55 rounds on a whole state in the 29-bit form (x 2^261, below SPONGE29::LANES1_STATE_MILLI_P / 1000 p, limbs normalised).
 // No cross-lane move: a lane's three S-boxes are independent chains (instruction-level parallelism in place of the 3-lane form's ds_bpermute), and the row
 // constants are wave-uniform.  Per round 3 x 156 multiply-accumulates of S-box and 3 x 234 of row against 3 x (156 + 306) in the 3-lane form (the own term
@@ -316,14 +356,22 @@ __device__ __forceinline__ void poseidon_rounds_one(fe29_t x[3], const PoseidonR
     (void)x; (void)q1;                                               // device-only (the host pass never calls it)
 #endif
 }
-template <int F>
+// ROWS1 = false: the plain rounds whatever the tables hold -- for a kernel whose pinned register budget the second round form does not fit (the callers say which)
+template <int F, bool ROWS1 = true>
 __device__ __forceinline__ void poseidon_permute_tri(fe_t &s, const PoseidonParams *__restrict__ pp) {
     // the rounds run in the carry-free 29-bit-limb representation (fp29.cuh); state in and out as 8 x 32 Montgomery-2^256, canonical
 #if defined(__HIP_DEVICE_COMPILE__)
-    const TriPos tp = tri_pos();
+    TriPos tp = tri_pos();
+    // the lane's element passes through an empty asm: the per-lane constant addresses of BOTH round forms are then made inside this permutation.  Without it they are
+    // hoisted out of the callers' absorb loops, and a kernel carries the two forms' address registers (18 VGPRs) from its first permutation to its last
+    if (ROWS1) asm volatile("" : "+v"(tp.e));
     const PoseidonParams29 *__restrict__ q = pparams29_of(pp);
+    const PoseidonRows1 *__restrict__ q1 = prows1_of(pp);
     fe29_t x = fe29_mul_asm<F>(fe29_from_words(s), q->enter);        // x 2^256 -> x 2^261
-    poseidon_rounds_tri<F>(x, q, tp);
+    // the normalised rows where the installed tables have them (no zero on the MDS diagonal: api_sponge.hip poseidon_rows1), the plain rounds otherwise: one flag at a
+    // wave-uniform address -- a scalar load and a uniform branch per permutation, nothing per round
+    if (ROWS1 && q1->ok) poseidon_rounds_tri_norm<F>(x, q1, tp);
+    else poseidon_rounds_tri<F>(x, q, tp);
     s = fe_cond_sub_p<F>(fe29_to_words(fe29_mul_asm<F>(x, q->leave)));   // x 2^261 -> x 2^256; the strict product: 4.1 p p / 2^261 + p < 1.04 p: one conditional subtraction
 #else
     (void)s; (void)pp;                                               // device-only (the host pass never calls it)
@@ -371,9 +419,9 @@ __device__ __forceinline__ void poseidon_permute_hex(fe_t &s, const PoseidonPara
 #endif
 }
 // LANES-lane cooperative permutation / element ownership, LANES = 3 (wave-packed triples), 8 (octet) or 16
-template <int F, int LANES> __device__ __forceinline__ void poseidon_permute_coop(fe_t &s, const PoseidonParams *__restrict__ pp) {
+template <int F, int LANES, bool ROWS1 = true> __device__ __forceinline__ void poseidon_permute_coop(fe_t &s, const PoseidonParams *__restrict__ pp) {
     static_assert(LANES == 3 || LANES == 8 || LANES == 16, "the cooperative forms are 3, 8 and 16 lanes per sponge");
-    if (LANES == 16) poseidon_permute_hex<F>(s, pp); else if (LANES == 8) poseidon_permute_oct<F>(s, pp); else poseidon_permute_tri<F>(s, pp);
+    if (LANES == 16) poseidon_permute_hex<F>(s, pp); else if (LANES == 8) poseidon_permute_oct<F>(s, pp); else poseidon_permute_tri<F, ROWS1>(s, pp);
 }
 template <int LANES> __device__ __forceinline__ uint32_t coop_elem() {                 // state element this lane owns
     if (LANES == 3) return tri_pos().e;
@@ -409,18 +457,18 @@ template <int LANES> __device__ __forceinline__ uint32_t coop_role_item(uint32_t
 // mina-poseidon `ArithmeticSponge` state machine (rate 2) over base field F, Montgomery state, lane-cooperative over
 // LANES = 3 (wave-packed triples), 8 or 16 lanes: `s` = the state element this lane owns (coop_elem), the position (squeezed, count)
 // is replicated.  Absorbed values and squeezed results are replicated on all lanes of the group.
-template <int F, int LANES> struct DevSponge {
+template <int F, int LANES, bool ROWS1 = true> struct DevSponge {
     fe_t s; int squeezed; int count; const PoseidonParams *pp;
     __device__ void add_at(int pos, const fe_t &x) { if ((int)coop_elem<LANES>() == pos) s = fe_add<F>(s, x); }
     __device__ fe_t get(int pos) { return coop_get<LANES>(s, pos); }
     __device__ void absorb(const fe_t &x) {
         if (!squeezed) {
-            if (count == 2) { poseidon_permute_coop<F, LANES>(s, pp); add_at(0, x); count = 1; }
+            if (count == 2) { poseidon_permute_coop<F, LANES, ROWS1>(s, pp); add_at(0, x); count = 1; }
             else { add_at(count, x); ++count; }
         } else { add_at(0, x); squeezed = 0; count = 1; }
     }
     __device__ fe_t squeeze() {
-        if (!squeezed || count == 2) { poseidon_permute_coop<F, LANES>(s, pp); squeezed = 1; count = 1; return get(0); }
+        if (!squeezed || count == 2) { poseidon_permute_coop<F, LANES, ROWS1>(s, pp); squeezed = 1; count = 1; return get(0); }
         return get(count++);
     }
 };

@@ -334,7 +334,7 @@ def search_lazy_sets():
 
 # ------------------------------------------------------------------------------------------------ SPEC: the Poseidon rounds' lane forms (sponge.cuh)
 # state bound (units of p / 1000) each lane form keeps between rounds; MDS entries and round constants are canonical (< p)
-SPONGE = {"LANES3_STATE_MILLI_P": 4100, "LANES8_STATE_MILLI_P": 4100, "LANES16_STATE_MILLI_P": 6100, "LANES1_STATE_MILLI_P": 6300}
+SPONGE = {"LANES3_STATE_MILLI_P": 4100, "LANES8_STATE_MILLI_P": 4100, "LANES16_STATE_MILLI_P": 6100, "LANES1_STATE_MILLI_P": 6300, "LANES3N_STATE_MILLI_P": 4200}
 
 
 def prove_sponge_rounds(field: int, c=None):
@@ -380,8 +380,21 @@ def prove_sponge_rounds(field: int, c=None):
                     ("salt + body hash", entered.vmax + max(row1.vmax, full.vmax))):
         need(v < x.vmax + 1, f"1-lane: {what} = {v / p:.3f} p does not fit the state bound {x.vmax / p:.3f} p")
     out["lanes1"] = {"x2": x2, "x7": x7, "row": row1, "last_row": full, "absorbed": absorbed}
+    # 3 lanes per sponge on the NORMALISED rows (round 9, sponge.cuh poseidon_rounds_tri_norm: the transcript sponges and every other caller of poseidon_permute_tri): a
+    # lane's arithmetic is the single-lane form's -- x^2, x^4, x^6, x^7, then rounds 0 .. 53 its own x^7 unmultiplied plus two products by the row's constants
+    # (fe29_row1_sg<F, true>: the same columns, the constants in VGPRs), round 54 the full row (fe29_dot3rc_sg).  The state ENTERS through the strict product by
+    # 2^266 mod p (poseidon_permute_tri: absorbs happen outside, on the 8 x 32 words), never through a sum in the 29-bit form, so the bound to close is the row's own.
+    x = norm(c["LANES3N_STATE_MILLI_P"] * p // 1000, "state (3-lane, normalised rows)")
+    x2 = pr.sqr("3-lane normalised x^2", x, lazy="sg"); x4 = pr.sqr("3-lane normalised x^4", x2, lazy="sg"); x6 = pr.mul("3-lane normalised x^6", x4, x2, lazy="sg")
+    x7 = pr.mul("3-lane normalised x^7", x6, x, lazy="sg")
+    rown = pr.product("3-lane normalised row + rc", [(mds, x7)] * 2, lazy="sg", hi=x7, c=rc)
+    fulln = pr.product("3-lane normalised last row + rc", [(mds, x7)] * 3, lazy="sg", c=rc)
+    enteredn = pr.mul("3-lane normalised enter: Montgomery-2^256 words x 2^266", norm(p, "state element"), norm(p, "2^266 mod p"))
+    for what, v in (("a normalised round", rown.vmax), ("the last round", fulln.vmax), ("the entered state", enteredn.vmax)):
+        need(v < x.vmax + 1, f"3-lane normalised: {what} gives {v / p:.3f} p, above the state bound {x.vmax / p:.3f} p")
+    out["lanes3n"] = {"x2": x2, "x7": x7, "row": rown, "last_row": fulln, "entered": enteredn}
     # the way out of every form: one STRICT product by 2^256 mod p must land below 2^256 (fe29_to_words) and below 2 p (one conditional subtraction)
-    for key in ("LANES3_STATE_MILLI_P", "LANES8_STATE_MILLI_P", "LANES16_STATE_MILLI_P", "LANES1_STATE_MILLI_P"):
+    for key in ("LANES3_STATE_MILLI_P", "LANES8_STATE_MILLI_P", "LANES16_STATE_MILLI_P", "LANES1_STATE_MILLI_P", "LANES3N_STATE_MILLI_P"):
         leave = pr.mul(f"leave ({key})", norm(c[key] * p // 1000), norm(p, "2^256 mod p"))
         need(leave.vmax < 2 * p and leave.vmax < 1 << 256, f"{key}: leaving the permutation needs more than one conditional subtraction")
     return pr, out

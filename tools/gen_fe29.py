@@ -10,7 +10,7 @@ and the LAZY forms the chip-filling 3-lane permutation runs its rounds in (fe29_
 m_k = -col mod 2^32 is NOT masked to 29 bits (its three high bits add a multiple of p 2^(29 k): the value stays the same field element,
 the result is < a b / R + 8.0001 p instead of < a b / R + p), the accumulator starts from the first product (no zeroing), and the dot
 product takes a tenth operand c added before the reduction ((sum + c) / R: the round constant, stored times R).  Bounds: fp29.cuh.
-SIGNED-digit forms (round 5, fe29_mul_sg / fe29_sqr_sg / fe29_mul_hi_sg / fe29_sqr_hi_sg; fe29_row1_sg, the single-lane form's normalised MDS row with SGPR constants): the quotient digit of column k < 8 is the column's own low word read as an
+SIGNED-digit forms (round 5, fe29_mul_sg / fe29_sqr_sg / fe29_mul_hi_sg / fe29_sqr_hi_sg; fe29_row1_sg, the single-lane form's normalised MDS row with SGPR constants -- PER_LANE: the same row with per-lane VGPR constants for the 3-lane form): the quotient digit of column k < 8 is the column's own low word read as an
 int32 -- NO instruction makes it (the lazy forms spend a v_sub per digit, the strict ones a v_sub and a v_and) -- and it is SUBTRACTED by `v_mad_i64_i32` against the
 negated prime limbs; digit 8 is (col & M29) - 2^30 (one v_and_or), always negative, so the quotient is positive without an offset term: the result is
 T / R + (1 p, 2 p], limbs 0..7 normalised (tools/fe29_bounds.py `product_signed`; measured: tools/probes/sg_probe.hip).
@@ -202,7 +202,14 @@ def emit_signed():
                     yield (f"b{t}.v[{j}]", f"s:a{t}.v[{i}]")
         if k < L:
             yield (f"s:c.v[{k}]", 1)
-    out += ["template <int F> __device__ __forceinline__ fe29_t fe29_row1_sg(const fe29_t &t, const fe29_t &a0, const fe29_t &b0, const fe29_t &a1, const fe29_t &b1, const fe29_t &c) {"] + body_sg(row1, hi="t") + ["}"]
+    # PER_LANE (round 9, the 3-lane form: sponge.cuh poseidon_rounds_tri_norm): lane e of a triple runs row e, so a0, a1 and c differ from lane to lane and cannot ride
+    # the constant bus -- the same routine, the same column terms in the same order, with every operand in a VGPR
+    def row1v(k):
+        for term in row1(k):
+            yield tuple(x[2:] if isinstance(x, str) and x.startswith("s:") else x for x in term)
+    indent = lambda lines: ["    " + ln for ln in lines]
+    out += ["template <int F, bool PER_LANE = false> __device__ __forceinline__ fe29_t fe29_row1_sg(const fe29_t &t, const fe29_t &a0, const fe29_t &b0, const fe29_t &a1, const fe29_t &b1, const fe29_t &c) {",
+            "    if constexpr (PER_LANE) {"] + indent(body_sg(row1v, hi="t")) + ["    } else {"] + indent(body_sg(row1, hi="t")) + ["    }", "}"]
     return out
 
 
