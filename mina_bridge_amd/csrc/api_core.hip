@@ -80,28 +80,6 @@ int mb_ctx_create_view(mina_ctx *parent, mina_ctx **out) {
     mb_ctx_refresh_view(*out, parent);
     return MINA_OK;
 }
-void mb_ctx_refresh_view(mina_ctx *v, mina_ctx *p) {
-    for (int i = 0; i < 2; ++i) {
-        v->fk[i] = p->fk[i];
-        SrsState &a = v->srs[i]; const SrsState &b = p->srs[i];
-        a.depth = b.depth; a.c = b.c; a.W = b.W;
-        a.table.alias(b.table); a.table29.alias(b.table29); a.table29s.alias(b.table29s); a.h.alias(b.h);
-        // the host-side Lagrange basis is derived from the SRS: the view keeps its copy (or one it computed itself) until the parent's SRS or domain changes
-        if (a.srs_gen != b.srs_gen || a.lagrange_log2 != b.lagrange_log2 || (a.lagrange_host.empty() && !b.lagrange_host.empty())) { a.lagrange_host = b.lagrange_host; a.lagrange_log2 = b.lagrange_log2; a.srs_gen = b.srs_gen; }
-        a.lagrange_table.alias(b.lagrange_table); a.lagrange_table_n = b.lagrange_table_n; a.lagrange_table_log2 = b.lagrange_table_log2;
-        a.lagrange_digits.alias(b.lagrange_digits); a.lagrange_digits29.alias(b.lagrange_digits29); a.lagrange_digits_n = b.lagrange_digits_n;
-        v->pparams[i].alias(p->pparams[i]); v->have_pparams[i] = p->have_pparams[i]; v->pparams_surrogate[i] = p->pparams_surrogate[i]; v->pparams_rows1[i] = p->pparams_rows1[i];
-        v->merkle_salts[i].alias(p->merkle_salts[i]); v->merkle_depth[i] = p->merkle_depth[i];
-    }
-    v->kimchi_index.alias(p->kimchi_index); v->kimchi_tokens.alias(p->kimchi_tokens); v->kimchi_literals.alias(p->kimchi_literals);
-    v->have_kimchi = p->have_kimchi; v->kimchi_log2 = p->kimchi_log2; memcpy(v->kimchi_digest, p->kimchi_digest, sizeof v->kimchi_digest); memcpy(v->kimchi_comms_host, p->kimchi_comms_host, sizeof v->kimchi_comms_host);
-    v->pickles_index.alias(p->pickles_index); v->pickles_tokens.alias(p->pickles_tokens); v->pickles_literals.alias(p->pickles_literals);
-    v->have_pickles_dev = p->have_pickles_dev; v->pickles_ms_valid = p->pickles_ms_valid;
-    // borrowed: the parent frees it.  A host half the view had built for itself (step_of(view) before the parent had one) is freed first (it leaked)
-    if (v->step_host && v->step_host_free && v->step_host != p->step_host) v->step_host_free(v->step_host);
-    v->step_host = p->step_host; v->step_host_free = nullptr;
-    v->state_salts.alias(p->state_salts); v->have_state_salts = p->have_state_salts;
-}
 
 extern "C" void mina_ctx_destroy(mina_ctx *c) {
     if (!c) return;
@@ -109,12 +87,8 @@ extern "C" void mina_ctx_destroy(mina_ctx *c) {
     for (int i = 0; i < MB_DEV_HELPER0; ++i) if (c->lanes[i].stream) (void)hipStreamSynchronize(c->lanes[i].stream);
     for (hipStream_t s : c->fork_own) if (s) (void)hipStreamSynchronize(s);
     for (hipStream_t s : c->role) if (s) (void)hipStreamSynchronize(s);
-    for (int i = 0; i < 2; ++i) { c->srs[i].table.release(); c->srs[i].table29.release(); c->srs[i].table29s.release(); c->srs[i].h.release(); c->srs[i].lagrange_table.release(); c->srs[i].lagrange_digits.release(); c->srs[i].lagrange_digits29.release(); c->pparams[i].release(); c->merkle_salts[i].release(); }
-    c->state_salts.release(); c->acct_defaults.release(); c->dedup_totals.release(); c->kimchi_index.release(); c->kimchi_tokens.release(); c->kimchi_literals.release();
-    c->pickles_index.release(); c->pickles_tokens.release(); c->pickles_literals.release();
     if (c->step_host && c->step_host_free) c->step_host_free(c->step_host);
     c->step_host = nullptr;
-    for (int i = 0; i < MB_MAX_LANES; ++i) c->lanes[i].release_all();
     for (auto &r : c->prof.recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
     for (int i = 0; i < MB_MAX_LANES; ++i) {
         Lane &L = c->lanes[i];

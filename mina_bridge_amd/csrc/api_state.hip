@@ -257,7 +257,6 @@ static int ensure_state_salts(mina_ctx *c) {
     mb::prefix_salt_kernel<FIELD_FP><<<1, 64, 0, c->L->stream>>>(MB_N_PREFIX_SALTS, c->fk[FIELD_FP], c->pparams[FIELD_FP].as<PoseidonParams>(), tmp.as<uint32_t>(), c->state_salts.as<fe_t>());
     HIPC(hipGetLastError());
     HIPC(hipStreamSynchronize(c->L->stream));
-    tmp.release();
     c->have_state_salts = true;
     return MINA_OK;
 }

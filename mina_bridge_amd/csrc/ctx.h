@@ -24,10 +24,9 @@ using namespace mb;
 struct mina_ctx;
 // A VIEW of a context (round 5): its own lanes, streams and workspaces, while everything INSTALLED -- field constants, both SRS with their window tables, Poseidon
 // tables, salts, verifier / step index -- is borrowed from the parent (no second copy of the tables).  The boundary runs the culprit search of a failed chunk on a
-// view, so that the search needs neither the parent's lock nor a drained device (api_verify.hip Device::sc).  `refresh` re-reads the parent's installs; the caller
-// holds whatever serialises installs on the parent.  Destroy the view BEFORE the parent.
+// view, so that the search needs neither the parent's lock nor a drained device (api_verify.hip Device::sc).  mb_ctx_refresh_view (below mina_ctx) re-reads the
+// parent's installs; the caller holds whatever serialises installs on the parent.  Destroy the view BEFORE the parent.
 int mb_ctx_create_view(mina_ctx *parent, mina_ctx **out);
-void mb_ctx_refresh_view(mina_ctx *view, mina_ctx *parent);
 int mb_fail(int code, const std::string &msg);      // records the thread-local error text, returns code
 mina_verify_tuning mb_tune();                        // the process-wide tuning (api_core.hip; mina_verify_configure_ex), by value
 #define fail mb_fail
@@ -39,9 +38,14 @@ mina_verify_tuning mb_tune();                        // the process-wide tuning 
             return fail(MINA_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e__));         \
     } while (0)
 
+// Device memory (DevBuf) and page-locked host memory (PinnedBuf) that free themselves: whatever holds one by value needs no teardown list.  Two rules:
+//   NO STATIC-STORAGE OBJECTS.  An object with static storage duration never holds one by value: its destructor would call into the runtime after the runtime has
+//     shut down at process exit.  Every holder is a heap object (new mina_ctx, the boundary's new Device) or a local.
+//   VIEW BEFORE PARENT.  A view context (Installed::borrow_from) is destroyed before the context it borrows from.
 struct DevBuf {
     void *p = nullptr; size_t cap = 0;
-    bool borrowed = false;             // the memory belongs to another context's DevBuf (a VIEW context: mb_ctx_refresh_view): never freed here; outgrown -> replaced by an own allocation
+    bool borrowed = false;             // the memory belongs to another context's DevBuf (a VIEW context: Installed::borrow_from): never freed here; outgrown -> replaced by an own allocation
+    DevBuf() = default; DevBuf(const DevBuf &) = delete; DevBuf &operator=(const DevBuf &) = delete; ~DevBuf() { release(); }
     int ensure(size_t bytes) {
         if (bytes <= cap) return MINA_OK;
         if (p) { if (!borrowed && hipFree(p) != hipSuccess) return MINA_ERR_HIP; p = nullptr; cap = 0; borrowed = false; }
@@ -57,6 +61,7 @@ struct DevBuf {
 // page-locked host staging (grow-only): packing straight into it makes the H2D copy a real DMA at PCIe speed
 struct PinnedBuf {
     void *p = nullptr; size_t cap = 0;
+    PinnedBuf() = default; PinnedBuf(const PinnedBuf &) = delete; PinnedBuf &operator=(const PinnedBuf &) = delete; ~PinnedBuf() { release(); }
     int ensure(size_t bytes) {
         if (bytes <= cap) return MINA_OK;
         if (p) { (void)hipHostFree(p); p = nullptr; cap = 0; }
@@ -83,6 +88,15 @@ struct SrsState {
     DevBuf lagrange_digits;            // d * 2^(8w) * L_i, d = 1..128, of the first lagrange_digits_n (<= 64) basis points (lagrange.cuh: direct commitments)
     uint32_t lagrange_digits_n = 0;
     DevBuf lagrange_digits29;          // ... its 2^261-domain twin: the direct commitments' mixed adds run on 29-bit limbs (lagrange.cuh pubcomm_direct29_kernel)
+    inline void borrow_from(const SrsState &b) {    // a view context's (Installed::borrow_from): every field above, the tables aliased
+        SrsState &a = *this;
+        a.depth = b.depth; a.c = b.c; a.W = b.W;
+        a.table.alias(b.table); a.table29.alias(b.table29); a.table29s.alias(b.table29s); a.h.alias(b.h);
+        // the host-side Lagrange basis is derived from the SRS: the view keeps its copy (or one it computed itself) until the parent's SRS or domain changes
+        if (a.srs_gen != b.srs_gen || a.lagrange_log2 != b.lagrange_log2 || (a.lagrange_host.empty() && !b.lagrange_host.empty())) { a.lagrange_host = b.lagrange_host; a.lagrange_log2 = b.lagrange_log2; a.srs_gen = b.srs_gen; }
+        a.lagrange_table.alias(b.lagrange_table); a.lagrange_table_n = b.lagrange_table_n; a.lagrange_table_log2 = b.lagrange_table_log2;
+        a.lagrange_digits.alias(b.lagrange_digits); a.lagrange_digits29.alias(b.lagrange_digits29); a.lagrange_digits_n = b.lagrange_digits_n;
+    }
 };
 
 struct MsmWorkspace {
@@ -118,19 +132,6 @@ struct Lane {
     DevBuf ac_ws, ac_in;                     // the device path of a Proof-of-Account job (account_pack.cuh; api_account_dev.hip): its workspace (AccountWs), the uploaded bytes + verdict words of a boundary call
     DevBuf gs_tab, gs_folded, gs_xa, gs_xb, gs_chals, gs_points, gs_bad, gs_flags;   // the grouped culprit search (api_ipa.hip mb_*_check_parts): segment tables, one folded vector and two sums per part, the accumulator leg's challenges / checked points / per-proof malformed words, one flag per part
     DevBuf kc_state, kc_pos, kc_cip, kc_pts, kc_v, kc_u, kc_comms, kc_xfer, kc_pch, pk_xe, pk_pub, pk_ok;                  // kimchi to_batch output rows (api_kimchi.hip)
-    void release_all() {
-        MsmWorkspace &w = ws;
-        DevBuf *all[] = {&w.scalars, &w.points, &w.points29, &w.ekey, &w.eval, &w.eoff, &w.count, &w.start, &w.task_start, &w.rem_pos, &w.rem_bucket, &w.info, &w.sorted, &w.partial, &w.heavy, &w.order, &w.redo, &w.ghist, &w.stage,
-                         &w.buckets, &w.buckets29, &w.seg_bad, &w.red_r, &w.red_ws, &w.red2_r, &w.red2_w, &w.set_total, &w.out_words, &w.out_xyzz, &tmp_a, &tmp_b, &tmp_c, &tmp_d,
-                         &bp_ltab, &bp_htab, &bp_partial, &bp_ldig, &bp_hdig, &bp_colsum, &ipa_chals, &ipa_folded, &ipa_xyzz_a, &ipa_xyzz_b, &ipa_points, &ipa_scalars,
-                         &ipa_sigma, &ipa_in_a, &ipa_in_b, &ipa_in_c, &ipa_verdict, &ipa_xfer, &ipa_shared, &ipa_shared_off, &acc_rho_scaled,
-                         &st_ok, &st_hashes, &st_pub_xyzz, &st_pubcomm, &st_flags, &st_in, &st_verdicts,
-                         &dd_rep, &dd_uniq, &dd_table, &dd_counts, &pk_off, &pk_len, &pk_status, &pk_info, &pk_fmt, &ac_ws, &ac_in,
-                         &gs_tab, &gs_folded, &gs_xa, &gs_xb, &gs_chals, &gs_points, &gs_bad, &gs_flags,
-                         &kc_state, &kc_pos, &kc_cip, &kc_pts, &kc_v, &kc_u, &kc_comms, &kc_xfer, &kc_pch, &pk_xe, &pk_pub, &pk_ok};
-        for (DevBuf *b : all) b->release();
-        host_stage.release();
-    }
 };
 // ---- how the legs of pipelined device-resident jobs are laid over streams (state_job.hip dev_fork_lanes).  Streams only run side by side on separate hardware
 // queues, a stream's event wait is a barrier in the queue it shares, and the process has GPU_MAX_HW_QUEUES of them, one of which serves the caller's null stream:
@@ -169,7 +170,39 @@ static constexpr int MB_DEV_HELPER0 = MB_PIPE_LANES + 3 * 16;   // helper lanes 
 static constexpr int MB_MAX_LANES = MB_DEV_HELPER0 + 3 * MB_DEV_FORK_MAX;  // pipeline lanes + the helper lanes of the boundary's 16 slots (api_verify.hip: legs of slot s on lanes 32 + 3 s ..) + those of the forked device-resident jobs
 enum : int { MB_SALT_PSTATE_BODY = 0, MB_SALT_PSTATE, MB_SALT_ACCOUNT, MB_SALT_ZKAPP_ACCOUNT, MB_SALT_ZKAPP_URI, MB_SALT_SIDE_LOADED_VK, MB_N_PREFIX_SALTS };
 
-struct mina_ctx {
+// Everything INSTALLED on a context: what a view context borrows from its parent -- borrow_from, directly under the fields it must stay in step with.
+struct Installed {
+    FieldK fk[2];
+    SrsState srs[2];
+    DevBuf pparams[2]; bool have_pparams[2] = {false, false};
+    bool pparams_surrogate[2] = {false, false};                  // the installed Poseidon tables are the library's UNPINNED surrogate set
+    bool pparams_rows1[2] = {false, false};                      // the installed tables have the single-lane form's normalised rows (sponge.cuh PoseidonRows1: no zero on the MDS diagonal)
+    DevBuf merkle_salts[2]; uint32_t merkle_depth[2] = {0, 0};   // salted initial states of the Merkle hash per height
+    DevBuf kimchi_index, kimchi_tokens, kimchi_literals; bool have_kimchi = false; uint32_t kimchi_log2 = 0; uint8_t kimchi_digest[32] = {0};   // installed wrap verifier index
+    uint8_t kimchi_comms_host[28 * 64] = {0};   // its commitments as installed: sigma 7, coefficients 15, selectors 6 (messages_for_next_step_proof hashes them)
+    DevBuf pickles_index, pickles_tokens, pickles_literals; bool have_pickles_dev = false, pickles_ms_valid = false;   // installed step index (api_pickles.hip); ms = the Tick sponge after the wrap index commitments
+    void *step_host = nullptr; void (*step_host_free)(void *) = nullptr;   // host half of the installed step index (api_pickles.hip), owned by the context
+    DevBuf state_salts; bool have_state_salts = false;           // salted initial states of the named hash prefixes (Fp): MB_SALT_*
+    inline void borrow_from(const Installed &p) {
+        Installed *const v = this;
+        for (int i = 0; i < 2; ++i) {
+            v->fk[i] = p.fk[i];
+            v->srs[i].borrow_from(p.srs[i]);
+            v->pparams[i].alias(p.pparams[i]); v->have_pparams[i] = p.have_pparams[i]; v->pparams_surrogate[i] = p.pparams_surrogate[i]; v->pparams_rows1[i] = p.pparams_rows1[i];
+            v->merkle_salts[i].alias(p.merkle_salts[i]); v->merkle_depth[i] = p.merkle_depth[i];
+        }
+        v->kimchi_index.alias(p.kimchi_index); v->kimchi_tokens.alias(p.kimchi_tokens); v->kimchi_literals.alias(p.kimchi_literals);
+        v->have_kimchi = p.have_kimchi; v->kimchi_log2 = p.kimchi_log2; memcpy(v->kimchi_digest, p.kimchi_digest, sizeof v->kimchi_digest); memcpy(v->kimchi_comms_host, p.kimchi_comms_host, sizeof v->kimchi_comms_host);
+        v->pickles_index.alias(p.pickles_index); v->pickles_tokens.alias(p.pickles_tokens); v->pickles_literals.alias(p.pickles_literals);
+        v->have_pickles_dev = p.have_pickles_dev; v->pickles_ms_valid = p.pickles_ms_valid;
+        // borrowed: the parent frees it.  A host half the view had built for itself (step_of(view) before the parent had one) is freed first (it leaked)
+        if (v->step_host && v->step_host_free && v->step_host != p.step_host) v->step_host_free(v->step_host);
+        v->step_host = p.step_host; v->step_host_free = nullptr;
+        v->state_salts.alias(p.state_salts); v->have_state_salts = p.have_state_salts;
+    }
+};
+
+struct mina_ctx : Installed {
     int device = 0;
     ProfState prof;
     Lane lanes[MB_MAX_LANES];
@@ -178,17 +211,6 @@ struct mina_ctx {
     int pinned = -1;                 // >= 0: every `_dev` entry point runs on this lane (mina_ctx_pin_lane): a caller that queues its own work on that lane's stream needs no host synchronisation
     Lane *L = nullptr;               // lane the current call runs on
     Lane *ipa_rows = nullptr; uint32_t ipa_rows_batch = 0, ipa_rows_k = 0, ipa_rows_per = 0, ipa_rows_nshared = 0; int ipa_rows_curve = -1;   // lane holding the prepared rows of the last folded opening check (mb_ipa_recheck_rows)
-    FieldK fk[2];
-    SrsState srs[2];
-    DevBuf pparams[2]; bool have_pparams[2] = {false, false};
-    DevBuf merkle_salts[2]; uint32_t merkle_depth[2] = {0, 0};   // salted initial states of the Merkle hash per height
-    DevBuf kimchi_index, kimchi_tokens, kimchi_literals; bool have_kimchi = false; uint32_t kimchi_log2 = 0; uint8_t kimchi_digest[32] = {0};   // installed wrap verifier index
-    uint8_t kimchi_comms_host[28 * 64] = {0};   // its commitments as installed: sigma 7, coefficients 15, selectors 6 (messages_for_next_step_proof hashes them)
-    DevBuf pickles_index, pickles_tokens, pickles_literals; bool have_pickles_dev = false, pickles_ms_valid = false;   // installed step index (api_pickles.hip); ms = the Tick sponge after the wrap index commitments
-    void *step_host = nullptr; void (*step_host_free)(void *) = nullptr;   // host half of the installed step index (api_pickles.hip), owned by the context
-    bool pparams_surrogate[2] = {false, false};                  // the installed Poseidon tables are the library's UNPINNED surrogate set
-    bool pparams_rows1[2] = {false, false};                      // the installed tables have the single-lane form's normalised rows (sponge.cuh PoseidonRows1: no zero on the MDS diagonal)
-    DevBuf state_salts; bool have_state_salts = false;           // salted initial states of the named hash prefixes (Fp): MB_SALT_*
     bool is_view = false;            // a view of another context (mb_ctx_create_view: the culprit search's): creates no stream beyond its lane 0 -- its lanes 1 .. 3 borrow the failed chunk's, and the opening check's side stream is off
     bool state_dedup = false;        // the protocol-state leg of a job hashes each distinct record once (mina_ctx_set_state_dedup; api_state.hip pstate_hash_dedup_dev)
     DevBuf dedup_totals; uint64_t dedup_states = 0;   // mina_ctx_state_dedup_stats: {distinct, collisions} summed on the device by the legs' scan kernels, the states counted as they are queued
@@ -220,6 +242,7 @@ struct mina_ctx {
     void use_lane0() { L = &lanes[0]; }
     void next_lane() { L = pinned >= 0 ? &lanes[pinned] : &lanes[rr++ % (unsigned)nlanes]; }
 };
+static inline void mb_ctx_refresh_view(mina_ctx *view, mina_ctx *parent) { view->borrow_from(*parent); }
 
 // waits for everything the `_dev` entry points have queued: the pipeline lanes and, for jobs that ran under plan B, the role streams
 static inline hipError_t mb_ctx_wait_all(mina_ctx *c) {

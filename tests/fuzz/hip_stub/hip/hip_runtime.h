@@ -3,6 +3,7 @@
 // Streams execute their commands at once on the calling thread (a valid in-order schedule of every stream), events are already complete when recorded, device
 // memory is host memory.  Test infrastructure: never part of the product build (mina_bridge_amd/build.py uses hipcc and the real runtime).
 #pragma once
+#include <atomic>
 #include <cstddef>
 #include <cstdint>
 #include <cstdlib>
@@ -67,12 +68,17 @@ static inline hipError_t hipSetDevice(int) { return hipSuccess; }
 static inline hipError_t hipGetDeviceCount(int *n) { *n = 1; return hipSuccess; }
 static inline hipError_t hipDeviceGetAttribute(int *v, int, int) { *v = 256; return hipSuccess; }
 static inline hipError_t hipDeviceSynchronize() { MB_TRACE("hipDeviceSynchronize\n"); return hipSuccess; }
-static inline hipError_t mb_stub_alloc(const char *what, void **p, size_t n) { *p = calloc(1, n ? n : 1); if (!*p) return hipErrorInvalidValue; MB_TRACE_ALLOC(what, *p, n); return hipSuccess; }
+// Live allocations: hipMalloc + hipHostMalloc less the frees of non-null pointers, over every translation unit (atomic: the ThreadSanitizer build counts too).  A
+// program that has destroyed everything checks mb_stub_live_allocs() == 0: a buffer nobody freed shows without a list of buffers.
+inline std::atomic<long> &mb_stub_live() { static std::atomic<long> n{0}; return n; }
+static inline long mb_stub_live_allocs() { return mb_stub_live().load(); }
+static inline hipError_t mb_stub_alloc(const char *what, void **p, size_t n) { *p = calloc(1, n ? n : 1); if (!*p) return hipErrorInvalidValue; mb_stub_live().fetch_add(1); MB_TRACE_ALLOC(what, *p, n); return hipSuccess; }
+static inline void mb_stub_free(const char *what, void *p) { if (p) mb_stub_live().fetch_sub(1); MB_TRACE_FREE(what, p); free(p); }
 static inline hipError_t hipMalloc(void **p, size_t n) { return mb_stub_alloc("hipMalloc", p, n); }
 template <class T> static inline hipError_t hipMalloc(T **p, size_t n) { return hipMalloc((void **)p, n); }
-static inline hipError_t hipFree(void *p) { MB_TRACE_FREE("hipFree", p); free(p); return hipSuccess; }
+static inline hipError_t hipFree(void *p) { mb_stub_free("hipFree", p); return hipSuccess; }
 static inline hipError_t hipHostMalloc(void **p, size_t n, unsigned = 0) { return mb_stub_alloc("hipHostMalloc", p, n); }
-static inline hipError_t hipHostFree(void *p) { MB_TRACE_FREE("hipHostFree", p); free(p); return hipSuccess; }
+static inline hipError_t hipHostFree(void *p) { mb_stub_free("hipHostFree", p); return hipSuccess; }
 static inline hipError_t hipMemcpy(void *d, const void *s, size_t n, hipMemcpyKind k) { MB_TRACE("hipMemcpy %s %zu %s <- %s\n", mb_stub_kind[k], n, mb_stub_mem(d).c_str(), mb_stub_mem(s).c_str()); memcpy(d, s, n); return hipSuccess; }
 static inline hipError_t hipMemcpyAsync(void *d, const void *s, size_t n, hipMemcpyKind k, hipStream_t st = nullptr) {
     MB_TRACE("hipMemcpyAsync %s %zu %s <- %s on s%d\n", mb_stub_kind[k], n, mb_stub_mem(d).c_str(), mb_stub_mem(s).c_str(), mb_stub_id(st)); memcpy(d, s, n); return hipSuccess;

@@ -41,8 +41,8 @@ extern "C" int mina_ctx_create(int device_id, mina_ctx **out) {
     c->use_lane0(); *out = c; return MINA_OK;
 }
 int mb_ctx_create_view(mina_ctx *parent, mina_ctx **out) { int rc = mina_ctx_create(parent->device, out); if (!rc) { (*out)->is_view = true; mb_ctx_refresh_view(*out, parent); } return rc; }
-void mb_ctx_refresh_view(mina_ctx *v, mina_ctx *p) { v->have_kimchi = p->have_kimchi; v->kimchi_log2 = p->kimchi_log2; v->have_state_salts = p->have_state_salts; }   // (read under the parent's lock by the caller)
-extern "C" void mina_ctx_destroy(mina_ctx *c) { if (!c) return; for (auto &l : c->lanes) { if (l.stream) (void)hipStreamDestroy(l.stream); l.release_all(); } delete c; }
+// (mb_ctx_refresh_view is the product's own, ctx.h: the stub installers below set flags only, so it aliases empty buffers; the caller holds the locks that serialise installs)
+extern "C" void mina_ctx_destroy(mina_ctx *c) { if (!c) return; for (auto &l : c->lanes) if (l.stream) (void)hipStreamDestroy(l.stream); delete c; }
 extern "C" int mina_poseidon_set_params(mina_ctx *c, int field, const uint8_t *) { c->have_pparams[field] = true; c->pparams_surrogate[field] = false; return MINA_OK; }
 extern "C" int mina_srs_create(mina_ctx *c, int curve, uint32_t depth) { c->srs[curve].depth = depth; return MINA_OK; }
 int mb_poseidon_env_params(mina_ctx *) { return MINA_OK; }
@@ -186,6 +186,7 @@ static int run_trace(const std::vector<std::string> &proofs, const std::vector<s
     MB_TRACE("# mina_verify_shutdown\n");
     mina_verify_configure_ex(nullptr);
     mina_verify_shutdown();
+    if (mb_stub_live_allocs()) { fprintf(stderr, "trace: %ld allocations still live after mina_verify_shutdown\n", mb_stub_live_allocs()); return 1; }
     fprintf(stderr, "trace: %ld device jobs, %ld culprit searches, %d failures\n", g_jobs.load(), g_searches.load(), failed);
     return (failed || g_searches.load() == 0 || g_jobs.load() == 0) ? 1 : 0;
 }
@@ -280,6 +281,7 @@ int main(int argc, char **argv) {
     stop.store(true);
     for (auto &t : th) t.join();
     mina_verify_shutdown();
+    if (mb_stub_live_allocs()) { fprintf(stderr, "%ld allocations still live after mina_verify_shutdown\n", mb_stub_live_allocs()); return 1; }
     printf("{\"seconds\": %.1f, \"state_callers\": %d, \"account_callers\": %d, \"calls\": %ld, \"verdicts\": %ld, \"device_jobs\": %ld, \"culprit_searches\": %ld, \"account_jobs\": %ld, \"installs\": %ld, "
            "\"wrong_verdicts\": %ld, \"failed_calls\": %ld}\n", seconds, n_state, n_acct, calls.load(), verdicts.load(), g_jobs.load(), g_searches.load(), g_account_jobs.load(), g_installs.load(), wrong.load(), errors.load());
     return (wrong.load() || errors.load() || g_searches.load() == 0 || g_jobs.load() == 0) ? 1 : 0;

@@ -20,7 +20,9 @@ def test_boundary_queues_the_same_runtime_calls_in_the_same_order():
     the same run after run (five runs compared when it was recorded).  Done = the log equals tests/golden/boundary_call_trace.txt line for line.
 
     The golden file was recorded from the commit BEFORE run_device_shape became ShapePass, except the tail behind `# mina_verify_shutdown`, recorded after it: the
-    teardown moved into Slot::destroy, which also frees pk_host / pk_dev (the stand-in context never allocates them, so the tail came out the same).  A change
+    teardown moved into Slot::destroy, which also frees pk_host / pk_dev (the stand-in context never allocates them, so the tail came out the same).  The tail was
+    recorded once more when the contexts' buffers began to free themselves: their hipFree lines moved behind the stream destruction, and `hipFree m65+0` (the
+    context's dedup_totals, which the stand-in mina_ctx_destroy had forgotten) is new -- with the free lines taken out, the old and the new file are the same.  A change
     that moves the queueing on purpose records the file again (`tests/fuzz/trace_boundary <the two fixtures> trace`, behind the first line); its diff then shows
     what moved."""
     subprocess.check_call(["make", "-C", FUZZ, "-s", "trace"])
