@@ -145,9 +145,10 @@ def polish_evaluate(tokens, index: VerifierIndex, pt: int, evals, consts: dict, 
 
 
 # ------------------------------------------------------------------------------------------------ verifier: oracles + to_batch
-def oracles_and_batch(index: VerifierIndex, proof: dict, public_inputs, pp_base, pp_scalar, g_bytes, h):
+def oracles_and_batch(index: VerifierIndex, proof: dict, public_inputs, pp_base, pp_scalar, g_bytes, h, ft_comm: bool = True):
     """proof: {w_comm[15], z_comm, t_comm[7], evals[43] of (zeta, zeta_omega), ft_eval1, prev: [(chals, comm)], opening}.
-    Returns every intermediate (`o`) and the `ipa_verify_batch` entry."""
+    Returns every intermediate (`o`) and the `ipa_verify_batch` entry.  ft_comm=False leaves the chunked ft_comm out (None in its place in `comms`): its
+    scalar multiplications are most of the cost, and the scalars (ft_eval0, the combined inner product) do not depend on it."""
     curve = index.curve
     r, m = R.scalar_modulus(curve), R.base_modulus(curve)
     endo_r = R.endo_r(curve)
@@ -227,11 +228,14 @@ def oracles_and_batch(index: VerifierIndex, proof: dict, public_inputs, pp_base,
         ps = ps * ((gamma + beta * S(i) + W(i)) % r) % r
     ps = (-ps) % r
     o["perm_scalar"] = ps
-    f_comm = R.scalar_mul(ps, index.sigma_comm[PERMUTS - 1], m)
-    tc = None
-    for t in reversed(proof["t_comm"]):
-        tc = R.add(R.scalar_mul(zeta1, tc, m) if tc is not None else None, t, m)
-    ft_comm = R.add(f_comm, R.neg(R.scalar_mul((zeta1 - 1) % r, tc, m), m) if tc is not None else None, m)
+    if ft_comm:
+        f_comm = R.scalar_mul(ps, index.sigma_comm[PERMUTS - 1], m)
+        tc = None
+        for t in reversed(proof["t_comm"]):
+            tc = R.add(R.scalar_mul(zeta1, tc, m) if tc is not None else None, t, m)
+        ft_comm = R.add(f_comm, R.neg(R.scalar_mul((zeta1 - 1) % r, tc, m), m) if tc is not None else None, m)
+    else:
+        ft_comm = None
     o["ft_comm"] = ft_comm
     # evaluation list
     comms, evals = [], []

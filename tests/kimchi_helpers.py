@@ -17,8 +17,10 @@ def encode_tokens(tokens) -> bytes:
         elif op == K.T_CELL:
             out += bytes([t[1], t[2]])
         elif op == K.T_POW:
+            if not 0 <= t[1] < 1 << 64: raise ValueError("POW exponent %r does not fit the byte-code's 64 bits" % (t[1],))
             out += struct.pack("<Q", t[1])
         elif op == K.T_LAGRANGE:
+            if not -(1 << 31) <= t[1] < 1 << 31: raise ValueError("UNNORMALIZED_LAGRANGE offset %r does not fit the byte-code's signed 32 bits" % (t[1],))
             out += struct.pack("<i", t[1])
         elif op == K.T_LOAD:
             out += struct.pack("<H", t[1])
