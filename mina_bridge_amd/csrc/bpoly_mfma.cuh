@@ -8,7 +8,9 @@
 //   * every table entry is written as 32 balanced base-256 digits d_i in [-128, 127] (exact: sum d_i 256^i = the 255-bit integer),
 //     one int8 plane per digit, the batch index contiguous (the MFMA's K dimension);
 //   * C'[(hi, a)][(lo, c)] = sum_b Hd[(hi, a)][b] * Ld[(lo, c)][b] is one int8 GEMM with M' = 32 nh, N' = 32 nl, K = B
-//     (`v_mfma_i32_32x32x32_i8`; |C'| <= B * 2^14 < 2^31 for B < 2^17);
+//     (`v_mfma_i32_32x32x32_i8`; the largest |C'| is -128 * -128 * B = B * 2^14, every digit of both rows -128 in every column: 2^31 - 2^14 at
+//     B = 2^17 - 1, which an int32 holds, and 2^31 at B = 2^17, which it does not -- `batch < (1u << 17)` in `run_bpoly_fold` (api_sponge.hip) is the guard that
+//     keeps larger batches on the VALU kernels; the most negative C' is 127 * -128 * B, inside the range wherever the positive bound is);
 //   * a 32 x 32 accumulator tile is exactly the digit-by-digit product block of one (hi, lo) pair: its 63 anti-diagonal sums
 //     (a + c = k) are the base-256 columns of the 521-bit integer T = sum_b H_b[hi] L_b[lo]; the epilogue adds them into 64-bit bins
 //     in LDS and writes 63 sums per output instead of the 1024 products;

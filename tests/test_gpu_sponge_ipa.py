@@ -55,8 +55,11 @@ def test_b_poly_fold(ctx, oracle, field, k, batch):
 @pytest.mark.parametrize("k,batch", [(7, 300), (9, 1030), (2, 256), (12, 257)])
 def test_b_poly_fold_matrix_core_path(ctx, oracle, field, k, batch):
     """batches >= 256 take the int8 MFMA field-GEMM (bpoly_mfma.cuh): balanced base-256 digit planes, 32x32x32 tiles, anti-diagonal
-    sums, one reduction per output.  Bit-exact vs the CPU fold, with extreme values in the mix (0, 1, p - 1, 2^254 - 1 as challenges
-    and weights) so that every digit carry and the signed columns are exercised; batch sizes off the K-tile (padding columns)."""
+    sums, one reduction per output.  Bit-exact vs the CPU fold on random inputs with extreme PLAIN values in the mix (0, 1, p - 1,
+    2^254 - 1 as challenges and weights); batch sizes off the K-tile (padding columns).  The kernels cut the Montgomery image of a
+    table entry into digits, so apart from 0 these extremes give random digits like any other value: the digit corners (runs of
+    -128 and +127, carries through all 32 digits, top byte 0x40), the accumulator bound at batch 2^17 - 1, the small shapes and the
+    pad columns after another call are in tests/test_gpu_bpoly_mfma_edges.py, on inputs solved for their images."""
     m = MODS[field]
     chals = rand_scalars(batch * k, m, seed=160 + k + batch)
     w = rand_scalars(batch, m, seed=161)
