@@ -65,28 +65,6 @@ extern "C" int mina_field_sum_rows_dev(mina_ctx *c, int field, size_t rows, size
     return MINA_OK;
 }
 
-extern "C" int mina_msm_srs_range_dev(mina_ctx *c, int curve, uint32_t first, size_t n, const void *d_scalars, void *d_out) {
-    if (!c || !d_scalars || !d_out) return fail(MINA_ERR_ARG, "null argument");
-    if (curve != 0 && curve != 1) return fail(MINA_ERR_ARG, "bad curve");
-    if (n == 0 || n > 0xffffffffu) return fail(MINA_ERR_ARG, "bad n");
-    HIPC(hipSetDevice(c->device));
-    c->next_lane();
-    return mb_msm_fixed(c, curve, (uint32_t)n, (const uint32_t *)d_scalars, (uint32_t *)d_out, nullptr, first);
-}
-
-extern "C" int mina_msm_dev(mina_ctx *c, int curve, size_t n, const void *d_bases, const void *d_scalars, void *d_out) {
-    if (!c || !d_bases || !d_scalars || !d_out) return fail(MINA_ERR_ARG, "null argument");
-    if (curve != 0 && curve != 1) return fail(MINA_ERR_ARG, "bad curve");
-    if (n == 0 || n > (1u << 24)) return fail(MINA_ERR_ARG, "bad n");
-    HIPC(hipSetDevice(c->device));
-    c->next_lane();
-    int rc;
-    MsmWorkspace &w = c->L->ws;
-    if ((rc = w.points.ensure(n * sizeof(affine_t)))) return rc;
-    DISPATCH_FIELD(base_field_of(curve), { points_to_mont_kernel<F_><<<cdiv(n, 256), 256, 0, c->L->stream>>>((uint32_t)n, (const uint32_t *)d_bases, c->fk[F_].r2, w.points.as<affine_t>()); });
-    return mb_msm_variable(c, curve, (uint32_t)n, (const uint32_t *)d_scalars, w.points.p, (uint32_t *)d_out, nullptr);
-}
-
 extern "C" int mina_points_sum_dev(mina_ctx *c, int curve, size_t n, const void *d_records, void *d_out) {
     if (!c || !d_records || !d_out) return fail(MINA_ERR_ARG, "null argument");
     if (curve != 0 && curve != 1) return fail(MINA_ERR_ARG, "bad curve");

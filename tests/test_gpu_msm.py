@@ -419,3 +419,34 @@ def test_29_bit_group_law_on_table_points_at_the_top_of_the_field(oracle, srs_or
                     assert (c.msm_srs_multi(curve, np.stack([sc] * 5), 5)[3] == want).all(), (trial, fp29, "bucket-lane form")
     finally:
         c.close()
+
+
+def test_msm_srs_multi_on_both_sides_of_the_sort_switch(oracle, srs_oracle):
+    """The atomic counting sort (msm_digits_kernel, msm_scatter_kernel) behind `mina_msm_srs_multi`: the driver leaves the partitioned sort when its
+    table of partitions x sort blocks x problems outgrows 2^22 words.  The SRS table has c = 16: 32768 buckets per problem in partitions of 2^8 = 128
+    partitions, and 65536 scalars in blocks of 256 = 256 sort blocks.  128 x 256 x 129 = 4 227 072 > 2^22 = 4 194 304: 129 problems take the atomic sort (and,
+    with it, tasks instead of one lane per bucket); 128 problems are exactly 2^22 and stay on the partitioned sort.  65536 x 16 x 129 = 1.35 x 10^8 entries are
+    below the pipeline's 2^28.  The rows are four distinct ones tiled -- uniform, all zero, eight non-zero scalars, all r - 1 (one bucket per window holds the
+    whole row) --: every problem == mina_msm_srs of its row, and the last, a uniform one, == the oracle.  On a context of its own: the workspace of this shape
+    is several GiB and grow-only."""
+    import mina_bridge_amd as m
+    curve, n, r = 1, 65536, P
+    g, _ = srs_oracle[curve]
+    few = np.zeros((n, 32), np.uint8); few[:8] = rand_scalars(8, r, seed=8102)
+    rows = np.stack([rand_scalars(n, r, seed=8101), np.zeros((n, 32), np.uint8), few, np.repeat(oracle.ints_to_le([r - 1]), n, axis=0)])
+    pick = np.arange(129) % 4
+    sc = rows[pick]
+    c = m.MinaContext(0)
+    try:
+        c.srs_create(curve, n)
+        single = [c.msm_srs(curve, row) for row in rows]
+        assert not single[1].any()
+        for nprob in (129, 128):
+            got = c.msm_srs_multi(curve, sc[:nprob], nprob)
+            assert got.shape == (nprob, 64)
+            for j in range(nprob):
+                assert (got[j] == single[pick[j]]).all(), (nprob, j)
+            if nprob == 129:
+                assert (got[128] == oracle.msm_pippenger(curve, g[:n], rows[0], threads=8)).all()
+    finally:
+        c.close()

@@ -143,6 +143,33 @@ def test_scalar_distributions(ctx, dev, oracle, points, curve):
             assert (np.ascontiguousarray(got[:, 64:68]).view(np.uint32) == 1).all(), name
 
 
+def test_long_segments_on_the_atomic_counting_sort(oracle, srs_oracle):
+    """The atomic counting sort over segments (msm_digits_seg_kernel, msm_scatter_kernel): the driver leaves the partitioned sort when its table of
+    partitions x sort blocks x problems outgrows 2^22 words.  A longest segment of 2^17 - 1 points takes c = 13: 20 windows of 4096 buckets = 81920 buckets per
+    problem in partitions of 2^9 = 160 partitions, and 512 sort blocks of 256 scalars.  160 x 512 x 53 segments = 4 341 760 > 2^22 = 4 194 304 (51 segments
+    would still fit); 131071 x 20 x 53 = 1.39 x 10^8 entries are below the pipeline's 2^28.  The segments are overlapping ranges of ONE array of 2^17 points (the
+    65536 SRS points twice: the repeats meet in one bucket wherever their digits agree), three of them long, two empty, the rest short and ragged.  On a
+    context of its own: the workspace of this shape is several GiB and grow-only."""
+    import mina_bridge_amd as m
+    curve, n = 0, 131072
+    g, _ = srs_oracle[curve]
+    bases = np.concatenate([g, g])
+    sc = rand_scalars(n, SCALAR_MOD[curve], seed=53)
+    sc[::11] = 0
+    segs = [(0, n - 1), (1, n), (65536, n), (0, 0), (n, n), (40000, 40001), (70000, 70031), (70000, 70032), (65000, 66000)]
+    segs += [(2500 * i, 2500 * i + 1 + 37 * i) for i in range(44)]
+    assert len(segs) == 53 and max(hi - lo for lo, hi in segs) == (1 << 17) - 1
+    c = m.MinaContext(0)
+    d = Dev(c)
+    try:
+        got = check_msm(c, d, oracle, curve, bases, sc, segs, naive=False)
+        lo, hi = segs[8]
+        assert (record_to_affine(got[8]) == oracle.msm_pippenger(curve, bases[lo:hi], sc[lo:hi], threads=8)).all()
+    finally:
+        d.close()
+        c.close()
+
+
 # ------------------------------------------------------------------------------------------------ the fold
 def fold_segments(ctx, dev, field, k, chals, weights, segs):
     batch, nseg, n = len(chals) // k, len(segs), 1 << k
