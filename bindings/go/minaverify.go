@@ -98,6 +98,23 @@ func (c *Ctx) SearchStats() (searches, rounds, parts uint64, err error) {
 	return uint64(a), uint64(b), uint64(d), nil
 }
 
+// SetSegFoldMfmaMin: segments of minLen proofs or more (and fewer than 2^17) of a segmented b_poly fold run on the matrix cores; 0 = never, 256 = the default.
+func (c *Ctx) SetSegFoldMfmaMin(minLen uint32) error {
+	if rc := C.mina_ctx_set_seg_fold_mfma_min(c.p, C.uint32_t(minLen)); rc != 0 {
+		return lastError()
+	}
+	return nil
+}
+
+// SegFoldStats: segments the context folded on the matrix cores and with the VALU kernels (empty ones in neither), and its matrix-core passes.
+func (c *Ctx) SegFoldStats() (mfmaSegments, valuSegments, mfmaPasses uint64, err error) {
+	var a, b, d C.uint64_t
+	if rc := C.mina_ctx_seg_fold_stats(c.p, &a, &b, &d); rc != 0 {
+		return 0, 0, 0, lastError()
+	}
+	return uint64(a), uint64(b), uint64(d), nil
+}
+
 // StateJobEachDev: per-proof verdicts (one uint32 each in dVerdicts) of a Proof-of-State job whose inputs are in HBM; waits for its lane.
 func (c *Ctx) StateJobEachDev(jobs *C.mina_state_jobs, dVerdicts, dFlags unsafe.Pointer) error {
 	if rc := C.mina_state_job_each_dev(c.p, jobs, dVerdicts, dFlags); rc != 0 {

@@ -594,6 +594,17 @@ int mina_state_job_each_dev(mina_ctx *ctx, const mina_state_jobs *jobs, void *d_
  * mina_ctx_search_stats: legs searched in groups, rounds (levels) and parts (segments checked) since the context was created; functions of (batch, G, culprits). */
 int mina_ctx_set_search_groups(mina_ctx *ctx, uint32_t groups);
 int mina_ctx_search_stats(mina_ctx *ctx, uint64_t *searches, uint64_t *rounds, uint64_t *parts);
+/* Which kernels fold the segments of mina_b_poly_fold_segments_dev and of the grouped search's rounds.  The rule, applied on the host per segment: the int8 matrix
+ * cores (the single fold's GEMM with the K loop cut to the segment, neighbours masked out) where mina_verify_tuning.bpoly_mfma != 0, k >= 2 and
+ * min_len <= length < 2^17 -- an int32 accumulator holds length * 2^14 only below 2^17 proofs; the VALU segmented kernels for every other non-empty segment; an empty
+ * segment is all zero.  Results are the same bytes either way (exact integers modulo p).  min_len: 0 = never, else 1 .. 2^17 - 1; the default is 256, the single
+ * fold's rule and the only measured crossover (not measured for segments on an MI355X yet: tools/bench_search.py --fold-mfma-min).  Workspace: 512 B x 2^k of column
+ * sums per matrix-core segment, capped at a budget of 256 MiB per lane -- the segments go out in passes of max(1, 256 MiB / (512 B x 2^k)), queued back to back.
+ * mina_ctx_seg_fold_stats: running totals of the context that RAN the folds -- segments folded on the matrix cores, segments folded by the VALU kernels (empty
+ * segments count in neither) and matrix-core passes.  A boundary search (MINA_VERIFY_GROUPED_SEARCH) runs on a view context of its own with the default min_len;
+ * its counters are not carried over to the device's context. */
+int mina_ctx_set_seg_fold_mfma_min(mina_ctx *ctx, uint32_t min_len);
+int mina_ctx_seg_fold_stats(mina_ctx *ctx, uint64_t *mfma_segments, uint64_t *valu_segments, uint64_t *mfma_passes);
 /* Test-facing: *live = the streams the context's lanes hold now, *made_by_searches = the streams its culprit searches have created since the context was created
  * (the fan search creates the streams its lanes lack and destroys them when it is done; the grouped search creates none and queues on the job's lane only). */
 int mina_ctx_lane_streams(mina_ctx *ctx, uint32_t *live, uint64_t *made_by_searches);
@@ -638,7 +649,8 @@ int mina_point_records_equal_dev(mina_ctx *ctx, const void *d_a, const void *d_b
  *
  * mina_b_poly_fold_segments_dev: d_out[s][j] = sum over b in segment s of weights[b] * b_poly_coefficients(chals[b])[j], canonical, equal byte for byte to
  * mina_b_poly_fold_dev over that range alone (both are exact sums modulo p, whichever kernels that call takes; an empty segment gives zeros).  d_weights may be
- * null (every weight 1).  nseg <= 65535, nseg * 2^k <= 2^28; d_out 16-byte aligned. */
+ * null (every weight 1).  nseg <= 65535, nseg * 2^k <= 2^28; d_out 16-byte aligned.  Long segments are folded on the matrix cores, the others by the VALU
+ * kernels: mina_ctx_set_seg_fold_mfma_min. */
 int mina_msm_segments_dev(mina_ctx *ctx, int curve, size_t n_total, size_t nseg, const void *d_seg_begin, const void *d_seg_end /* nseg u32 each */,
                           const void *d_bases /* n_total*64 canonical affine */, const void *d_scalars /* n_total*32 */, void *d_out /* nseg records */);
 int mina_b_poly_fold_segments_dev(mina_ctx *ctx, int field, uint32_t k, size_t batch, size_t nseg, const void *d_seg_begin,

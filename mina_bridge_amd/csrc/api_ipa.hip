@@ -654,19 +654,23 @@ size_t mb_search_parts_cap(mina_ctx *c, int curve, uint32_t k) {
     return (size_t)std::max<uint64_t>(1, std::min<uint64_t>(128, by_entries));
 }
 
-// the tables of a pass into the lane's gs_tab: [begin | end] in proofs, then [begin | end] scaled by `per` (entries of the rows), np words each.  They go through
-// the lane's pinned staging buffer at `stage_off`: the passes of a round are queued back to back, each with its own 16 * np bytes of it, and the search waits for the
-// lane at the end of the round -- the buffer is free again when the next round fills it.
-static int parts_tables(mina_ctx *c, size_t np, const uint32_t *lo, const uint32_t *cnt, uint32_t base, uint32_t per, size_t stage_off) {
+// the tables of a pass into the lane's gs_tab: [begin | end] in proofs, [begin | end] scaled by `per` (entries of the rows), then the ids of the parts whose fold
+// runs on the matrix cores (mb_bpoly_seg_plan: the host knows every length), np words each.  They go through the lane's pinned staging buffer at `stage_off`: the
+// passes of a round are queued back to back, each with its own MB_PARTS_STAGE * np bytes of it, and the search waits for the lane at the end of the round -- the
+// buffer is free again when the next round fills it.
+static int parts_tables(mina_ctx *c, uint32_t k, size_t np, const uint32_t *lo, const uint32_t *cnt, uint32_t base, uint32_t per, size_t stage_off, BpolySegPlan &plan) {
     Lane &L = *c->L;
     int rc;
-    if ((rc = L.host_stage.ensure(stage_off + np * 16)) || (rc = L.gs_tab.ensure(np * 16))) return rc;      // (the caller sized the staging buffer for the whole round: no reallocation between its passes)
+    if ((rc = L.host_stage.ensure(stage_off + np * MB_PARTS_STAGE)) || (rc = L.gs_tab.ensure(np * MB_PARTS_STAGE))) return rc;      // (the caller sized the staging buffer for the whole round: no reallocation between its passes)
     uint32_t *t = (uint32_t *)((uint8_t *)L.host_stage.p + stage_off);
     for (size_t p = 0; p < np; ++p) {
         t[p] = lo[p] - base; t[np + p] = lo[p] - base + cnt[p];
         t[2 * np + p] = (lo[p] - base) * per; t[3 * np + p] = (lo[p] - base + cnt[p]) * per;
+        t[4 * np + p] = 0;
     }
-    HIPC(hipMemcpyAsync(L.gs_tab.p, t, np * 16, hipMemcpyHostToDevice, L.stream));
+    plan = mb_bpoly_seg_plan(c, k, np, cnt, t + 4 * np);
+    plan.d_ids = L.gs_tab.as<uint32_t>() + 4 * np;
+    HIPC(hipMemcpyAsync(L.gs_tab.p, t, np * MB_PARTS_STAGE, hipMemcpyHostToDevice, L.stream));
     return MINA_OK;
 }
 
@@ -685,11 +689,12 @@ int mb_ipa_recheck_rows_parts(mina_ctx *c, size_t np, const uint32_t *lo, const 
     Lane &L = *c->L;
     int rc;
     if ((rc = L.gs_folded.ensure(np * (size_t)n * 32)) || (rc = L.gs_xa.ensure(np * sizeof(xyzz_t))) || (rc = L.gs_xb.ensure(np * sizeof(xyzz_t)))) return rc;
-    if ((rc = parts_tables(c, np, lo, cnt, first, per, stage_off))) return rc;
+    BpolySegPlan plan;
+    if ((rc = parts_tables(c, k, np, lo, cnt, first, per, stage_off, plan))) return rc;
     const uint32_t *tab = L.gs_tab.as<uint32_t>();
     if (const uint32_t nsh = c->ipa_rows_nshared)              // these proofs get their own scalars of the batch-shared points back (idempotent)
         mb::ipa_shared_restore_kernel<<<cdiv((size_t)span * nsh * 8, 256), 256, 0, L.stream>>>(first, span, nsh, per, src->ipa_shared_off.as<uint32_t>(), src->ipa_shared.as<uint32_t>(), src->ipa_scalars.as<uint32_t>());
-    if ((rc = mb_bpoly_fold_segments(c, FS, k, span, np, longest, tab, tab + np, src->ipa_chals.as<uint32_t>() + (size_t)first * k * 8, src->ipa_sigma.as<uint32_t>() + (size_t)first * 8, L.gs_folded.as<uint32_t>()))) return rc;
+    if ((rc = mb_bpoly_fold_segments(c, FS, k, span, np, plan, tab, tab + np, src->ipa_chals.as<uint32_t>() + (size_t)first * k * 8, src->ipa_sigma.as<uint32_t>() + (size_t)first * 8, L.gs_folded.as<uint32_t>()))) return rc;
     if ((rc = mb_msm_table(c, curve, s.table.p, s.depth, s.c, s.W, 0, n, (uint32_t)np, L.gs_folded.as<uint32_t>(), nullptr, L.gs_xa.p))) return rc;
     if ((rc = mb_msm_segments(c, curve, span * per, np, longest * per, tab + 2 * np, tab + 3 * np, src->ipa_scalars.as<uint32_t>() + (size_t)first * per * 8,
                               src->ipa_points.as<affine_t>() + (size_t)first * per, nullptr, L.gs_xb.p))) return rc;
@@ -722,9 +727,10 @@ int mb_accumulator_check_parts(mina_ctx *c, int curve, uint32_t k, size_t batch,
     Lane &L = *c->L;
     int rc;
     if ((rc = L.gs_folded.ensure(np * (size_t)n * 32)) || (rc = L.gs_xa.ensure(np * sizeof(xyzz_t))) || (rc = L.gs_xb.ensure(np * sizeof(xyzz_t)))) return rc;
-    if ((rc = parts_tables(c, np, lo, cnt, 0, 1, stage_off))) return rc;
+    BpolySegPlan plan;
+    if ((rc = parts_tables(c, k, np, lo, cnt, 0, 1, stage_off, plan))) return rc;
     const uint32_t *tab = L.gs_tab.as<uint32_t>();
-    if ((rc = mb_bpoly_fold_segments(c, FS, k, batch, np, longest, tab, tab + np, L.gs_chals.as<uint32_t>(), d_rho, L.gs_folded.as<uint32_t>()))) return rc;
+    if ((rc = mb_bpoly_fold_segments(c, FS, k, batch, np, plan, tab, tab + np, L.gs_chals.as<uint32_t>(), d_rho, L.gs_folded.as<uint32_t>()))) return rc;
     if ((rc = mb_msm_table(c, curve, s.table.p, s.depth, s.c, s.W, 0, n, (uint32_t)np, L.gs_folded.as<uint32_t>(), nullptr, L.gs_xa.p))) return rc;
     if ((rc = mb_msm_segments(c, curve, (uint32_t)batch, np, longest, tab, tab + np, d_rho, L.gs_points.p, nullptr, L.gs_xb.p))) return rc;
     DISPATCH_FIELD(FB, { mb::xyzz_compare_parts_kernel<F_><<<(uint32_t)np, 64, 0, L.stream>>>(L.gs_xa.as<xyzz_t>(), L.gs_xb.as<xyzz_t>(), 0, tab, tab + np, L.gs_bad.as<uint32_t>(), (uint32_t)batch, d_flags); });

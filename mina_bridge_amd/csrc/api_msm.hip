@@ -270,7 +270,7 @@ int mb_msm_variable(mina_ctx *c, int curve, uint32_t n, const uint32_t *d_scalar
 
 // The segment tables of the two segmented entry points (device memory): read back on the current lane -- the one host wait of those calls, behind whatever
 // the lane already holds -- and checked: begin <= end <= limit for every segment.  max_len = the longest segment.
-int mb_read_segments(mina_ctx *c, size_t nseg, const void *d_begin, const void *d_end, size_t limit, uint32_t *max_len) {
+int mb_read_segments(mina_ctx *c, size_t nseg, const void *d_begin, const void *d_end, size_t limit, uint32_t *max_len, std::vector<uint32_t> *lens) {
     std::vector<uint32_t> h(2 * nseg);
     HIPC(hipMemcpyAsync(h.data(), d_begin, nseg * 4, hipMemcpyDeviceToHost, c->L->stream));
     HIPC(hipMemcpyAsync(h.data() + nseg, d_end, nseg * 4, hipMemcpyDeviceToHost, c->L->stream));
@@ -282,6 +282,7 @@ int mb_read_segments(mina_ctx *c, size_t nseg, const void *d_begin, const void *
         mx = std::max(mx, e - b);
     }
     *max_len = mx;
+    if (lens) { lens->resize(nseg); for (size_t s = 0; s < nseg; ++s) (*lens)[s] = h[nseg + s] - h[s]; }
     return MINA_OK;
 }
 

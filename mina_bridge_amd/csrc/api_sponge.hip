@@ -3,6 +3,7 @@
 #include "sponge.cuh"
 #include "bpoly_mfma.cuh"
 #include "bpoly_seg.cuh"
+#include "bpoly_mfma_seg.cuh"
 
 // ------------------------------------------------------------------------------------------------
 // // K2
@@ -77,34 +78,74 @@ extern "C" int mina_b_poly_fold_dev(mina_ctx *c, int field, uint32_t k, size_t b
     return mb_bpoly_fold(c, field, k, batch, (const uint32_t *)d_chals, (const uint32_t *)d_weights, (uint32_t *)d_out);
 }
 
-// nseg folds over ranges of one batch in one launch set: the half tables of the whole batch once (bpoly_tables_kernel, as the single fold's VALU path), then
-// the fold with the segment on grid.y and the conversion to canonical words.  Sums of canonical Montgomery products modulo p: the words equal those of
-// mina_b_poly_fold_dev over each range alone, whichever of its kernels (VALU, matrix cores, single-proof) that call takes.
+// nseg folds over ranges of one batch in one launch set.  The host has classified the segments by length (BpolySegPlan, ctx.h):
+//   * the VALU kernels (bpoly_seg.cuh): the half tables of the whole batch once (bpoly_tables_kernel, as the single fold's VALU path), the fold with the segment on
+//     grid.y and the conversion to canonical words -- over all of grid.y, each block leaving the matrix cores' segments alone by the plan's length rule; empty
+//     segments are theirs and come out zero;
+//   * the matrix cores (bpoly_mfma_seg.cuh): the digit planes of the whole batch once, pad columns cleared as run_bpoly_fold clears them, then the segmented GEMM and
+//     its reduce in passes of bpm_seg_per_pass(k) segments -- the lane's colsum stays within BPM_SEG_COLSUM_BUDGET (256 MiB; one segment's worth where 2^k x 512 B is
+//     more) -- queued back to back on the lane's stream: two launches per pass, however many segments.
+// Only the table builders and kernel sets that have work are launched.  Sums of canonical Montgomery products modulo p, exact integers on the matrix cores: the words
+// equal those of mina_b_poly_fold_dev over each range alone, whichever of its kernels (VALU, matrix cores, single-proof) that call takes.
 template <int F>
-static int run_bpoly_fold_segments(mina_ctx *c, uint32_t k, size_t batch, size_t nseg, uint32_t max_len, const MsmSegments &sg, const uint32_t *d_chals, const uint32_t *d_weights, uint32_t *d_out) {
+static int run_bpoly_fold_segments(mina_ctx *c, uint32_t k, size_t batch, size_t nseg, const BpolySegPlan &plan, const MsmSegments &sg, const uint32_t *d_chals, const uint32_t *d_weights, uint32_t *d_out) {
     BpolyShape sh = bp_shape(k, batch);
     const uint32_t nl = 1u << sh.lb, nh = 1u << sh.hb, n = 1u << k;
-    const uint32_t lo_blocks = cdiv(nl, 256), hi_tiles = cdiv(nh, BP_HT);
-    uint32_t slices = 1;                                         // few long segments: slices of each fill the chip, as in run_bpoly_fold
-    while (slices * 2 <= max_len && (size_t)lo_blocks * hi_tiles * nseg * slices < 2048 && slices < 64) slices *= 2;
     Lane &L = *c->L;
     int rc;
-    if ((rc = L.bp_ltab.ensure(batch * nl * sizeof(fe_t))) || (rc = L.bp_htab.ensure(batch * nh * sizeof(fe_t)))) return rc;
-    if (slices > 1 && (rc = L.bp_partial.ensure(nseg * slices * n * sizeof(fe_t)))) return rc;
-    fe_t *partial = slices > 1 ? L.bp_partial.as<fe_t>() : (fe_t *)d_out;      // one slice: the fold writes into the output, converted in place
-    { ProfScope ps_(c, PS_BPOLY_TABLES); bpoly_tables_kernel<F><<<cdiv(batch * (nl + nh), 256), 256, 0, L.stream>>>(sh, c->fk[F], d_chals, d_weights, L.bp_ltab.as<fe_t>(), L.bp_htab.as<fe_t>()); }
-    { ProfScope ps_(c, PS_BPOLY_FOLD); bpoly_fold_seg_kernel<F><<<dim3(lo_blocks * hi_tiles * slices, (uint32_t)nseg), 256, 0, L.stream>>>(sh, slices, sg, L.bp_ltab.as<fe_t>(), L.bp_htab.as<fe_t>(), partial); }
-    { ProfScope ps_(c, PS_BPOLY_FINISH); bpoly_finish_seg_kernel<F><<<dim3(cdiv(n, 256), (uint32_t)nseg), 256, 0, L.stream>>>(n, slices, partial, d_out); }
+    const BpolySegSkip skip{plan.n_mfma ? plan.mfma_min : 0u, plan.n_mfma ? BPM_SEG_END : 0u};
+    if (plan.n_mfma < nseg) {                                    // VALU and empty segments
+        const uint32_t lo_blocks = cdiv(nl, 256), hi_tiles = cdiv(nh, BP_HT);
+        const size_t mine = nseg - plan.n_mfma;
+        uint32_t slices = 1;                                     // few long segments: slices of each fill the chip, as in run_bpoly_fold
+        while (slices * 2 <= plan.max_valu_len && (size_t)lo_blocks * hi_tiles * mine * slices < 2048 && slices < 64) slices *= 2;
+        if (slices > 1 && (rc = L.bp_partial.ensure(nseg * slices * n * sizeof(fe_t)))) return rc;
+        fe_t *partial = slices > 1 ? L.bp_partial.as<fe_t>() : (fe_t *)d_out;      // one slice: the fold writes into the output, converted in place
+        if (plan.n_valu) {
+            if ((rc = L.bp_ltab.ensure(batch * nl * sizeof(fe_t))) || (rc = L.bp_htab.ensure(batch * nh * sizeof(fe_t)))) return rc;
+            ProfScope ps_(c, PS_BPOLY_TABLES); bpoly_tables_kernel<F><<<cdiv(batch * (nl + nh), 256), 256, 0, L.stream>>>(sh, c->fk[F], d_chals, d_weights, L.bp_ltab.as<fe_t>(), L.bp_htab.as<fe_t>());
+        }
+        { ProfScope ps_(c, PS_BPOLY_FOLD); bpoly_fold_seg_kernel<F><<<dim3(lo_blocks * hi_tiles * slices, (uint32_t)nseg), 256, 0, L.stream>>>(sh, slices, sg, skip, L.bp_ltab.as<fe_t>(), L.bp_htab.as<fe_t>(), partial); }
+        { ProfScope ps_(c, PS_BPOLY_FINISH); bpoly_finish_seg_kernel<F><<<dim3(cdiv(n, 256), (uint32_t)nseg), 256, 0, L.stream>>>(n, slices, sg, skip, partial, d_out); }
+    }
+    if (plan.n_mfma) {
+        const uint32_t kpad = (uint32_t)(cdiv(batch, BPM_KALIGN) * BPM_KALIGN);
+        const uint32_t per_pass = std::min(bpm_seg_per_pass(k), plan.n_mfma), n_max = std::min(plan.max_mfma_len, BPM_SEG_END - 1);
+        if ((rc = L.bp_ldig.ensure((size_t)nl * BPM_DIGITS * kpad)) || (rc = L.bp_hdig.ensure((size_t)nh * BPM_DIGITS * kpad)) ||
+            (rc = L.bp_colsum.ensure((size_t)per_pass * n * BPM_COLS * 8))) return rc;
+        if (kpad != batch) { HIPC(hipMemsetAsync(L.bp_ldig.p, 0, (size_t)nl * BPM_DIGITS * kpad, L.stream)); HIPC(hipMemsetAsync(L.bp_hdig.p, 0, (size_t)nh * BPM_DIGITS * kpad, L.stream)); }
+        { ProfScope ps_(c, PS_BPOLY_TABLES);
+          if (sh.lb >= 3 && sh.hb >= 3) bpoly_tables_digits8_kernel<F><<<cdiv(batch * ((nl + nh) / 8), 256), 256, 0, L.stream>>>(sh, kpad, c->fk[F], d_chals, d_weights, L.bp_ldig.as<int8_t>(), L.bp_hdig.as<int8_t>());
+          else bpoly_tables_digits_kernel<F><<<cdiv(batch * (nl + nh), 256), 256, 0, L.stream>>>(sh, kpad, c->fk[F], d_chals, d_weights, L.bp_ldig.as<int8_t>(), L.bp_hdig.as<int8_t>()); }
+        for (uint32_t base = 0; base < plan.n_mfma; base += per_pass) {
+            const uint32_t w = std::min(per_pass, plan.n_mfma - base);
+            { ProfScope ps_(c, PS_BPOLY_FOLD); bpoly_field_gemm_seg_kernel<<<dim3(cdiv(nh, 4) * cdiv(nl, 4), w), 256, 0, L.stream>>>(nh, nl, kpad, sg, (uint32_t)nseg, n_max, plan.d_ids + base, L.bp_hdig.as<int8_t>(), L.bp_ldig.as<int8_t>(), L.bp_colsum.as<unsigned long long>()); }
+            { ProfScope ps_(c, PS_BPOLY_FINISH); bpoly_colsum_reduce_seg_kernel<F><<<dim3(cdiv(n, 256), w), 256, 0, L.stream>>>(nh, nl, sh.lb, (uint32_t)nseg, c->fk[F], plan.d_ids + base, L.bp_colsum.as<unsigned long long>(), d_out); }
+            ++c->sf_mfma_passes;
+        }
+    }
+    c->sf_mfma_segments += plan.n_mfma; c->sf_valu_segments += plan.n_valu;
     HIPC(hipGetLastError());
     return MINA_OK;
 }
 
-int mb_bpoly_fold_segments(mina_ctx *c, int field, uint32_t k, size_t batch, size_t nseg, uint32_t max_len, const uint32_t *d_begin, const uint32_t *d_end,
+BpolySegPlan mb_bpoly_seg_plan(const mina_ctx *c, uint32_t k, size_t nseg, const uint32_t *len, uint32_t *ids_host) {
+    BpolySegPlan p;
+    p.mfma_min = (mb_tune().bpoly_mfma != 0 && k / 2 >= 1) ? c->seg_fold_mfma_min : 0u;
+    for (size_t s = 0; s < nseg; ++s) {
+        if (p.mfma_min && len[s] >= p.mfma_min && len[s] < BPM_SEG_END) { ids_host[p.n_mfma++] = (uint32_t)s; p.max_mfma_len = std::max(p.max_mfma_len, len[s]); }
+        else if (len[s]) { ++p.n_valu; p.max_valu_len = std::max(p.max_valu_len, len[s]); }
+    }
+    return p;
+}
+
+int mb_bpoly_fold_segments(mina_ctx *c, int field, uint32_t k, size_t batch, size_t nseg, const BpolySegPlan &plan, const uint32_t *d_begin, const uint32_t *d_end,
                            const uint32_t *d_chals, const uint32_t *d_weights, uint32_t *d_out) {
     if (bad_field(field) || k < 1 || k > 20 || batch == 0 || batch > (1u << 24) || nseg == 0 || nseg > 65535) return fail(MINA_ERR_ARG, "bad segmented fold shape");
+    if (plan.n_mfma > nseg || (plan.n_mfma && !plan.d_ids)) return fail(MINA_ERR_ARG, "bad segmented fold plan");
     const MsmSegments sg{d_begin, d_end, (uint32_t)batch};
     int rc = MINA_OK;
-    DISPATCH_FIELD(field, { rc = run_bpoly_fold_segments<F_>(c, k, batch, nseg, max_len, sg, d_chals, d_weights, d_out); });
+    DISPATCH_FIELD(field, { rc = run_bpoly_fold_segments<F_>(c, k, batch, nseg, plan, sg, d_chals, d_weights, d_out); });
     return rc;
 }
 
@@ -118,10 +159,33 @@ extern "C" int mina_b_poly_fold_segments_dev(mina_ctx *c, int field, uint32_t k,
     if (((uint64_t)nseg << k) > (1u << 28)) return fail(MINA_ERR_ARG, "nseg * 2^k beyond 2^28 output scalars");
     HIPC(hipSetDevice(c->device));
     c->next_lane();
+    Lane &L = *c->L;
     int rc;
     uint32_t max_len = 0;
-    if ((rc = mb_read_segments(c, nseg, d_seg_begin, d_seg_end, batch, &max_len))) return rc;
-    return mb_bpoly_fold_segments(c, field, k, batch, nseg, max_len, (const uint32_t *)d_seg_begin, (const uint32_t *)d_seg_end, (const uint32_t *)d_chals, (const uint32_t *)d_weights, (uint32_t *)d_out);
+    std::vector<uint32_t> lens;
+    if ((rc = mb_read_segments(c, nseg, d_seg_begin, d_seg_end, batch, &max_len, &lens))) return rc;
+    // the lane is idle behind that wait: its pinned id list is free to be written again
+    if ((rc = L.bp_seg_stage.ensure(nseg * 4))) return rc;
+    BpolySegPlan plan = mb_bpoly_seg_plan(c, k, nseg, lens.data(), (uint32_t *)L.bp_seg_stage.p);
+    if (plan.n_mfma) {
+        if ((rc = L.bp_seg_ids.ensure((size_t)plan.n_mfma * 4))) return rc;
+        HIPC(hipMemcpyAsync(L.bp_seg_ids.p, L.bp_seg_stage.p, (size_t)plan.n_mfma * 4, hipMemcpyHostToDevice, L.stream));
+        plan.d_ids = L.bp_seg_ids.as<uint32_t>();
+    }
+    return mb_bpoly_fold_segments(c, field, k, batch, nseg, plan, (const uint32_t *)d_seg_begin, (const uint32_t *)d_seg_end, (const uint32_t *)d_chals, (const uint32_t *)d_weights, (uint32_t *)d_out);
+}
+
+extern "C" int mina_ctx_set_seg_fold_mfma_min(mina_ctx *c, uint32_t min_len) {
+    if (!c) return fail(MINA_ERR_ARG, "null argument");
+    if (min_len >= BPM_SEG_END) return fail(MINA_ERR_ARG, "segmented fold on the matrix cores: 0 (never) or a shortest segment of 1 .. 2^17 - 1 proofs");
+    c->seg_fold_mfma_min = min_len;
+    return MINA_OK;
+}
+
+extern "C" int mina_ctx_seg_fold_stats(mina_ctx *c, uint64_t *mfma_segments, uint64_t *valu_segments, uint64_t *mfma_passes) {
+    if (!c || !mfma_segments || !valu_segments || !mfma_passes) return fail(MINA_ERR_ARG, "null argument");
+    *mfma_segments = c->sf_mfma_segments; *valu_segments = c->sf_valu_segments; *mfma_passes = c->sf_mfma_passes;
+    return MINA_OK;
 }
 
 extern "C" int mina_b_poly_fold(mina_ctx *c, int field, uint32_t k, size_t batch, const uint8_t *chals, const uint8_t *weights, uint8_t *out) {

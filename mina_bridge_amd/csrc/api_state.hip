@@ -638,14 +638,14 @@ static int state_job_each(mina_ctx *c, Lane &L, const mina_state_jobs &d, uint8_
             const size_t nparts = lo.size();
             if (nparts == 0) break;
             ++c->gs_rounds; c->gs_parts += nparts;
-            if ((r = L.gs_flags.ensure(nparts * 4)) || (r = L.host_stage.ensure(nparts * 16))) return r;
+            if ((r = L.gs_flags.ensure(nparts * 4)) || (r = L.host_stage.ensure(nparts * MB_PARTS_STAGE))) return r;
             uint32_t *fl = L.gs_flags.as<uint32_t>();
             for (size_t base = 0; base < nparts;) {
                 size_t w = std::min(cap, nparts - base);
                 auto longest = [&](size_t w_) { uint32_t x = 0; for (size_t q = 0; q < w_; ++q) x = std::max(x, cnt[base + q]); return x; };
                 while (w > 1 && !mb_msm_segments_fit(longest(w) * per, w)) w = (w + 1) / 2;
-                r = ipa_leg ? mb_ipa_recheck_rows_parts(c, w, &lo[base], &cnt[base], fl + base, base * 16)
-                            : mb_accumulator_check_parts(c, CURVE_VESTA, d.acc_k, B, (const uint32_t *)d.acc_rho, w, &lo[base], &cnt[base], fl + base, base * 16);
+                r = ipa_leg ? mb_ipa_recheck_rows_parts(c, w, &lo[base], &cnt[base], fl + base, base * MB_PARTS_STAGE)
+                            : mb_accumulator_check_parts(c, CURVE_VESTA, d.acc_k, B, (const uint32_t *)d.acc_rho, w, &lo[base], &cnt[base], fl + base, base * MB_PARTS_STAGE);
                 if (r) return r;
                 base += w;
             }

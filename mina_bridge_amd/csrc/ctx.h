@@ -125,6 +125,7 @@ struct Lane {
     DevBuf tmp_a, tmp_b, tmp_c, tmp_d;       // staging for the host-buffer entry points
     PinnedBuf host_stage;                    // pinned host side of the big H2D blobs (synchronous entry points only)
     DevBuf bp_ltab, bp_htab, bp_partial, bp_ldig, bp_hdig, bp_colsum;
+    DevBuf bp_seg_ids; PinnedBuf bp_seg_stage;   // mina_b_poly_fold_segments_dev: the ids of its matrix-core segments and their pinned host side (written only behind that call's wait for the lane)
     DevBuf ipa_chals, ipa_folded, ipa_xyzz_a, ipa_xyzz_b, ipa_points, ipa_scalars, ipa_sigma, ipa_in_a, ipa_in_b, ipa_in_c, ipa_verdict, ipa_xfer, ipa_shared, ipa_shared_off, acc_rho_scaled /* exchange variant: the caller's acc_rho times the shard's own CSPRNG scalar */;
     DevBuf st_ok, st_hashes, st_pub_xyzz, st_pubcomm, st_flags, st_in, st_verdicts;   // Proof-of-State job (api_state.hip)
     DevBuf dd_rep, dd_uniq, dd_table, dd_counts;  // its deduplicated state leg (state_dedup.cuh): 4 B x n each, the table 16 B x the power of two >= 2 n, counters + one word per 1024 states
@@ -229,7 +230,11 @@ struct mina_ctx : Installed {
     // The grouped culprit search of a failed job (mina_ctx_set_search_groups; api_state.hip): 0 = the fan search.  The counters of mina_ctx_search_stats follow from
     // (batch, groups, culprits) alone: searches = legs searched in groups, rounds = levels, parts = segments checked.
     uint32_t search_groups = 0; uint64_t gs_searches = 0, gs_rounds = 0, gs_parts = 0;
-    uint64_t search_streams_made = 0;   // streams any culprit search of this context has created (the fan search, for the lanes it lacks): mina_ctx_lane_streams
+    // The segmented b_poly fold (api_sponge.hip run_bpoly_fold_segments): segments of seg_fold_mfma_min proofs or more, and fewer than 2^17, are folded on the matrix
+    // cores (mina_ctx_set_seg_fold_mfma_min; 0 = never; 256 = the single fold's rule).  mina_ctx_seg_fold_stats: segments folded by either kind of kernel and
+    // matrix-core passes, counted as they are queued by the context that ran the fold.
+    uint32_t seg_fold_mfma_min = 256; uint64_t sf_mfma_segments = 0, sf_valu_segments = 0, sf_mfma_passes = 0;
+    uint64_t search_streams_made = 0;  // streams any culprit search of this context has created (the fan search, for the lanes it lacks): mina_ctx_lane_streams
     // mina_state_job_batch without its upload: per-proof verdicts (host bytes) of a job whose inputs are in HBM, on lane 0, waited for (api_state.hip
     // mb_state_job_each_host).  Filled by mina_ctx_create; the boundary hands a failed chunk's device staging to it under MINA_VERIFY_GROUPED_SEARCH, and a context
     // without it -- the stand-in contexts of the ThreadSanitizer tier -- keeps the host-buffer path.
@@ -466,7 +471,8 @@ int mb_ipa_recheck_rows(mina_ctx *c, size_t lo, size_t cnt, uint32_t *d_verdict 
 // MSM with one problem per part, the segmented variable-base MSM, one comparison launch; d_flags[p] = 1 iff part p's folded check holds.  Nothing waits for the GPU.
 // rows: from the rows of the opening check prepared last (as mb_ipa_recheck_rows).  accumulator: mb_accumulator_parts_prepare once per search (challenges,
 // checked points, one malformed word per proof -- a part holding a malformed commitment fails), then any number of passes.
-int mb_ipa_recheck_rows_parts(mina_ctx *c, size_t np, const uint32_t *lo, const uint32_t *cnt, uint32_t *d_flags, size_t stage_off /* this pass's 16 * np bytes of the lane's pinned staging buffer */);
+int mb_ipa_recheck_rows_parts(mina_ctx *c, size_t np, const uint32_t *lo, const uint32_t *cnt, uint32_t *d_flags, size_t stage_off /* this pass's MB_PARTS_STAGE * np bytes of the lane's pinned staging buffer */);
+static constexpr size_t MB_PARTS_STAGE = 20;   // bytes per part of a pass's tables: [begin | end] in proofs, [begin | end] in row entries, the fold's matrix-core segment ids
 int mb_accumulator_parts_prepare(mina_ctx *c, int curve, uint32_t k, size_t batch, const uint32_t *d_prechal, const uint32_t *d_sg_words);
 int mb_accumulator_check_parts(mina_ctx *c, int curve, uint32_t k, size_t batch, const uint32_t *d_rho, size_t np, const uint32_t *lo, const uint32_t *cnt, uint32_t *d_flags, size_t stage_off);
 size_t mb_search_parts_cap(mina_ctx *c, int curve, uint32_t k);      // parts per pass: min(128, 2^28 / (2^k * W)) for the SRS table's W windows
@@ -485,11 +491,22 @@ int mb_bpoly_fold(mina_ctx *c, int field, uint32_t k, size_t batch, const uint32
 int mb_msm_variable(mina_ctx *c, int curve, uint32_t n, const uint32_t *d_scalars, const void *d_points_mont,
                     uint32_t *d_out_words, void *d_out_xyzz);
 // the segment tables of mina_msm_segments_dev / mina_b_poly_fold_segments_dev, read back on the current lane (one host wait) and checked against `limit` (api_msm.hip)
-int mb_read_segments(mina_ctx *c, size_t nseg, const void *d_begin, const void *d_end, size_t limit, uint32_t *max_len);
+int mb_read_segments(mina_ctx *c, size_t nseg, const void *d_begin, const void *d_end, size_t limit, uint32_t *max_len, std::vector<uint32_t> *lens = nullptr /* the length of every segment */);
 // the segmented forms on the current lane, tables already checked (max_len = the longest segment); the MSM takes Montgomery affine points and writes 17-word
 // records and / or XYZZ values, one per segment.  mb_msm_segments_fit: the pipeline's limits hold for nseg segments of up to max_len entries
 bool mb_msm_segments_fit(uint32_t max_len, size_t nseg);
 int mb_msm_segments(mina_ctx *c, int curve, uint32_t n_total, size_t nseg, uint32_t max_len, const uint32_t *d_begin, const uint32_t *d_end,
                     const uint32_t *d_scalars, const void *d_points_mont, uint32_t *d_out_words, void *d_out_xyzz);
-int mb_bpoly_fold_segments(mina_ctx *c, int field, uint32_t k, size_t batch, size_t nseg, uint32_t max_len, const uint32_t *d_begin, const uint32_t *d_end,
+// Which kernels fold which segments of a segmented b_poly fold, decided on the HOST from the segments' lengths (both callers know them: mb_read_segments, the
+// search's cnt[]).  mb_bpoly_seg_plan applies the rule -- matrix cores (bpoly_mfma_seg.cuh) where mina_verify_tuning.bpoly_mfma != 0, k >= 2 and
+// mina_ctx::seg_fold_mfma_min <= length < 2^17; the VALU kernels (bpoly_seg.cuh) for every other segment, empty ones included -- and writes the ids of the
+// matrix-core segments, ascending, to ids_host[0 .. n_mfma).  The caller uploads that list with its tables (no host wait) and sets d_ids before the fold.
+struct BpolySegPlan {
+    uint32_t mfma_min = 0;             // the rule the device kernels share: segments with mfma_min <= length < 2^17 are the matrix cores'; 0 = none
+    uint32_t n_mfma = 0, n_valu = 0;   // matrix-core segments; non-empty VALU segments (empty ones count in neither)
+    uint32_t max_mfma_len = 0, max_valu_len = 0;
+    const uint32_t *d_ids = nullptr;   // device: n_mfma segment ids
+};
+BpolySegPlan mb_bpoly_seg_plan(const mina_ctx *c, uint32_t k, size_t nseg, const uint32_t *len, uint32_t *ids_host);
+int mb_bpoly_fold_segments(mina_ctx *c, int field, uint32_t k, size_t batch, size_t nseg, const BpolySegPlan &plan, const uint32_t *d_begin, const uint32_t *d_end,
                            const uint32_t *d_chals, const uint32_t *d_weights, uint32_t *d_out);

@@ -39,7 +39,7 @@ EXPORTS = [
     "mina_protocol_state_pack_dev", "mina_state_frontend_dev", "mina_account_frontend_dev", "mina_account_job_dev",
     "mina_state_jobs_prepare", "mina_state_job_batch_dev", "mina_state_job_batch", "mina_state_job_fold_dev",
     "mina_challenge_to_field_dev", "mina_field_sum_rows_dev", "mina_msm_srs_range_dev", "mina_msm_dev", "mina_points_sum_dev", "mina_point_records_equal_dev",
-    "mina_msm_segments_dev", "mina_b_poly_fold_segments_dev", "mina_state_job_each_dev", "mina_ctx_set_search_groups", "mina_ctx_search_stats", "mina_ctx_lane_streams", "mina_ctx_set_stream_budget",
+    "mina_msm_segments_dev", "mina_b_poly_fold_segments_dev", "mina_state_job_each_dev", "mina_ctx_set_search_groups", "mina_ctx_search_stats", "mina_ctx_set_seg_fold_mfma_min", "mina_ctx_seg_fold_stats", "mina_ctx_lane_streams", "mina_ctx_set_stream_budget",
     "mina_step_index_install", "mina_step_index_load_json", "mina_polish_tokens_from_json", "mina_verifier_index_load_json", "mina_pickles_public_input",
     "mina_verifier_index_install", "mina_verifier_index_digest", "mina_kimchi_to_batch", "mina_pickles_public_inputs_batch", "mina_wrap_proof_flatten", "mina_state_proof_split",
     "mina_verify_state", "mina_verify_state_batch", "mina_verify_state_checks", "mina_verify_state_files", "mina_verify_account", "mina_verify_account_batch",
@@ -1158,6 +1158,16 @@ class MinaContext:
         a, b, c = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
         self._ck(self._lib.mina_ctx_search_stats(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)), "mina_ctx_search_stats")
         return {"searches": a.value, "rounds": b.value, "parts": c.value}
+
+    def set_seg_fold_mfma_min(self, min_len: int):
+        """segments of `min_len` proofs or more (and fewer than 2^17) of a segmented b_poly fold run on the matrix cores; 0 = never; 256 = the default"""
+        self._ck(self._lib.mina_ctx_set_seg_fold_mfma_min(self._h, ctypes.c_uint32(min_len)), "mina_ctx_set_seg_fold_mfma_min")
+
+    def seg_fold_stats(self) -> dict:
+        """segments this context folded on the matrix cores / with the VALU kernels (empty ones in neither) and its matrix-core passes, since it was created"""
+        a, b, c = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self._ck(self._lib.mina_ctx_seg_fold_stats(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)), "mina_ctx_seg_fold_stats")
+        return {"mfma_segments": a.value, "valu_segments": b.value, "mfma_passes": c.value}
 
     def lane_streams(self) -> dict:
         """test-facing: streams the context's lanes hold now, and streams its culprit searches have created so far"""
