@@ -115,6 +115,27 @@ func (c *Ctx) SegFoldStats() (mfmaSegments, valuSegments, mfmaPasses uint64, err
 	return uint64(a), uint64(b), uint64(d), nil
 }
 
+// SetMsmFusedTail: task-form MSMs queued after the call run bucket sums, reduction and finish as one launch (on) or as the staged kernels (off, the default).
+func (c *Ctx) SetMsmFusedTail(on bool) error {
+	v := 0
+	if on {
+		v = 1
+	}
+	if rc := C.mina_ctx_set_msm_fused_tail(c.p, C.int(v)); rc != 0 {
+		return lastError()
+	}
+	return nil
+}
+
+// MsmTailStats: MSMs the context has queued with the fused tail and with the staged one.
+func (c *Ctx) MsmTailStats() (fusedRuns, stagedRuns uint64, err error) {
+	var a, b C.uint64_t
+	if rc := C.mina_ctx_msm_tail_stats(c.p, &a, &b); rc != 0 {
+		return 0, 0, lastError()
+	}
+	return uint64(a), uint64(b), nil
+}
+
 // StateJobEachDev: per-proof verdicts (one uint32 each in dVerdicts) of a Proof-of-State job whose inputs are in HBM; waits for its lane.
 func (c *Ctx) StateJobEachDev(jobs *C.mina_state_jobs, dVerdicts, dFlags unsafe.Pointer) error {
 	if rc := C.mina_state_job_each_dev(c.p, jobs, dVerdicts, dFlags); rc != 0 {

@@ -605,6 +605,17 @@ int mina_ctx_search_stats(mina_ctx *ctx, uint64_t *searches, uint64_t *rounds, u
  * its counters are not carried over to the device's context. */
 int mina_ctx_set_seg_fold_mfma_min(mina_ctx *ctx, uint32_t min_len);
 int mina_ctx_seg_fold_stats(mina_ctx *ctx, uint64_t *mfma_segments, uint64_t *valu_segments, uint64_t *mfma_passes);
+/* The tail of an MSM -- bucket sums, bucket reduction, finish -- as ONE launch instead of five or six (opt-in).  With the mode on, every MSM that accumulates in
+ * tasks (a single MSM, a segmented one, the lanes of a pipelined context; NOT the multi-problem calls that give every bucket a lane, which keep the staged tail) runs
+ * one kernel behind its accumulate: a workgroup per row of 128 buckets sums the row's buckets in LDS and publishes the row's plain and weighted sums; the workgroup
+ * that arrives last at a bucket set's counter totals the set, and the one that completes a problem's last set writes the result.  No workgroup waits for another.
+ * Results are the same points: the 68-byte records and 64-byte points are the same bytes as with the mode off, XYZZ outputs the same point in another
+ * representation.  on: 0 or 1; the default is 0.  Takes effect for the calls queued after it; a view context takes its parent's setting when it is created or
+ * refreshed.  The boundary (mina_verify_*) does not use the mode.  Measured on one MI355X (tools/bench_msm_tail.py, profiles/msm_fused_tail.json): 9 kernels per lone 2^16 MSM
+ * instead of 14, but a lone call is SLOWER (568 -> 646 us; a lone accumulator check 399 -> 479 us) and 16 pipelined lanes are level: for callers who pay per launch.
+ * mina_ctx_msm_tail_stats: MSMs this context has queued with the fused tail and with the staged one since it was created. */
+int mina_ctx_set_msm_fused_tail(mina_ctx *ctx, int on);      /* default 0; takes effect for the calls queued after it */
+int mina_ctx_msm_tail_stats(mina_ctx *ctx, uint64_t *fused_runs, uint64_t *staged_runs);
 /* Test-facing: *live = the streams the context's lanes hold now, *made_by_searches = the streams its culprit searches have created since the context was created
  * (the fan search creates the streams its lanes lack and destroys them when it is done; the grouped search creates none and queues on the job's lane only). */
 int mina_ctx_lane_streams(mina_ctx *ctx, uint32_t *live, uint64_t *made_by_searches);

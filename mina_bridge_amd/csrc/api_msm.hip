@@ -30,11 +30,12 @@ struct MsmPlan {
     bool pipelined;       // several lanes in flight: the throughput forms of the bucket sums and of the reduction
     bool coop;            // one MSM at a time: the reduction's latency form (four lanes per add)
     bool fused_finish;    // one bucket set per problem and no affine output wanted: the reduction kernel's result IS the answer (no finish launch)
+    bool fused_tail;      // mina_ctx_set_msm_fused_tail on a task-form plan: stages 3 - 5 are ONE launch (msm.cuh msm_tail_kernel), whatever the sort, the law, `pipelined` or segments
     uint32_t nb_total; size_t entries, max_tasks; uint64_t gh_words;
     uint32_t R, C, log2C, seg_blocks, Gr, Gc; SegSum rows, cols;      // 2-D bucket reduction: C = 128 columns, R = NB / C rows (NB is a power of two in [128, 32768])
 };
 
-static int msm_plan(const MsmShape &sh, int nlanes, uint32_t fp29, bool twin, bool split_table /* the 29-bit tables the caller passed */, bool want_words, bool want_xyzz /* the outputs it wants */, MsmPlan &p) {
+static int msm_plan(const MsmShape &sh, int nlanes, uint32_t fp29, bool twin, bool split_table /* the 29-bit tables the caller passed */, bool want_words, bool want_xyzz /* the outputs it wants */, bool fused_tail_mode /* mina_ctx::msm_fused_tail */, MsmPlan &p) {
     if (sh.nprob == 0 || sh.nsets % sh.nprob) return fail(MINA_ERR_ARG, "bad problem count");
     if ((uint64_t)sh.NB * sh.nsets > (1u << 26) || (uint64_t)sh.n * sh.W * sh.nprob > (1u << 28)) return fail(MINA_ERR_ARG, "MSM batch too large for one pipeline");
     if (sh.NB < 128 || sh.NB > 32768) return fail(MINA_ERR_ARG, "unsupported bucket count");
@@ -58,6 +59,7 @@ static int msm_plan(const MsmShape &sh, int nlanes, uint32_t fp29, bool twin, bo
     p.pipelined = nlanes > 1;
     p.coop = !p.pipelined && !p.red29;                         // one MSM at a time: latency form; pipelined lanes: throughput form (the 29-bit reduction has the throughput form only)
     p.fused_finish = sh.nsets == sh.nprob && !want_words && want_xyzz;
+    p.fused_tail = fused_tail_mode && !p.bucket_lanes;         // (the bucket-lane form, and with it the 29-bit reduction, keeps the staged tail)
     p.C = 128; p.log2C = 7; p.R = sh.NB / p.C;
     SegSum &rows = p.rows, &cols = p.cols;
     const uint32_t chunk = p.coop ? SEG_CHUNK : 16, lpg = p.coop ? 4 : 1;
@@ -70,17 +72,22 @@ static int msm_plan(const MsmShape &sh, int nlanes, uint32_t fp29, bool twin, bo
     return MINA_OK;
 }
 
+// the fused tail's ticket words, one per bucket set and one per problem: a block of whole 16-byte units at the start of its allocation, zeroed before every launch
+static size_t tail_ticket_bytes(const MsmPlan &p) { return (((size_t)p.sh.nsets + p.sh.nprob) * 4 + 15) & ~(size_t)15; }
+
 // every buffer of the lane's workspace the plan's launches touch, at the size they need (0: not on this plan's path)
 static int msm_reserve(MsmWorkspace &w, const MsmPlan &p) {
     const size_t e = p.entries, nb = p.nb_total, t = p.max_tasks, sets = p.sh.nsets, xz = sizeof(xyzz_t);
     const bool atomic = !p.part_sort, tasks = !p.bucket_lanes;            // tasks: task numbering and the 128-B task partials
+    const size_t staged = p.fused_tail ? 0 : 1, fused = p.fused_tail ? 1 : 0;   // the staged tail's buckets and reduction arrays | the fused tail's row pairs and tickets
     const struct { DevBuf &buf; size_t bytes; } need[] = {
         {w.ghist, p.part_sort ? (p.gh_words + 8) * 4 : 0}, {w.stage, p.part_sort ? e * 8 : 0}, {w.ekey, e * 4}, {w.eval, atomic ? e * 4 : 0}, {w.eoff, atomic ? e * 4 : 0},
         {w.sorted, e * 4}, {w.count, nb * 4}, {w.start, (nb + 1) * 4},
         {w.order, p.bucket_lanes ? nb * 4 : 0}, {w.buckets29, p.red29 ? nb * sizeof(xyzz29_t) : 0}, {w.seg_bad, p.red29 ? ((size_t)(p.sh.NB / 128) + 128) * sets * 4 : 0},
         {w.task_start, tasks ? (nb + 1) * 4 : 0}, {w.rem_pos, tasks ? nb * 4 : 0}, {w.rem_bucket, tasks ? nb * 4 : 0}, {w.partial, tasks ? t * xz : 0},
-        {w.info, 16}, {w.redo, p.law != LAW_8X32 ? (std::max(t, nb) + 1) * 4 : 0}, {w.heavy, (t / MSM_HEAVY_TASKS + e / MSM_HEAVY_ENTRIES + 2) * 4}, {w.buckets, nb * xz},
-        {w.red_r, (size_t)p.R * sets * xz}, {w.red_ws, (size_t)p.C * sets * xz}, {w.red2_r, 24 * sets * xz}, {w.red2_w, 24 * sets * xz}, {w.set_total, sets * xz}};
+        {w.info, 16}, {w.redo, p.law != LAW_8X32 ? (std::max(t, nb) + 1) * 4 : 0}, {w.heavy, (t / MSM_HEAVY_TASKS + e / MSM_HEAVY_ENTRIES + 2) * 4}, {w.buckets, staged * nb * xz},
+        {w.red_r, staged * p.R * sets * xz}, {w.red_ws, staged * p.C * sets * xz}, {w.red2_r, staged * 24 * sets * xz}, {w.red2_w, staged * 24 * sets * xz}, {w.set_total, sets * xz},
+        {w.tail_rows, fused * 2 * p.R * sets * xz}, {w.tail_tickets, fused * tail_ticket_bytes(p)}};
     for (const auto &n : need) if (int rc = n.buf.ensure(n.bytes)) return rc;
     return MINA_OK;
 }
@@ -193,6 +200,16 @@ struct MsmRun {
         ProfScope ps_(c, PS_FINISH);
         msm_finish_kernel<F><<<p.sh.nprob, 64, 0, st>>>(p.sh.nsets / p.sh.nprob, p.sh.c, w.set_total.as<xyzz_t>(), fk.one, fk.pm2, d_out_xyzz, d_out_words);
     }
+
+    // stages 3 - 5 of a p.fused_tail plan in one launch: a workgroup per row of 128 buckets; the last arriver of a set totals it, the last of a problem finishes it.
+    // The tickets are zeroed in stream order ahead of every launch: a run that failed leaves nothing behind for the next.
+    int tail(uint32_t *d_out_words, xyzz_t *d_out_xyzz) {
+        ProfScope ps_(c, PS_BUCKET_SUM);
+        HIPC(hipMemsetAsync(w.tail_tickets.p, 0, tail_ticket_bytes(p), st));
+        msm_tail_kernel<F><<<p.R * p.sh.nsets, 256, 0, st>>>(p.R, p.sh.nsets, p.sh.nsets / p.sh.nprob, p.sh.c, w.task_start.as<uint32_t>(), w.rem_pos.as<uint32_t>(), w.info.as<uint32_t>(), w.partial.as<xyzz_t>(),
+                                                             w.tail_rows.as<xyzz_t>(), w.tail_tickets.as<uint32_t>(), w.set_total.as<xyzz_t>(), fk.one, fk.pm2, d_out_xyzz, d_out_words);
+        return MINA_OK;
+    }
 };
 
 template <int F>
@@ -202,15 +219,19 @@ static int run_msm(mina_ctx *c, const MsmShape &sh, const uint32_t *d_scalars, c
                    const void *d_points29s = nullptr /* ... or its pre-split form (SrsState::table29s, tab29_t records; mina_verify_tuning.msm_fp29 = 2) */,
                    const MsmSegments *seg = nullptr /* the problems are ranges of ONE scalar / point array (msm_seg.cuh): sh.n = the longest range, `d_scalars` and the references index the whole array */) {
     MsmPlan p;
-    if (int rc = msm_plan(sh, c->nlanes, mb_tune().msm_fp29, d_points29 != nullptr, d_points29 && d_points29s, d_out_words != nullptr, d_out_xyzz != nullptr, p)) return rc;
+    if (int rc = msm_plan(sh, c->nlanes, mb_tune().msm_fp29, d_points29 != nullptr, d_points29 && d_points29s, d_out_words != nullptr, d_out_xyzz != nullptr, c->msm_fused_tail, p)) return rc;
     if (int rc = msm_reserve(c->L->ws, p)) return rc;
     MsmRun<F> run{c, p, c->L->ws, c->L->stream, c->fk[F]};
     if (int rc = run.sort(d_scalars, seg)) return rc;
     run.accumulate(d_points, p.law == LAW_SPLIT ? d_points29s : p.law == LAW_TWIN ? d_points29 : nullptr);
-    run.bucket_sums(d_points);
-    if (int rc = run.reduce(p.fused_finish ? d_out_xyzz : nullptr)) return rc;
-    if (!p.fused_finish) run.finish(d_out_words, d_out_xyzz);
+    if (p.fused_tail) { if (int rc = run.tail(d_out_words, d_out_xyzz)) return rc; }
+    else {
+        run.bucket_sums(d_points);
+        if (int rc = run.reduce(p.fused_finish ? d_out_xyzz : nullptr)) return rc;
+        if (!p.fused_finish) run.finish(d_out_words, d_out_xyzz);
+    }
     HIPC(hipGetLastError());
+    ++(p.fused_tail ? c->mt_fused_runs : c->mt_staged_runs);
     return MINA_OK;
 }
 
@@ -310,6 +331,19 @@ int mb_msm_segments(mina_ctx *c, int curve, uint32_t n_total, size_t nseg, uint3
     const MsmSegments sg{d_begin, d_end, n_total};
     DISPATCH_FIELD(base_field_of(curve), { rc = run_msm<F_>(c, sh, d_scalars, (const affine_t *)d_points_mont, d_out_words, (xyzz_t *)d_out_xyzz, twin, nullptr, &sg); });
     return rc;
+}
+
+extern "C" int mina_ctx_set_msm_fused_tail(mina_ctx *c, int on) {
+    if (!c) return fail(MINA_ERR_ARG, "null argument");
+    if (on != 0 && on != 1) return fail(MINA_ERR_ARG, "fused MSM tail: 0 (off) or 1 (on)");
+    c->msm_fused_tail = on != 0;
+    return MINA_OK;
+}
+
+extern "C" int mina_ctx_msm_tail_stats(mina_ctx *c, uint64_t *fused_runs, uint64_t *staged_runs) {
+    if (!c || !fused_runs || !staged_runs) return fail(MINA_ERR_ARG, "null argument");
+    *fused_runs = c->mt_fused_runs; *staged_runs = c->mt_staged_runs;
+    return MINA_OK;
 }
 
 extern "C" int mina_msm_segments_dev(mina_ctx *c, int curve, size_t n_total, size_t nseg, const void *d_seg_begin, const void *d_seg_end,

@@ -101,6 +101,7 @@ struct SrsState {
 
 struct MsmWorkspace {
     DevBuf scalars, points, points29 /* the 2^261-domain twin of a variable-base MSM's points (api_msm.hip mb_msm_variable) */, ekey, eval, eoff, count, start, task_start, rem_pos, rem_bucket, info, sorted, partial, heavy, order, redo, ghist, stage, buckets, red_r, red_ws, red2_r, red2_w, set_total, out_words, out_xyzz, buckets29, seg_bad;
+    DevBuf tail_rows, tail_tickets;    // the fused tail (msm.cuh msm_tail_kernel): a pair of XYZZ records per row of 128 buckets, a ticket word per bucket set and per problem
 };
 
 // HIP-event stage timing on the context stream (off by default; bench.py turns it on for the timed region)
@@ -234,6 +235,9 @@ struct mina_ctx : Installed {
     // cores (mina_ctx_set_seg_fold_mfma_min; 0 = never; 256 = the single fold's rule).  mina_ctx_seg_fold_stats: segments folded by either kind of kernel and
     // matrix-core passes, counted as they are queued by the context that ran the fold.
     uint32_t seg_fold_mfma_min = 256; uint64_t sf_mfma_segments = 0, sf_valu_segments = 0, sf_mfma_passes = 0;
+    // The fused MSM tail (mina_ctx_set_msm_fused_tail; api_msm.hip MsmPlan::fused_tail): task-form MSMs run bucket sums, reduction and finish as ONE launch.
+    // mina_ctx_msm_tail_stats: MSMs queued with either tail, counted by the context that queued them.
+    bool msm_fused_tail = false; uint64_t mt_fused_runs = 0, mt_staged_runs = 0;
     uint64_t search_streams_made = 0;  // streams any culprit search of this context has created (the fan search, for the lanes it lacks): mina_ctx_lane_streams
     // mina_state_job_batch without its upload: per-proof verdicts (host bytes) of a job whose inputs are in HBM, on lane 0, waited for (api_state.hip
     // mb_state_job_each_host).  Filled by mina_ctx_create; the boundary hands a failed chunk's device staging to it under MINA_VERIFY_GROUPED_SEARCH, and a context
@@ -247,7 +251,7 @@ struct mina_ctx : Installed {
     void use_lane0() { L = &lanes[0]; }
     void next_lane() { L = pinned >= 0 ? &lanes[pinned] : &lanes[rr++ % (unsigned)nlanes]; }
 };
-static inline void mb_ctx_refresh_view(mina_ctx *view, mina_ctx *parent) { view->borrow_from(*parent); }
+static inline void mb_ctx_refresh_view(mina_ctx *view, mina_ctx *parent) { view->borrow_from(*parent); view->msm_fused_tail = parent->msm_fused_tail; }
 
 // waits for everything the `_dev` entry points have queued: the pipeline lanes and, for jobs that ran under plan B, the role streams
 static inline hipError_t mb_ctx_wait_all(mina_ctx *c) {

@@ -1110,6 +1110,183 @@ __global__ void msm_finish_kernel(uint32_t nsets /* per problem */, uint32_t c, 
     out_words[16] = 0;
 }
 
+// ---------------------------------------------------------------- K1z: K1e, K1e', K1f, K1g, K1g' and K1h in ONE launch (opt-in: mina_ctx_set_msm_fused_tail)
+// The task form's tail as one kernel: one 256-lane workgroup per ROW of C = 128 buckets of one bucket set, R = NB / 128 rows per set, grid = R * nsets.
+//   (a) the row's 128 bucket values = the sums of their task partials, as K1e forms them (quad q: buckets q and q + 64), kept in LDS and never written to HBM; a
+//       bucket of more than MSM_HEAVY_TASKS full tasks is summed by all 64 quads afterwards (what K1e' does with a block): no queue, no second launch;
+//   (b) the row's plain sum S_r = sum_c B[r][c] and weighted sum T_r = sum_c (c + 1) B[r][c] leave as one pair of records in `rows`; with b = r C + c,
+//           sum_b (b + 1) B_b = sum_r T_r + C * sum_r r * S_r                      (no column sums; tests/msm_tail_model.py restates this kernel on integers)
+//   (c) the workgroup publishes its pair and draws a ticket from its set's counter.  The one that draws the LAST ticket of the set reads the R pairs, forms the set
+//       total and draws a ticket from its problem's counter; the one that completes the problem's last set runs K1h: Horner over the set totals, then the outputs.
+// Nothing waits: a workgroup that is not the last arriver returns, and the last one reads only what is complete.  The pairs were written on other XCDs, whose L2s are
+// not coherent with this one: the writer drains its stores, releases at agent scope (L2 write-back) and then adds to the counter with an agent-scope atomic; the last
+// arriver acquires at agent scope (L1 / L2 invalidate) before any lane of the workgroup loads a pair.  `rows`, `set_total` and `tickets` are read and written inside
+// the launch: no __restrict__, no const, so that none of their loads goes to the scalar cache.  tickets: nsets + nprob words, zeroed in stream order before the launch.
+template <int F> __device__ __forceinline__ xyzz_t tail_block_sum(xyzz_t v, xyzz_t *s4) {      // one value per quad in, the sum of the 64 on quad 0 of wave 0
+    const uint32_t wave = threadIdx.x >> 6, q = (threadIdx.x & 63) >> 2;
+    v = quadwave_sum<F>(v, 16);
+    __syncthreads();                                         // s4 may still be read from an earlier call
+    if ((threadIdx.x & 63) == 0) s4[wave] = v;
+    __syncthreads();
+    xyzz_t t = xyzz_inf();
+    if (wave == 0) { t = (q < 4) ? s4[q] : xyzz_inf(); t = quadwave_sum<F>(t, 4); }
+    return t;
+}
+// sum_i v_i (sum) and sum_i i * v_i (wsum) over i < n <= 256, v_i = load(i), and -- with_x -- the plain sum of a second family x_i = extra(i) (xsum); all on quad 0
+// of wave 0.  Quad Q of the workgroup's 64 (Q = 16 wave + j) takes the P = 1, 2 or 4 consecutive values i = P Q + t, so that no wave walks more than one group of 16:
+//     sum_i i v_i = P * sum_Q Q s_Q + sum_Q l_Q,           s_Q = sum_t v_t,  l_Q = sum_t t v_t  (sums of suffix sums: no doubling)
+//     sum_Q Q s_Q = sum_w (X_w + 16 w S_w),                (S_w, X_w) = K1g's collective over the wave's 16 quads
+// and the four waves' S_w, X_w, L_w = sum_j l_j (and the x sums) are combined by waves 0 .. 3 side by side.  s_x[4][4], s_y[3]: staging in LDS.
+template <int F, class Load, class Extra>
+__device__ __forceinline__ void tail_weighted_block_sum(uint32_t n, bool with_x, Load load, Extra extra, xyzz_t (*s_x)[4], xyzz_t *s_y, xyzz_t &sum, xyzz_t &wsum, xyzz_t &xsum) {
+    const uint32_t wave = threadIdx.x >> 6, j = (threadIdx.x & 63) >> 2, Q = threadIdx.x >> 2;
+    const uint32_t log2P = n <= 64 ? 0 : (n <= 128 ? 1 : 2), P = 1u << log2P;
+    xyzz_t suf = xyzz_inf(), l = xyzz_inf(), x = xyzz_inf();
+#pragma unroll 1
+    for (uint32_t t = P - 1; t >= 1; --t) {                  // suffix sums v_t + .. + v_(P-1), t >= 1, and their sum
+        const uint32_t i = P * Q + t;
+        if (i < n) xyzz_add_quad<F>(suf, load(i));
+        xyzz_add_quad<F>(l, suf);
+    }
+    xyzz_t s = suf;
+    if (P * Q < n) xyzz_add_quad<F>(s, load(P * Q));
+    if (with_x) {
+#pragma unroll 1
+        for (uint32_t t = 0; t < P; ++t) { const uint32_t i = P * Q + t; if (i < n) xyzz_add_quad<F>(x, extra(i)); }
+    }
+    xyzz_t S;
+    const xyzz_t X = quadwave_weighted_sum<F>(s, S, 16);
+    if (P > 1) l = quadwave_sum<F>(l, 16);
+    if (with_x) x = quadwave_sum<F>(x, 16);
+    __syncthreads();                                         // the staging arrays may still be read from an earlier call
+    if ((threadIdx.x & 63) == 0) { s_x[0][wave] = S; s_x[1][wave] = X; s_x[2][wave] = l; s_x[3][wave] = x; }
+    __syncthreads();
+    xyzz_t y = xyzz_inf(), tot = xyzz_inf();
+    const xyzz_t v = (j < 4) ? s_x[wave][j] : xyzz_inf();
+    if (wave == 0) {                                          // sum_w S_w and 16 sum_w w S_w
+        y = quadwave_weighted_sum<F>(v, tot, 4);
+        if (threadIdx.x < 4) {
+#pragma unroll 1
+            for (int i = 0; i < 4; ++i) y = xyzz_dbl_quad<F>(y);
+        }
+    } else {                                                  // waves 1, 2, 3: sum_w X_w, sum_w L_w, sum_w of the x sums
+        const xyzz_t r = quadwave_sum<F>(v, 4);
+        if ((threadIdx.x & 63) == 0) s_y[wave - 1] = r;
+    }
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        xyzz_add_quad<F>(y, s_y[0]);
+#pragma unroll 1
+        for (uint32_t i = 0; i < log2P; ++i) y = xyzz_dbl_quad<F>(y);
+        xyzz_add_quad<F>(y, s_y[1]);
+        xsum = s_y[2];
+    }
+    sum = tot; wsum = y;
+}
+// publishes what lane 0 of the workgroup has stored and draws a ticket from *counter; true (on every lane) for the workgroup that drew ticket `last`, which may
+// then load what the others published.  Contains workgroup barriers: every lane calls it.
+__device__ __forceinline__ bool tail_last_arriver(uint32_t *counter, uint32_t last, uint32_t *s_ticket) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    if (threadIdx.x == 0) {
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                 // the stores have left the wave ...
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");               // ... and the XCD's L2, before the ticket that tells of them
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const uint32_t t = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (t == last) {
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");           // drop this CU's (and XCD's) copies of the others' lines; the barrier below holds the other waves' loads behind it
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        *s_ticket = t;
+    }
+    __syncthreads();
+    const bool is_last = *s_ticket == last;
+    __syncthreads();                                         // s_ticket is written again by the next call
+    return is_last;
+#else
+    return false;
+#endif
+}
+template <int F>
+__global__ void __launch_bounds__(256)
+msm_tail_kernel(uint32_t R, uint32_t nsets, uint32_t sets_per_prob, uint32_t c, const uint32_t *__restrict__ full_start, const uint32_t *__restrict__ rem_pos,
+                const uint32_t *__restrict__ info, const xyzz_t *__restrict__ partial, xyzz_t *rows /* 2 R nsets: (S_r, T_r) */, uint32_t *tickets /* nsets + nprob, zero */,
+                xyzz_t *set_total, fe_t one, fe_t pm2, xyzz_t *__restrict__ out_xyzz, uint32_t *__restrict__ out_words) { mb_wave_prio<1>();
+    constexpr uint32_t C = 128;
+    __shared__ xyzz_t s_b[C], s_x[4][4], s_y[3];
+    __shared__ uint32_t s_fs[C + 1], s_ticket;
+    const uint32_t tid = threadIdx.x, qi = tid >> 2, blk = blockIdx.x, b0 = blk * C, set = blk / R;
+    // (a) bucket sums
+    if (tid <= C) s_fs[tid] = full_start[b0 + tid];
+    __syncthreads();
+    const uint32_t nfull = info[0];
+    int filled = 0;
+#pragma unroll 1
+    for (uint32_t col = qi; col < C; col += 64) {
+        const uint32_t lo = s_fs[col], hi = s_fs[col + 1], rp = rem_pos[b0 + col];
+        xyzz_t acc = xyzz_inf();
+        filled |= (hi > lo) || rp != MSM_INVALID;
+        if (hi - lo <= MSM_HEAVY_TASKS) {                    // uniform within the quad
+            if (rp != MSM_INVALID) acc = partial[nfull + rp];
+            for (uint32_t t = lo; t < hi; ++t) xyzz_add_quad<F>(acc, partial[t]);
+        }
+        if ((tid & 3u) == 0) s_b[col] = acc;
+    }
+    xyzz_t sum = xyzz_inf(), wsum = xyzz_inf();
+    const bool any = __syncthreads_or(filled) != 0;          // (a row without an entry -- most rows of a short fixed-base call -- publishes two infinities at once)
+    if (any) {
+#pragma unroll 1
+        for (uint32_t col = 0; col < C; ++col) {             // the heavy buckets, one after the other, by the whole workgroup; every branch is uniform over it
+            const uint32_t lo = s_fs[col], hi = s_fs[col + 1];
+            if (hi - lo <= MSM_HEAVY_TASKS) continue;
+            const uint32_t rp = rem_pos[b0 + col];
+            xyzz_t acc = (qi == 0 && rp != MSM_INVALID) ? partial[nfull + rp] : xyzz_inf();
+            for (uint32_t t = lo + qi; t < hi; t += 64) xyzz_add_quad<F>(acc, partial[t]);
+            acc = tail_block_sum<F>(acc, s_x[0]);
+            if (tid == 0) s_b[col] = acc;
+        }
+        __syncthreads();                                     // every bucket of the row is in s_b
+    }
+    // (b) the row's pair, then (c) -- as the set's last arriver -- the set total: the same weighted sum, over the row's buckets and then over the set's S_r
+    const xyzz_t *rs = rows + 2 * (size_t)set * R;
+#pragma unroll 1
+    for (int phase = 0; phase < 2; ++phase) {
+        xyzz_t tsum = xyzz_inf();                            // phase 1: sum_r T_r
+        if (phase || any)
+            tail_weighted_block_sum<F>(phase ? R : C, phase != 0, [&](uint32_t i) { return phase ? rs[2 * i] : s_b[i]; }, [&](uint32_t i) { return rs[2 * i + 1]; }, s_x, s_y, sum, wsum, tsum);
+        const xyzz_t other = phase ? tsum : sum;             // what joins the weighted sum: the row's S_r | sum_r T_r
+        if (tid < 4) {
+            if (phase) { for (int i = 0; i < 7; ++i) wsum = xyzz_dbl_quad<F>(wsum); }         // * C
+            xyzz_add_quad<F>(wsum, other);                   // T_r = sum_c c B + S_r | the set total = C sum_r r S_r + sum_r T_r
+        }
+        if (phase == 0) {
+            if (tid == 0) { rows[2 * (size_t)blk] = sum; rows[2 * (size_t)blk + 1] = wsum; }
+            if (!tail_last_arriver(&tickets[set], R - 1, &s_ticket)) return;
+        }
+    }
+    const uint32_t prob = set / sets_per_prob;
+    if (tid == 0) set_total[set] = wsum;
+    if (!tail_last_arriver(&tickets[nsets + prob], sets_per_prob - 1, &s_ticket)) return;
+    // K1h, by the workgroup that completed the problem
+    if (tid >= 4) return;
+    const xyzz_t *st = set_total + (size_t)prob * sets_per_prob;
+    xyzz_t t = st[sets_per_prob - 1];
+    for (int w = (int)sets_per_prob - 2; w >= 0; --w) {
+        for (uint32_t i = 0; i < c; ++i) t = xyzz_dbl_quad<F>(t);
+        xyzz_add_quad<F>(t, st[w]);
+    }
+    if (tid != 0) return;
+    if (out_xyzz) out_xyzz[prob] = t;
+    if (!out_words) return;
+    out_words += (size_t)prob * 17;
+    if (xyzz_is_inf(t)) { for (int i = 0; i < 16; ++i) out_words[i] = 0; out_words[16] = 1; return; }
+    fe_t zi = fe_pow<F>(fe_mul<F>(t.zz, t.zzz), pm2, one);       // 1 / (zz * zzz)
+    fe_t izz = fe_mul<F>(zi, t.zzz), izzz = fe_mul<F>(zi, t.zz);
+    fe_t x = fe_from_mont<F>(fe_mul<F>(t.x, izz));
+    fe_t y = fe_from_mont<F>(fe_mul<F>(t.y, izzz));
+    for (int i = 0; i < 8; ++i) { out_words[i] = x.v[i]; out_words[8 + i] = y.v[i]; }
+    out_words[16] = 0;
+}
+
 // canonical affine bytes (x||y words) -> Montgomery affine; (0,0) stays infinity
 template <int F>
 __global__ void points_to_mont_kernel(uint32_t n, const uint32_t *__restrict__ in_words, fe_t r2, affine_t *__restrict__ out) {
