@@ -136,6 +136,40 @@ func (c *Ctx) MsmTailStats() (fusedRuns, stagedRuns uint64, err error) {
 	return uint64(a), uint64(b), nil
 }
 
+// SetFastInverse: MSMs queued after the call invert by batched divsteps at their finish (on) or by the power p - 2 (off, the default); the same bytes.
+func (c *Ctx) SetFastInverse(on bool) error {
+	v := 0
+	if on {
+		v = 1
+	}
+	if rc := C.mina_ctx_set_fast_inverse(c.p, C.int(v)); rc != 0 {
+		return lastError()
+	}
+	return nil
+}
+
+// InverseStats: MSM finishes the context has queued with the divstep inversion and with the power.
+func (c *Ctx) InverseStats() (gcdFinishes, fermatFinishes uint64, err error) {
+	var a, b C.uint64_t
+	if rc := C.mina_ctx_inverse_stats(c.p, &a, &b); rc != 0 {
+		return 0, 0, lastError()
+	}
+	return uint64(a), uint64(b), nil
+}
+
+// FieldInvGcd: n field inverses (32-byte little-endian elements, 0 -> 0) by the divstep iteration; the bytes of mina_field_inv.
+func (c *Ctx) FieldInvGcd(field int, a []byte) ([]byte, error) {
+	n := len(a) / 32
+	out := make([]byte, n*32)
+	if n == 0 {
+		return out, nil
+	}
+	if rc := C.mina_field_inv_gcd(c.p, C.int(field), C.size_t(n), (*C.uint8_t)(unsafe.Pointer(&a[0])), (*C.uint8_t)(unsafe.Pointer(&out[0]))); rc != 0 {
+		return nil, lastError()
+	}
+	return out, nil
+}
+
 // StateJobEachDev: per-proof verdicts (one uint32 each in dVerdicts) of a Proof-of-State job whose inputs are in HBM; waits for its lane.
 func (c *Ctx) StateJobEachDev(jobs *C.mina_state_jobs, dVerdicts, dFlags unsafe.Pointer) error {
 	if rc := C.mina_state_job_each_dev(c.p, jobs, dVerdicts, dFlags); rc != 0 {

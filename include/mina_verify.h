@@ -206,6 +206,9 @@ int mina_to_group(mina_ctx *ctx, int curve, size_t n, const uint8_t *t, uint8_t 
 /* ---- field self-test hooks (used by the parity tests only) ----------------------------------- */
 int mina_field_mul(mina_ctx *ctx, int field, size_t n, const uint8_t *a, const uint8_t *b, uint8_t *out);
 int mina_field_inv(mina_ctx *ctx, int field, size_t n, const uint8_t *a, uint8_t *out);
+/* mina_field_inv by the divstep iteration (below: mina_ctx_set_fast_inverse) instead of the power p - 2, whatever the context's mode: the same arguments, the same
+ * errors, the same bytes (0 -> 0). */
+int mina_field_inv_gcd(mina_ctx *ctx, int field, size_t n, const uint8_t *a, uint8_t *out);
 int mina_field_sqrt(mina_ctx *ctx, int field, size_t n, const uint8_t *a, uint8_t *out, uint8_t *out_is_square);
 /* group law: the same chain of XYZZ additions/doublings on (P_i, Q_i) with the single-lane and with the 4-lane cooperative
  * routines; both results as affine points, same[i] = 1 iff the XYZZ coordinates agreed word for word at every step */
@@ -616,6 +619,20 @@ int mina_ctx_seg_fold_stats(mina_ctx *ctx, uint64_t *mfma_segments, uint64_t *va
  * mina_ctx_msm_tail_stats: MSMs this context has queued with the fused tail and with the staged one since it was created. */
 int mina_ctx_set_msm_fused_tail(mina_ctx *ctx, int on);      /* default 0; takes effect for the calls queued after it */
 int mina_ctx_msm_tail_stats(mina_ctx *ctx, uint64_t *fused_runs, uint64_t *staged_runs);
+/* The one field inversion at the end of every MSM -- 1 / (zz * zzz), which turns the XYZZ result into the affine record, on a single lane -- by batched divsteps
+ * (Bernstein-Yang "safegcd"; mina_bridge_amd/csrc/fe_modinv.cuh) instead of the power p - 2 (opt-in).  on: 0 or 1; the default is 0.  With the mode on, the finish
+ * of every MSM queued afterwards -- its own kernel, or the last step of the fused tail where mina_ctx_set_msm_fused_tail is on -- runs at most 25 batches of 30
+ * branch-free divsteps on nine signed 30-bit limbs in place of 254 dependent squarings: a FIXED bound (750 divsteps, above the 741 proven to suffice for 256-bit
+ * inputs), never a loop that waits for data.  The inverse of a field element is unique: records, points and verdicts are the same bytes as with the mode off.
+ * The mode does not touch anything else: mina_field_inv, the square roots, SRS and Lagrange generation, the transcript kernels (kimchi, IPA, Pickles), the
+ * normalisations of the state and shard paths, the launch shapes and the workspace all stay as they are, and the boundary (mina_verify_*) does not use the mode.
+ * Takes effect for the calls queued after it; a view context takes its parent's setting when it is created or refreshed.
+ * Measured on one MI355X (tools/bench_inverse.py, profiles/fast_inverse.json): the finish stage of a lone 2^16 MSM 198 -> 51 us, the lone MSM 569 -> 422 us wall; a
+ * lone accumulator check, whose MSM hands out XYZZ and has no finish, is level.
+ * mina_ctx_inverse_stats: MSM finishes this context has queued with the divstep inversion and with the power since it was created (an MSM that asks for the XYZZ
+ * result of a single bucket set alone has no finish and counts in neither). */
+int mina_ctx_set_fast_inverse(mina_ctx *ctx, int on);        /* default 0; takes effect for the MSMs queued after it */
+int mina_ctx_inverse_stats(mina_ctx *ctx, uint64_t *gcd_finishes, uint64_t *fermat_finishes);
 /* Test-facing: *live = the streams the context's lanes hold now, *made_by_searches = the streams its culprit searches have created since the context was created
  * (the fan search creates the streams its lanes lack and destroys them when it is done; the grouped search creates none and queues on the job's lane only). */
 int mina_ctx_lane_streams(mina_ctx *ctx, uint32_t *live, uint64_t *made_by_searches);

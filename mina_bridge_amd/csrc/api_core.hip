@@ -188,6 +188,19 @@ extern "C" int mina_field_inv(mina_ctx *c, int field, size_t n, const uint8_t *a
     DISPATCH_FIELD(field, { field_inv_kernel<F_><<<cdiv(n, 256), 256, 0, c->L->stream>>>((uint32_t)n, c->fk[F_], c->L->tmp_a.as<uint32_t>(), c->L->tmp_c.as<uint32_t>()); });
     return d2h_sync(c, out, c->L->tmp_c, n * 32);
 }
+// mina_field_inv on the divstep inversion (fe_modinv.cuh), whatever mina_ctx_set_fast_inverse says: the same arguments, errors and bytes
+extern "C" int mina_field_inv_gcd(mina_ctx *c, int field, size_t n, const uint8_t *a, uint8_t *out) {
+    if (!c || (n && (!a || !out))) return fail(MINA_ERR_ARG, "null argument");
+    if (bad_field(field)) return fail(MINA_ERR_ARG, "bad field");
+    if (n == 0) return MINA_OK;
+    HIPC(hipSetDevice(c->device));
+    c->use_lane0();
+    int rc;
+    if ((rc = h2d(c, c->L->tmp_a, a, n * 32))) return rc;
+    if ((rc = c->L->tmp_c.ensure(n * 32))) return rc;
+    DISPATCH_FIELD(field, { field_inv_gcd_kernel<F_><<<cdiv(n, 256), 256, 0, c->L->stream>>>((uint32_t)n, c->fk[F_], c->L->tmp_a.as<uint32_t>(), c->L->tmp_c.as<uint32_t>()); });
+    return d2h_sync(c, out, c->L->tmp_c, n * 32);
+}
 extern "C" int mina_field_sqrt(mina_ctx *c, int field, size_t n, const uint8_t *a, uint8_t *out, uint8_t *ok) {
     if (!c || (n && (!a || !out || !ok))) return fail(MINA_ERR_ARG, "null argument");
     if (bad_field(field)) return fail(MINA_ERR_ARG, "bad field");

@@ -98,7 +98,7 @@ template <class Fn> static inline void with_form(bool b, Fn &&f) { if (b) f(std:
 // one call's launches: the five stages, in the order run_msm calls them, over the plan, the lane's workspace and stream and the base field's constants
 template <int F>
 struct MsmRun {
-    mina_ctx *c; const MsmPlan &p; MsmWorkspace &w; hipStream_t st; const FieldK &fk;
+    mina_ctx *c; const MsmPlan &p; MsmWorkspace &w; hipStream_t st; const FieldK &fk; bool gcd_inverse;      // gcd_inverse: mina_ctx::fast_inverse when the call was queued
     // one pass of the partitioned sort's level 1 (K1p-a counts, K1p-c scatters into the staging array), over segments or over problems of sh.n scalars
     template <bool SCATTER> void part_pass(const uint32_t *d_scalars, const MsmSegments *seg) {
         const uint32_t grid = p.ss.Gl * p.sh.nprob;
@@ -195,10 +195,11 @@ struct MsmRun {
         return MINA_OK;
     }
 
-    // stage 5: a problem's set totals -> its result, affine record and / or XYZZ
+    // stage 5: a problem's set totals -> its result, affine record and / or XYZZ; gcd_inverse (mina_ctx_set_fast_inverse): the kernel whose inversion is fe_modinv.cuh's
     void finish(uint32_t *d_out_words, xyzz_t *d_out_xyzz) {
         ProfScope ps_(c, PS_FINISH);
-        msm_finish_kernel<F><<<p.sh.nprob, 64, 0, st>>>(p.sh.nsets / p.sh.nprob, p.sh.c, w.set_total.as<xyzz_t>(), fk.one, fk.pm2, d_out_xyzz, d_out_words);
+        if (gcd_inverse) msm_finish_gcd_kernel<F><<<p.sh.nprob, 64, 0, st>>>(p.sh.nsets / p.sh.nprob, p.sh.c, w.set_total.as<xyzz_t>(), fk.r2, d_out_xyzz, d_out_words);
+        else msm_finish_kernel<F><<<p.sh.nprob, 64, 0, st>>>(p.sh.nsets / p.sh.nprob, p.sh.c, w.set_total.as<xyzz_t>(), fk.one, fk.pm2, d_out_xyzz, d_out_words);
     }
 
     // stages 3 - 5 of a p.fused_tail plan in one launch: a workgroup per row of 128 buckets; the last arriver of a set totals it, the last of a problem finishes it.
@@ -206,8 +207,12 @@ struct MsmRun {
     int tail(uint32_t *d_out_words, xyzz_t *d_out_xyzz) {
         ProfScope ps_(c, PS_BUCKET_SUM);
         HIPC(hipMemsetAsync(w.tail_tickets.p, 0, tail_ticket_bytes(p), st));
-        msm_tail_kernel<F><<<p.R * p.sh.nsets, 256, 0, st>>>(p.R, p.sh.nsets, p.sh.nsets / p.sh.nprob, p.sh.c, w.task_start.as<uint32_t>(), w.rem_pos.as<uint32_t>(), w.info.as<uint32_t>(), w.partial.as<xyzz_t>(),
-                                                             w.tail_rows.as<xyzz_t>(), w.tail_tickets.as<uint32_t>(), w.set_total.as<xyzz_t>(), fk.one, fk.pm2, d_out_xyzz, d_out_words);
+        if (gcd_inverse)
+            msm_tail_gcd_kernel<F><<<p.R * p.sh.nsets, 256, 0, st>>>(p.R, p.sh.nsets, p.sh.nsets / p.sh.nprob, p.sh.c, w.task_start.as<uint32_t>(), w.rem_pos.as<uint32_t>(), w.info.as<uint32_t>(), w.partial.as<xyzz_t>(),
+                                                                     w.tail_rows.as<xyzz_t>(), w.tail_tickets.as<uint32_t>(), w.set_total.as<xyzz_t>(), fk.r2, d_out_xyzz, d_out_words);
+        else
+            msm_tail_kernel<F><<<p.R * p.sh.nsets, 256, 0, st>>>(p.R, p.sh.nsets, p.sh.nsets / p.sh.nprob, p.sh.c, w.task_start.as<uint32_t>(), w.rem_pos.as<uint32_t>(), w.info.as<uint32_t>(), w.partial.as<xyzz_t>(),
+                                                                 w.tail_rows.as<xyzz_t>(), w.tail_tickets.as<uint32_t>(), w.set_total.as<xyzz_t>(), fk.one, fk.pm2, d_out_xyzz, d_out_words);
         return MINA_OK;
     }
 };
@@ -221,7 +226,7 @@ static int run_msm(mina_ctx *c, const MsmShape &sh, const uint32_t *d_scalars, c
     MsmPlan p;
     if (int rc = msm_plan(sh, c->nlanes, mb_tune().msm_fp29, d_points29 != nullptr, d_points29 && d_points29s, d_out_words != nullptr, d_out_xyzz != nullptr, c->msm_fused_tail, p)) return rc;
     if (int rc = msm_reserve(c->L->ws, p)) return rc;
-    MsmRun<F> run{c, p, c->L->ws, c->L->stream, c->fk[F]};
+    MsmRun<F> run{c, p, c->L->ws, c->L->stream, c->fk[F], c->fast_inverse};
     if (int rc = run.sort(d_scalars, seg)) return rc;
     run.accumulate(d_points, p.law == LAW_SPLIT ? d_points29s : p.law == LAW_TWIN ? d_points29 : nullptr);
     if (p.fused_tail) { if (int rc = run.tail(d_out_words, d_out_xyzz)) return rc; }
@@ -232,6 +237,7 @@ static int run_msm(mina_ctx *c, const MsmShape &sh, const uint32_t *d_scalars, c
     }
     HIPC(hipGetLastError());
     ++(p.fused_tail ? c->mt_fused_runs : c->mt_staged_runs);
+    if (p.fused_tail || !p.fused_finish) ++(run.gcd_inverse ? c->inv_gcd_finishes : c->inv_fermat_finishes);      // a finish ran, in the tail kernel or on its own
     return MINA_OK;
 }
 
@@ -343,6 +349,19 @@ extern "C" int mina_ctx_set_msm_fused_tail(mina_ctx *c, int on) {
 extern "C" int mina_ctx_msm_tail_stats(mina_ctx *c, uint64_t *fused_runs, uint64_t *staged_runs) {
     if (!c || !fused_runs || !staged_runs) return fail(MINA_ERR_ARG, "null argument");
     *fused_runs = c->mt_fused_runs; *staged_runs = c->mt_staged_runs;
+    return MINA_OK;
+}
+
+extern "C" int mina_ctx_set_fast_inverse(mina_ctx *c, int on) {
+    if (!c) return fail(MINA_ERR_ARG, "null argument");
+    if (on != 0 && on != 1) return fail(MINA_ERR_ARG, "fast inverse: 0 (off) or 1 (on)");
+    c->fast_inverse = on != 0;
+    return MINA_OK;
+}
+
+extern "C" int mina_ctx_inverse_stats(mina_ctx *c, uint64_t *gcd_finishes, uint64_t *fermat_finishes) {
+    if (!c || !gcd_finishes || !fermat_finishes) return fail(MINA_ERR_ARG, "null argument");
+    *gcd_finishes = c->inv_gcd_finishes; *fermat_finishes = c->inv_fermat_finishes;
     return MINA_OK;
 }
 

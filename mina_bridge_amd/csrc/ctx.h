@@ -238,6 +238,10 @@ struct mina_ctx : Installed {
     // The fused MSM tail (mina_ctx_set_msm_fused_tail; api_msm.hip MsmPlan::fused_tail): task-form MSMs run bucket sums, reduction and finish as ONE launch.
     // mina_ctx_msm_tail_stats: MSMs queued with either tail, counted by the context that queued them.
     bool msm_fused_tail = false; uint64_t mt_fused_runs = 0, mt_staged_runs = 0;
+    // The fast inverse (mina_ctx_set_fast_inverse): the one inversion at the end of an MSM -- msm_finish_kernel's, or the fused tail's -- is the divstep iteration of
+    // fe_modinv.cuh instead of the power p - 2; the same bytes.  mina_ctx_inverse_stats: MSM finishes queued with either form, counted by the context that queued them
+    // (an MSM whose reduction kernel hands out the XYZZ result itself has no finish and counts as neither).
+    bool fast_inverse = false; uint64_t inv_gcd_finishes = 0, inv_fermat_finishes = 0;
     uint64_t search_streams_made = 0;  // streams any culprit search of this context has created (the fan search, for the lanes it lacks): mina_ctx_lane_streams
     // mina_state_job_batch without its upload: per-proof verdicts (host bytes) of a job whose inputs are in HBM, on lane 0, waited for (api_state.hip
     // mb_state_job_each_host).  Filled by mina_ctx_create; the boundary hands a failed chunk's device staging to it under MINA_VERIFY_GROUPED_SEARCH, and a context
@@ -251,7 +255,7 @@ struct mina_ctx : Installed {
     void use_lane0() { L = &lanes[0]; }
     void next_lane() { L = pinned >= 0 ? &lanes[pinned] : &lanes[rr++ % (unsigned)nlanes]; }
 };
-static inline void mb_ctx_refresh_view(mina_ctx *view, mina_ctx *parent) { view->borrow_from(*parent); view->msm_fused_tail = parent->msm_fused_tail; }
+static inline void mb_ctx_refresh_view(mina_ctx *view, mina_ctx *parent) { view->borrow_from(*parent); view->msm_fused_tail = parent->msm_fused_tail; view->fast_inverse = parent->fast_inverse; }
 
 // waits for everything the `_dev` entry points have queued: the pipeline lanes and, for jobs that ran under plan B, the role streams
 static inline hipError_t mb_ctx_wait_all(mina_ctx *c) {

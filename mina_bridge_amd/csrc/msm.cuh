@@ -18,6 +18,7 @@
 #pragma once
 #include "ec.cuh"
 #include "ec29.cuh"
+#include "fe_modinv.cuh"
 
 namespace mb {
 
@@ -1086,9 +1087,28 @@ msm_reduce2d_kernel(uint32_t Gr, uint32_t Gc, uint32_t log2C, const xyzz_t *__re
 // K1h: per problem (one block each): Horner over its bucket sets (variable-base; a fixed-base problem has one set),
 // then normalise to affine (Montgomery) + canonical words.
 //   out_words[17 m + 0..16) = x||y canonical little-endian words, out_words[17 m + 16] = 1 if infinity; out_xyzz[m].
-template <int F>
-__global__ void msm_finish_kernel(uint32_t nsets /* per problem */, uint32_t c, const xyzz_t *__restrict__ set_total, fe_t one,
-                                  fe_t pm2, xyzz_t *__restrict__ out_xyzz, uint32_t *__restrict__ out_words) { mb_wave_prio<1>();
+// The one inversion of an MSM, 1 / (zz * zzz), comes in two forms that give the same words: Fermat (fe_pow by p - 2; the default) and the divstep iteration of
+// fe_modinv.cuh (mina_ctx_set_fast_inverse).  A kernel has ONE of them, chosen by its Inv type: msm_finish_kernel / msm_tail_kernel are the bodies below with
+// InvFermat, msm_finish_gcd_kernel / msm_tail_gcd_kernel the same bodies with InvGcd.
+struct InvFermat { const fe_t &one, &pm2; /* the kernel's own arguments: fe_pow indexes pm2, which stays where the arguments are */ template <int F> __device__ __forceinline__ fe_t inv(const fe_t &a) const { return fe_pow<F>(a, pm2, one); } };
+struct InvGcd { fe_t r2; template <int F> __device__ __forceinline__ fe_t inv(const fe_t &a) const { return fe_inv_gcd_r2<F>(a, r2); } };
+
+// lane 0 of the finishing quad: the XYZZ result -> the outputs that were asked for
+template <int F, class Inv>
+__device__ __forceinline__ void msm_finish_outputs(const xyzz_t &t, const Inv &inv, xyzz_t *__restrict__ out_xyzz, uint32_t *__restrict__ out_words) {
+    if (out_xyzz) *out_xyzz = t;
+    if (!out_words) return;
+    if (xyzz_is_inf(t)) { for (int i = 0; i < 16; ++i) out_words[i] = 0; out_words[16] = 1; return; }
+    fe_t zi = inv.template inv<F>(fe_mul<F>(t.zz, t.zzz));       // 1 / (zz * zzz)
+    fe_t izz = fe_mul<F>(zi, t.zzz), izzz = fe_mul<F>(zi, t.zz);
+    fe_t x = fe_from_mont<F>(fe_mul<F>(t.x, izz));
+    fe_t y = fe_from_mont<F>(fe_mul<F>(t.y, izzz));
+    for (int i = 0; i < 8; ++i) { out_words[i] = x.v[i]; out_words[8 + i] = y.v[i]; }
+    out_words[16] = 0;
+}
+template <int F, class Inv>
+__device__ __forceinline__ void msm_finish_body(uint32_t nsets /* per problem */, uint32_t c, const xyzz_t *__restrict__ set_total, const Inv &inv,
+                                                xyzz_t *__restrict__ out_xyzz, uint32_t *__restrict__ out_words) {
     if (threadIdx.x >= 4) return;                              // one quad: lane-cooperative doublings / adds
     set_total += (size_t)blockIdx.x * nsets;
     if (out_xyzz) out_xyzz += blockIdx.x;
@@ -1099,15 +1119,17 @@ __global__ void msm_finish_kernel(uint32_t nsets /* per problem */, uint32_t c, 
         xyzz_add_quad<F>(t, set_total[w]);
     }
     if (threadIdx.x != 0) return;
-    if (out_xyzz) *out_xyzz = t;
-    if (!out_words) return;
-    if (xyzz_is_inf(t)) { for (int i = 0; i < 16; ++i) out_words[i] = 0; out_words[16] = 1; return; }
-    fe_t zi = fe_pow<F>(fe_mul<F>(t.zz, t.zzz), pm2, one);       // 1 / (zz * zzz)
-    fe_t izz = fe_mul<F>(zi, t.zzz), izzz = fe_mul<F>(zi, t.zz);
-    fe_t x = fe_from_mont<F>(fe_mul<F>(t.x, izz));
-    fe_t y = fe_from_mont<F>(fe_mul<F>(t.y, izzz));
-    for (int i = 0; i < 8; ++i) { out_words[i] = x.v[i]; out_words[8 + i] = y.v[i]; }
-    out_words[16] = 0;
+    msm_finish_outputs<F>(t, inv, out_xyzz, out_words);
+}
+template <int F>
+__global__ void msm_finish_kernel(uint32_t nsets /* per problem */, uint32_t c, const xyzz_t *__restrict__ set_total, fe_t one,
+                                  fe_t pm2, xyzz_t *__restrict__ out_xyzz, uint32_t *__restrict__ out_words) { mb_wave_prio<1>();
+    msm_finish_body<F>(nsets, c, set_total, InvFermat{one, pm2}, out_xyzz, out_words);
+}
+template <int F>
+__global__ void msm_finish_gcd_kernel(uint32_t nsets /* per problem */, uint32_t c, const xyzz_t *__restrict__ set_total, fe_t r2,
+                                      xyzz_t *__restrict__ out_xyzz, uint32_t *__restrict__ out_words) { mb_wave_prio<1>();
+    msm_finish_body<F>(nsets, c, set_total, InvGcd{r2}, out_xyzz, out_words);
 }
 
 // ---------------------------------------------------------------- K1z: K1e, K1e', K1f, K1g, K1g' and K1h in ONE launch (opt-in: mina_ctx_set_msm_fused_tail)
@@ -1206,11 +1228,11 @@ __device__ __forceinline__ bool tail_last_arriver(uint32_t *counter, uint32_t la
     return false;
 #endif
 }
-template <int F>
-__global__ void __launch_bounds__(256)
-msm_tail_kernel(uint32_t R, uint32_t nsets, uint32_t sets_per_prob, uint32_t c, const uint32_t *__restrict__ full_start, const uint32_t *__restrict__ rem_pos,
-                const uint32_t *__restrict__ info, const xyzz_t *__restrict__ partial, xyzz_t *rows /* 2 R nsets: (S_r, T_r) */, uint32_t *tickets /* nsets + nprob, zero */,
-                xyzz_t *set_total, fe_t one, fe_t pm2, xyzz_t *__restrict__ out_xyzz, uint32_t *__restrict__ out_words) { mb_wave_prio<1>();
+template <int F, class Inv>
+__device__ __forceinline__ void
+msm_tail_body(uint32_t R, uint32_t nsets, uint32_t sets_per_prob, uint32_t c, const uint32_t *__restrict__ full_start, const uint32_t *__restrict__ rem_pos,
+              const uint32_t *__restrict__ info, const xyzz_t *__restrict__ partial, xyzz_t *rows /* 2 R nsets: (S_r, T_r) */, uint32_t *tickets /* nsets + nprob, zero */,
+              xyzz_t *set_total, const Inv &inv, xyzz_t *__restrict__ out_xyzz, uint32_t *__restrict__ out_words) {
     constexpr uint32_t C = 128;
     __shared__ xyzz_t s_b[C], s_x[4][4], s_y[3];
     __shared__ uint32_t s_fs[C + 1], s_ticket;
@@ -1275,16 +1297,22 @@ msm_tail_kernel(uint32_t R, uint32_t nsets, uint32_t sets_per_prob, uint32_t c, 
         xyzz_add_quad<F>(t, st[w]);
     }
     if (tid != 0) return;
-    if (out_xyzz) out_xyzz[prob] = t;
-    if (!out_words) return;
-    out_words += (size_t)prob * 17;
-    if (xyzz_is_inf(t)) { for (int i = 0; i < 16; ++i) out_words[i] = 0; out_words[16] = 1; return; }
-    fe_t zi = fe_pow<F>(fe_mul<F>(t.zz, t.zzz), pm2, one);       // 1 / (zz * zzz)
-    fe_t izz = fe_mul<F>(zi, t.zzz), izzz = fe_mul<F>(zi, t.zz);
-    fe_t x = fe_from_mont<F>(fe_mul<F>(t.x, izz));
-    fe_t y = fe_from_mont<F>(fe_mul<F>(t.y, izzz));
-    for (int i = 0; i < 8; ++i) { out_words[i] = x.v[i]; out_words[8 + i] = y.v[i]; }
-    out_words[16] = 0;
+    msm_finish_outputs<F>(t, inv, out_xyzz ? out_xyzz + prob : nullptr, out_words ? out_words + (size_t)prob * 17 : nullptr);
+}
+
+template <int F>
+__global__ void __launch_bounds__(256)
+msm_tail_kernel(uint32_t R, uint32_t nsets, uint32_t sets_per_prob, uint32_t c, const uint32_t *__restrict__ full_start, const uint32_t *__restrict__ rem_pos,
+                const uint32_t *__restrict__ info, const xyzz_t *__restrict__ partial, xyzz_t *rows /* 2 R nsets: (S_r, T_r) */, uint32_t *tickets /* nsets + nprob, zero */,
+                xyzz_t *set_total, fe_t one, fe_t pm2, xyzz_t *__restrict__ out_xyzz, uint32_t *__restrict__ out_words) { mb_wave_prio<1>();
+    msm_tail_body<F>(R, nsets, sets_per_prob, c, full_start, rem_pos, info, partial, rows, tickets, set_total, InvFermat{one, pm2}, out_xyzz, out_words);
+}
+template <int F>
+__global__ void __launch_bounds__(256)
+msm_tail_gcd_kernel(uint32_t R, uint32_t nsets, uint32_t sets_per_prob, uint32_t c, const uint32_t *__restrict__ full_start, const uint32_t *__restrict__ rem_pos,
+                    const uint32_t *__restrict__ info, const xyzz_t *__restrict__ partial, xyzz_t *rows /* 2 R nsets: (S_r, T_r) */, uint32_t *tickets /* nsets + nprob, zero */,
+                    xyzz_t *set_total, fe_t r2, xyzz_t *__restrict__ out_xyzz, uint32_t *__restrict__ out_words) { mb_wave_prio<1>();
+    msm_tail_body<F>(R, nsets, sets_per_prob, c, full_start, rem_pos, info, partial, rows, tickets, set_total, InvGcd{r2}, out_xyzz, out_words);
 }
 
 // canonical affine bytes (x||y words) -> Montgomery affine; (0,0) stays infinity

@@ -7,6 +7,7 @@
 //   kimchi `ScalarChallenge::to_field`.
 #pragma once
 #include "groupmap.cuh"
+#include "fe_modinv.cuh"
 #include "fp29.cuh"
 
 namespace mb {
@@ -666,6 +667,15 @@ __global__ void field_inv_kernel(uint32_t n, FieldK fk, const uint32_t *a, uint3
     if (i >= n) return;
     fe_t x; for (int q = 0; q < 8; ++q) x.v[q] = a[(size_t)i * 8 + q];
     fe_t r = fe_from_mont<F>(fe_inv<F>(fe_to_mont<F>(x, fk.r2), fk));
+    for (int q = 0; q < 8; ++q) out[(size_t)i * 8 + q] = r.v[q];
+}
+// field_inv_kernel with the divstep inversion (fe_modinv.cuh): the same words out, 0 -> 0
+template <int F>
+__global__ void field_inv_gcd_kernel(uint32_t n, FieldK fk, const uint32_t *a, uint32_t *out) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    fe_t x; for (int q = 0; q < 8; ++q) x.v[q] = a[(size_t)i * 8 + q];
+    fe_t r = fe_from_mont<F>(fe_inv_gcd<F>(fe_to_mont<F>(x, fk.r2), fk));
     for (int q = 0; q < 8; ++q) out[(size_t)i * 8 + q] = r.v[q];
 }
 template <int F>

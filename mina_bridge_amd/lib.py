@@ -31,7 +31,7 @@ EXPORTS = [
     "mina_b_poly", "mina_b_poly_coefficients", "mina_b_poly_fold", "mina_b_poly_fold_dev",
     "mina_poseidon_set_params", "mina_poseidon_params_parse", "mina_poseidon_load_params", "mina_poseidon_load_params_file", "mina_poseidon_permute", "mina_poseidon_permute_dev", "mina_poseidon_hash",
     "mina_challenge_to_field", "mina_fq_sponge_run", "mina_to_group", "mina_merkle_roots", "mina_merkle_verify_batch",
-    "mina_field_mul", "mina_field_inv", "mina_field_sqrt", "mina_selftest_group_law", "mina_selftest_fe29", "mina_selftest_fe32",
+    "mina_field_mul", "mina_field_inv", "mina_field_inv_gcd", "mina_field_sqrt", "mina_selftest_group_law", "mina_selftest_fe29", "mina_selftest_fe32",
     "mina_accumulator_check_batch", "mina_accumulator_check_dev", "mina_accumulator_check_multi_dev", "mina_accumulator_check_multi", "mina_ipa_batch_check", "mina_selftest_ipa_rows",
     "mina_consensus_project_window", "mina_consensus_relative_min_window_density", "mina_consensus_is_short_range",
     "mina_protocol_state_pack", "mina_protocol_state_hash_batch", "mina_protocol_state_hash_bytes",
@@ -39,7 +39,7 @@ EXPORTS = [
     "mina_protocol_state_pack_dev", "mina_state_frontend_dev", "mina_account_frontend_dev", "mina_account_job_dev",
     "mina_state_jobs_prepare", "mina_state_job_batch_dev", "mina_state_job_batch", "mina_state_job_fold_dev",
     "mina_challenge_to_field_dev", "mina_field_sum_rows_dev", "mina_msm_srs_range_dev", "mina_msm_dev", "mina_points_sum_dev", "mina_point_records_equal_dev",
-    "mina_msm_segments_dev", "mina_b_poly_fold_segments_dev", "mina_state_job_each_dev", "mina_ctx_set_search_groups", "mina_ctx_search_stats", "mina_ctx_set_seg_fold_mfma_min", "mina_ctx_seg_fold_stats", "mina_ctx_set_msm_fused_tail", "mina_ctx_msm_tail_stats", "mina_ctx_lane_streams", "mina_ctx_set_stream_budget",
+    "mina_msm_segments_dev", "mina_b_poly_fold_segments_dev", "mina_state_job_each_dev", "mina_ctx_set_search_groups", "mina_ctx_search_stats", "mina_ctx_set_seg_fold_mfma_min", "mina_ctx_seg_fold_stats", "mina_ctx_set_msm_fused_tail", "mina_ctx_msm_tail_stats", "mina_ctx_set_fast_inverse", "mina_ctx_inverse_stats", "mina_ctx_lane_streams", "mina_ctx_set_stream_budget",
     "mina_step_index_install", "mina_step_index_load_json", "mina_polish_tokens_from_json", "mina_verifier_index_load_json", "mina_pickles_public_input",
     "mina_verifier_index_install", "mina_verifier_index_digest", "mina_kimchi_to_batch", "mina_pickles_public_inputs_batch", "mina_wrap_proof_flatten", "mina_state_proof_split",
     "mina_verify_state", "mina_verify_state_batch", "mina_verify_state_checks", "mina_verify_state_files", "mina_verify_account", "mina_verify_account_batch",
@@ -896,6 +896,14 @@ class MinaContext:
         self._ck(self._lib.mina_field_inv(self._h, field, ctypes.c_size_t(n), _p(a), _p(out)), "mina_field_inv")
         return out
 
+    def field_inv_gcd(self, field: int, a) -> np.ndarray:
+        """field_inv by the divstep iteration (fe_modinv.cuh), whatever set_fast_inverse says: the same bytes, 0 -> 0"""
+        a = _u8(a)
+        n = a.size // 32
+        out = np.empty((n, 32), np.uint8)
+        self._ck(self._lib.mina_field_inv_gcd(self._h, field, ctypes.c_size_t(n), _p(a), _p(out)), "mina_field_inv_gcd")
+        return out
+
     def field_sqrt(self, field: int, a):
         a = _u8(a)
         n = a.size // 32
@@ -1178,6 +1186,17 @@ class MinaContext:
         a, b = ctypes.c_uint64(0), ctypes.c_uint64(0)
         self._ck(self._lib.mina_ctx_msm_tail_stats(self._h, ctypes.byref(a), ctypes.byref(b)), "mina_ctx_msm_tail_stats")
         return {"fused_runs": a.value, "staged_runs": b.value}
+
+    def set_fast_inverse(self, on: bool):
+        """MSMs queued after the call invert by batched divsteps (msm_finish_gcd_kernel / msm_tail_gcd_kernel: at most 25 batches of 30) at their finish; off, the
+        default: the power p - 2.  The same bytes either way"""
+        self._ck(self._lib.mina_ctx_set_fast_inverse(self._h, ctypes.c_int(1 if on else 0)), "mina_ctx_set_fast_inverse")
+
+    def inverse_stats(self) -> dict:
+        """MSM finishes this context has queued with the divstep inversion / with the power since it was created"""
+        a, b = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self._ck(self._lib.mina_ctx_inverse_stats(self._h, ctypes.byref(a), ctypes.byref(b)), "mina_ctx_inverse_stats")
+        return {"gcd_finishes": a.value, "fermat_finishes": b.value}
 
     def lane_streams(self) -> dict:
         """test-facing: streams the context's lanes hold now, and streams its culprit searches have created so far"""
