@@ -157,6 +157,27 @@ func (c *Ctx) InverseStats() (gcdFinishes, fermatFinishes uint64, err error) {
 	return uint64(a), uint64(b), nil
 }
 
+// SetChainInverse: the scalar stages of the wrap-proof chain and the Lagrange set-up queued after the call invert by batched divsteps (on) or by the power p - 2 (off, the default); the same bytes.
+func (c *Ctx) SetChainInverse(on bool) error {
+	v := 0
+	if on {
+		v = 1
+	}
+	if rc := C.mina_ctx_set_chain_inverse(c.p, C.int(v)); rc != 0 {
+		return lastError()
+	}
+	return nil
+}
+
+// ChainInverseStats: launches of the kernels SetChainInverse covers that the context has queued in the divstep form and in the power form.
+func (c *Ctx) ChainInverseStats() (gcdLaunches, fermatLaunches uint64, err error) {
+	var a, b C.uint64_t
+	if rc := C.mina_ctx_chain_inverse_stats(c.p, &a, &b); rc != 0 {
+		return 0, 0, lastError()
+	}
+	return uint64(a), uint64(b), nil
+}
+
 // FieldInvGcd: n field inverses (32-byte little-endian elements, 0 -> 0) by the divstep iteration; the bytes of mina_field_inv.
 func (c *Ctx) FieldInvGcd(field int, a []byte) ([]byte, error) {
 	n := len(a) / 32

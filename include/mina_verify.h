@@ -633,6 +633,26 @@ int mina_ctx_msm_tail_stats(mina_ctx *ctx, uint64_t *fused_runs, uint64_t *stage
  * result of a single bucket set alone has no finish and counts in neither). */
 int mina_ctx_set_fast_inverse(mina_ctx *ctx, int on);        /* default 0; takes effect for the MSMs queued after it */
 int mina_ctx_inverse_stats(mina_ctx *ctx, uint64_t *gcd_finishes, uint64_t *fermat_finishes);
+/* The chain inverse: the single-lane field inversions in the scalar stages of the wrap-proof chain and in the Lagrange set-up by the same divstep iteration
+ * (fe_modinv.cuh) instead of the power p - 2 (opt-in, a mode of its own).  on: 0 or 1; the default is 0.  With the mode on, every launch queued afterwards of
+ *   pickles_scalar_kernel, kimchi_scalar_kernel      ft_eval0 of the step and the wrap side: 1 / ((zeta - w_zk)(zeta - 1)) and one per UNNORMALIZED_LAGRANGE token
+ *   kimchi_pub_kernel<8>, <10>                       the public polynomial's one Montgomery-trick inversion per lane pass
+ *   kimchi_ftcomm_kernel                             the ft commitment row of mina_kimchi_to_batch
+ *   pubcomm_finish16_kernel, pubcomm_finish_kernel   the public-input commitment h - A as an affine record (the job path; mina_public_input_commitment_batch)
+ *   lagrange_finish_kernel, lagrange_digit_table_kernel      mina_srs_lagrange_basis and the 128 digit multiples per window of mina_state_jobs_prepare
+ *   points_sum_kernel                                mina_points_sum_dev
+ * is the launch of its twin `..._gcd_kernel`: the same body, arguments and launch shape with fe_inv_gcd in place of fe_inv (kimchi_pub_gcd_kernel keeps its
+ * denominators in LDS, 40 KiB per workgroup at chunks of 10, where kimchi_pub_kernel<10> keeps them in scratch).  The inverse of a field element is unique: every
+ * output is the same bytes as with the mode off, and with the mode off every launch, kernel and byte is what it was before the mode existed.
+ * The two modes are independent: mina_ctx_set_fast_inverse is the MSM finish alone and does not imply this mode; this mode does not touch the MSM finish.
+ * Left on the power whatever the modes say: ipa_prepare_kernel (its latency form keeps its challenge arrays in scratch, which the code-object contract allows
+ * under that kernel's name only), the group map and the square roots, mina_field_inv, the group-law self-test hook, and every inversion the HOST computes (polish.h,
+ * the host half of the Pickles statement, the single mina_public_input_commitment, the constant set-up of the fields, sponges and indexes).
+ * The boundary (mina_verify_*) does not use the mode.
+ * Takes effect for the calls queued after it; a view context takes its parent's setting when it is created or refreshed.
+ * mina_ctx_chain_inverse_stats: launches of the kernels listed above this context has queued in the divstep form and in the power form since it was created. */
+int mina_ctx_set_chain_inverse(mina_ctx *ctx, int on);       /* default 0; takes effect for the calls queued after it */
+int mina_ctx_chain_inverse_stats(mina_ctx *ctx, uint64_t *gcd_launches, uint64_t *fermat_launches);
 /* Test-facing: *live = the streams the context's lanes hold now, *made_by_searches = the streams its culprit searches have created since the context was created
  * (the fan search creates the streams its lanes lack and destroys them when it is done; the grouped search creates none and queues on the job's lane only). */
 int mina_ctx_lane_streams(mina_ctx *ctx, uint32_t *live, uint64_t *made_by_searches);

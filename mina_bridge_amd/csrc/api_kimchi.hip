@@ -125,9 +125,25 @@ kimchi_fq_kernel(uint32_t batch, uint32_t n_prev, FieldK kb, FieldK ks, const Po
 // chunk of CH terms), round-robin over the lanes, each inverts its CH denominators with one field inversion; shuffle-tree sum.
 // CH = 10 makes the 40 public inputs of a wrap proof exactly 8 items -- one pass of the lanes; with chunks of 8 they are 10 items and the
 // wave runs a second pass (inversion included) for two of its eight lanes.
-template <int CH>
-__global__ void __launch_bounds__(64)
-kimchi_pub_kernel(uint32_t batch, uint32_t npub, FieldK ks, const KimchiIndexDev *__restrict__ ix, KimchiIn in, fe_t *__restrict__ xf, uint32_t *__restrict__ bad_input) { mb_wave_prio();
+// The chunk's denominators and prefix products: PubRegs keeps them where kimchi_pub_kernel always had them (local arrays; at CH = 10 the allocator puts them in
+// scratch), PubLds one column per lane in LDS, word-major like LdsStack (kimchi_pub_gcd_kernel: 2 CH x 8 words x 64 lanes, 40 KiB at CH = 10, nothing in scratch).
+template <int CH> struct PubRegs {
+    fe_t den[CH], pre[CH];
+    __device__ __forceinline__ void put_den(int j, const fe_t &a) { den[j] = a; }
+    __device__ __forceinline__ void put_pre(int j, const fe_t &a) { pre[j] = a; }
+    __device__ __forceinline__ fe_t get_den(int j) const { return den[j]; }
+    __device__ __forceinline__ fe_t get_pre(int j) const { return pre[j]; }
+};
+template <int CH> struct PubLds {
+    LdsStack st;
+    __device__ __forceinline__ void put_den(int j, const fe_t &a) { st.put(j, a); }
+    __device__ __forceinline__ void put_pre(int j, const fe_t &a) { st.put(CH + j, a); }
+    __device__ __forceinline__ fe_t get_den(int j) const { return st.get(j); }
+    __device__ __forceinline__ fe_t get_pre(int j) const { return st.get(CH + j); }
+};
+template <int CH, class Inv, class Cols>
+__device__ __forceinline__ void kimchi_pub_body(uint32_t batch, uint32_t npub, const FieldK &ks, const KimchiIndexDev *__restrict__ ix, const KimchiIn &in, fe_t *__restrict__ xf,
+                                                uint32_t *__restrict__ bad_input, Cols &cols) {
     constexpr int FS = FIELD_FQ;
     const uint32_t gid = blockIdx.x * 64 + threadIdx.x, b = gid >> 3, ln = gid & 7u;
     if (b >= batch) return;
@@ -143,15 +159,16 @@ kimchi_pub_kernel(uint32_t batch, uint32_t npub, FieldK ks, const KimchiIndexDev
         const uint32_t side = it & 1u, base = (it >> 1) * CH, cnt = npub - base < (uint32_t)CH ? npub - base : (uint32_t)CH;
         const fe_t pt = side ? zetaw : zeta;
         fe_t wi = fe_pow_u64<FS>(omega_ch, it >> 1, ks.one);
-        fe_t den[CH], pre[CH], run = ks.one;
+        fe_t run = ks.one;
 #pragma unroll
-        for (uint32_t j = 0; j < (uint32_t)CH; ++j) if (j < cnt) { den[j] = fe_sub<FS>(pt, wi); pre[j] = run; run = fe_mul<FS>(run, den[j]); wi = fe_mul<FS>(wi, ix->omega); }
-        fe_t inv = fe_inv<FS>(run, ks), part = fe_zero();
+        for (uint32_t j = 0; j < (uint32_t)CH; ++j) if (j < cnt) { const fe_t d = fe_sub<FS>(pt, wi); cols.put_den(j, d); cols.put_pre(j, run); run = fe_mul<FS>(run, d); wi = fe_mul<FS>(wi, ix->omega); }
+        fe_t inv = Inv::template inv<FS>(run, ks), part = fe_zero();
 #pragma unroll
         for (int j = CH - 1; j >= 0; --j) if ((uint32_t)j < cnt) {
-            const fe_t dinv = fe_mul<FS>(inv, pre[j]); inv = fe_mul<FS>(inv, den[j]);
+            const fe_t d = cols.get_den(j);
+            const fe_t dinv = fe_mul<FS>(inv, cols.get_pre(j)); inv = fe_mul<FS>(inv, d);
             const fe_t p = ld_checked<FS>(in.pub + ((size_t)b * npub + base + j) * 8, ks, ok);
-            part = fe_add<FS>(part, fe_mul<FS>(fe_mul<FS>(dinv, p), fe_sub<FS>(pt, den[j])));       // w^i = pt - (pt - w^i)
+            part = fe_add<FS>(part, fe_mul<FS>(fe_mul<FS>(dinv, p), fe_sub<FS>(pt, d)));            // w^i = pt - (pt - w^i)
         }
         if (side) acc[1] = fe_sub<FS>(acc[1], part); else acc[0] = fe_sub<FS>(acc[0], part);
     }
@@ -161,6 +178,19 @@ kimchi_pub_kernel(uint32_t batch, uint32_t npub, FieldK ks, const KimchiIndexDev
         x[XF_PUB0 + ln] = fe_mul<FS>(fe_mul<FS>(ln ? acc[1] : acc[0], fe_sub<FS>(ptn, ks.one)), ix->n_inv);
     }
     if (!ok) *bad_input = 1u;
+}
+template <int CH>
+__global__ void __launch_bounds__(64)
+kimchi_pub_kernel(uint32_t batch, uint32_t npub, FieldK ks, const KimchiIndexDev *__restrict__ ix, KimchiIn in, fe_t *__restrict__ xf, uint32_t *__restrict__ bad_input) { mb_wave_prio();
+    PubRegs<CH> cols;
+    kimchi_pub_body<CH, FeInvPow>(batch, npub, ks, ix, in, xf, bad_input, cols);
+}
+template <int CH>
+__global__ void __launch_bounds__(64)
+kimchi_pub_gcd_kernel(uint32_t batch, uint32_t npub, FieldK ks, const KimchiIndexDev *__restrict__ ix, KimchiIn in, fe_t *__restrict__ xf, uint32_t *__restrict__ bad_input) { mb_wave_prio();
+    __shared__ uint32_t lds[2 * CH * 8 * 64];
+    PubLds<CH> cols{LdsStack{lds + threadIdx.x}};
+    kimchi_pub_body<CH, FeInvGcd>(batch, npub, ks, ix, in, xf, bad_input, cols);
 }
 
 template <int LANES>
@@ -185,11 +215,11 @@ kimchi_fr_kernel(uint32_t batch, FieldK ks, const PoseidonParams *__restrict__ p
 }
 
 // one lane per proof; the interpreter's stack and cache live in LDS (kimchi_dev.cuh)
-__global__ void __launch_bounds__(64)
-kimchi_scalar_kernel(uint32_t batch, uint32_t n_prev, FieldK ks, const KimchiIndexDev *__restrict__ ix, const KimchiToken *__restrict__ toks,
-                     const fe_t *__restrict__ lits, KimchiIn in, KimchiOut out, fe_t *__restrict__ xf, uint32_t *__restrict__ bad_input) { mb_wave_prio();
+template <class Inv>
+__device__ __forceinline__ void kimchi_scalar_body(uint32_t batch, uint32_t n_prev, const FieldK &ks, const KimchiIndexDev *__restrict__ ix, const KimchiToken *__restrict__ toks,
+                                                   const fe_t *__restrict__ lits, const KimchiIn &in, const KimchiOut &out, fe_t *__restrict__ xf, uint32_t *__restrict__ bad_input,
+                                                   uint32_t *lds /* KC_SLOTS * 8 * 64 words */) {
     constexpr int FS = FIELD_FQ;
-    __shared__ uint32_t lds[KC_SLOTS * 8 * 64];
     const uint32_t b = blockIdx.x * 64 + threadIdx.x;
     if (b >= batch) return;
     LdsStack st{lds + threadIdx.x};
@@ -204,7 +234,7 @@ kimchi_scalar_kernel(uint32_t batch, uint32_t n_prev, FieldK ks, const KimchiInd
     fe_t perm_scalar;
     FtEnv env{x[XF_ALPHA], x[XF_BETA], x[XF_GAMMA], zeta, zeta1, ix->omega, ix->omega_zk, ix->endo_coeff, ix->zk_roots, ix->shifts, ix->mds, lits, toks,
               k, ix->zk_rows, ix->perm_alpha_offset, ix->n_tokens};
-    const fe_t ft = ft_eval0_dev<FS>(env, ks, x[XF_PUB0], EV, st, ok, perm_scalar);
+    const fe_t ft = ft_eval0_dev<FS, Inv>(env, ks, x[XF_PUB0], EV, st, ok, perm_scalar);
     const fe_t v = x[XF_V], u = x[XF_U];
     // combined inner product over the evaluation list: recursion, public, ft, then the 43 columns
     fe_t cip = fe_zero(), vi = ks.one;
@@ -235,12 +265,25 @@ kimchi_scalar_kernel(uint32_t batch, uint32_t n_prev, FieldK ks, const KimchiInd
     for (uint32_t j = 1; j < 8; ++j) { x[XF_FTSC + j] = sc; sc = fe_mul<FS>(sc, zeta1); }
     if (!ok) *bad_input = 1u;
 }
+__global__ void __launch_bounds__(64)
+kimchi_scalar_kernel(uint32_t batch, uint32_t n_prev, FieldK ks, const KimchiIndexDev *__restrict__ ix, const KimchiToken *__restrict__ toks,
+                     const fe_t *__restrict__ lits, KimchiIn in, KimchiOut out, fe_t *__restrict__ xf, uint32_t *__restrict__ bad_input) { mb_wave_prio();
+    __shared__ uint32_t lds[KC_SLOTS * 8 * 64];
+    kimchi_scalar_body<FeInvPow>(batch, n_prev, ks, ix, toks, lits, in, out, xf, bad_input, lds);
+}
+__global__ void __launch_bounds__(64)
+kimchi_scalar_gcd_kernel(uint32_t batch, uint32_t n_prev, FieldK ks, const KimchiIndexDev *__restrict__ ix, const KimchiToken *__restrict__ toks,
+                         const fe_t *__restrict__ lits, KimchiIn in, KimchiOut out, fe_t *__restrict__ xf, uint32_t *__restrict__ bad_input) { mb_wave_prio();
+    __shared__ uint32_t lds[KC_SLOTS * 8 * 64];
+    kimchi_scalar_body<FeInvGcd>(batch, n_prev, ks, ix, toks, lits, in, out, xf, bad_input, lds);
+}
 
 // 8 lanes per proof: term j on lane j, then a shuffle tree; lane 0 normalises and writes row n_prev + 1.  The t commitments were
 // checked by the fq stage (a malformed one already failed the batch).  Only the host-buffer form (`mina_kimchi_to_batch`, which
 // returns the rows) runs this: the verifier hands the 8 (point, scalar) pairs to the opening check's MSM instead (IpaExpand)
-__global__ void __launch_bounds__(64)
-kimchi_ftcomm_kernel(uint32_t batch, uint32_t n_prev, FieldK kb, const KimchiIndexDev *__restrict__ ix, KimchiIn in, KimchiOut out, const fe_t *__restrict__ xf) { mb_wave_prio();
+template <class Inv>
+__device__ __forceinline__ void kimchi_ftcomm_body(uint32_t batch, uint32_t n_prev, const FieldK &kb, const KimchiIndexDev *__restrict__ ix, const KimchiIn &in, const KimchiOut &out,
+                                                   const fe_t *__restrict__ xf) {
     constexpr int FB = FIELD_FP;
     const uint32_t gid = blockIdx.x * 64 + threadIdx.x, b = gid >> 3, j = gid & 7u;
     if (b >= batch) return;
@@ -252,11 +295,19 @@ kimchi_ftcomm_kernel(uint32_t batch, uint32_t n_prev, FieldK kb, const KimchiInd
         uint32_t *o = out.comms + ((size_t)b * (n_prev + 2 + KC_COLS) + n_prev + 1) * 16;
         if (xyzz_is_inf(part)) { for (int i = 0; i < 16; ++i) o[i] = 0; }
         else {
-            const fe_t zi = fe_inv<FB>(fe_mul<FB>(part.zz, part.zzz), kb);
+            const fe_t zi = Inv::template inv<FB>(fe_mul<FB>(part.zz, part.zzz), kb);
             const fe_t x = fe_from_mont<FB>(fe_mul<FB>(part.x, fe_mul<FB>(zi, part.zzz))), y = fe_from_mont<FB>(fe_mul<FB>(part.y, fe_mul<FB>(zi, part.zz)));
             for (int i = 0; i < 8; ++i) { o[i] = x.v[i]; o[8 + i] = y.v[i]; }
         }
     }
+}
+__global__ void __launch_bounds__(64)
+kimchi_ftcomm_kernel(uint32_t batch, uint32_t n_prev, FieldK kb, const KimchiIndexDev *__restrict__ ix, KimchiIn in, KimchiOut out, const fe_t *__restrict__ xf) { mb_wave_prio();
+    kimchi_ftcomm_body<FeInvPow>(batch, n_prev, kb, ix, in, out, xf);
+}
+__global__ void __launch_bounds__(64)
+kimchi_ftcomm_gcd_kernel(uint32_t batch, uint32_t n_prev, FieldK kb, const KimchiIndexDev *__restrict__ ix, KimchiIn in, KimchiOut out, const fe_t *__restrict__ xf) { mb_wave_prio();
+    kimchi_ftcomm_body<FeInvGcd>(batch, n_prev, kb, ix, in, out, xf);
 }
 
 // the rows of the commitment list that are copies: recursion accumulators, the public-input commitment, then the 43 columns
@@ -375,13 +426,20 @@ int mb_kimchi_to_batch_dev(mina_ctx *c, size_t batch, uint32_t n_prev, uint32_t 
     if ((rc = with_lanes<16, 8, 3>(transcript_lanes(c, batch, (size_t)mb_tune().kimchi_coop8_max), [&](auto lanes) {
             constexpr int LN = decltype(lanes)::value;
             mb::kimchi_fq_kernel<LN><<<fq_roles * coop_role_blocks<LN>(batch), 64, 0, L.stream>>>(B, n_prev, kb, ks, ppb, pps, ix, in, out, xf, d_bad, coop_role_blocks<LN>(batch), (const fe_t *)pf_digest, pf_stride);
-            if (npub > 32 && npub <= 40) mb::kimchi_pub_kernel<10><<<cdiv(batch * 8, 64), 64, 0, L.stream>>>(B, npub, ks, ix, in, xf, d_bad);
+            const bool ten = npub > 32 && npub <= 40;
+            if (c->gcd_launch()) {                              // mina_ctx_set_chain_inverse: the twin whose inversion is fe_modinv.cuh's
+                if (ten) mb::kimchi_pub_gcd_kernel<10><<<cdiv(batch * 8, 64), 64, 0, L.stream>>>(B, npub, ks, ix, in, xf, d_bad);
+                else mb::kimchi_pub_gcd_kernel<8><<<cdiv(batch * 8, 64), 64, 0, L.stream>>>(B, npub, ks, ix, in, xf, d_bad);
+            }
+            else if (ten) mb::kimchi_pub_kernel<10><<<cdiv(batch * 8, 64), 64, 0, L.stream>>>(B, npub, ks, ix, in, xf, d_bad);
             else mb::kimchi_pub_kernel<8><<<cdiv(batch * 8, 64), 64, 0, L.stream>>>(B, npub, ks, ix, in, xf, d_bad);
             mb::kimchi_fr_kernel<LN><<<cdiv(coop_threads<LN>(batch), 64), 64, 0, L.stream>>>(B, ks, pps, in, xf, d_bad);
             return MINA_OK;
         }))) return rc;
-    mb::kimchi_scalar_kernel<<<cdiv(batch, 64), 64, 0, L.stream>>>(B, n_prev, ks, ix, c->kimchi_tokens.as<mb::KimchiToken>(), c->kimchi_literals.as<fe_t>(), in, out, xf, d_bad);
+    if (c->gcd_launch()) mb::kimchi_scalar_gcd_kernel<<<cdiv(batch, 64), 64, 0, L.stream>>>(B, n_prev, ks, ix, c->kimchi_tokens.as<mb::KimchiToken>(), c->kimchi_literals.as<fe_t>(), in, out, xf, d_bad);
+    else mb::kimchi_scalar_kernel<<<cdiv(batch, 64), 64, 0, L.stream>>>(B, n_prev, ks, ix, c->kimchi_tokens.as<mb::KimchiToken>(), c->kimchi_literals.as<fe_t>(), in, out, xf, d_bad);
     if (expand) { expand->p0 = &ix->sigma6; expand->pts = in.t_comm; expand->sc = xf + mb::XF_FTSC; expand->stride = mb::KC_XF; }
+    else if (c->gcd_launch()) mb::kimchi_ftcomm_gcd_kernel<<<cdiv(batch * 8, 64), 64, 0, L.stream>>>(B, n_prev, kb, ix, in, out, xf);
     else mb::kimchi_ftcomm_kernel<<<cdiv(batch * 8, 64), 64, 0, L.stream>>>(B, n_prev, kb, ix, in, out, xf);
     HIPC(hipGetLastError());
     return MINA_OK;

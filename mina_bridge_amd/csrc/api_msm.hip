@@ -365,6 +365,20 @@ extern "C" int mina_ctx_inverse_stats(mina_ctx *c, uint64_t *gcd_finishes, uint6
     return MINA_OK;
 }
 
+// the chain inverse (ctx.h): which covered launch runs which form is decided where it is queued, by mina_ctx::gcd_launch()
+extern "C" int mina_ctx_set_chain_inverse(mina_ctx *c, int on) {
+    if (!c) return fail(MINA_ERR_ARG, "null argument");
+    if (on != 0 && on != 1) return fail(MINA_ERR_ARG, "chain inverse: 0 (off) or 1 (on)");
+    c->chain_inverse = on != 0;
+    return MINA_OK;
+}
+
+extern "C" int mina_ctx_chain_inverse_stats(mina_ctx *c, uint64_t *gcd_launches, uint64_t *fermat_launches) {
+    if (!c || !gcd_launches || !fermat_launches) return fail(MINA_ERR_ARG, "null argument");
+    *gcd_launches = c->chain_gcd_launches; *fermat_launches = c->chain_fermat_launches;
+    return MINA_OK;
+}
+
 extern "C" int mina_msm_segments_dev(mina_ctx *c, int curve, size_t n_total, size_t nseg, const void *d_seg_begin, const void *d_seg_end,
                                      const void *d_bases, const void *d_scalars, void *d_out) {
     if (!c || !d_seg_begin || !d_seg_end || !d_out || (n_total && (!d_bases || !d_scalars))) return fail(MINA_ERR_ARG, "null argument");

@@ -385,11 +385,12 @@ pickles_tick_kernel(uint32_t batch, FieldK kp, const PoseidonParams *__restrict_
     if (!ok) ok_out[b] = 0u;
 }
 
-__global__ void __launch_bounds__(64)
-pickles_scalar_kernel(uint32_t batch, FieldK kp, FieldK kq, const PicklesIndexDev *__restrict__ ix, const KimchiToken *__restrict__ toks, const fe_t *__restrict__ lits,
-                      PicklesIn in, const fe_t *__restrict__ xe, uint32_t *__restrict__ pub_out, uint32_t *__restrict__ ok_out) { mb_wave_prio();
+// Inv: ft_eval0's inversions by the power (pickles_scalar_kernel) or by divsteps (pickles_scalar_gcd_kernel; mina_ctx_set_chain_inverse)
+template <class Inv>
+__device__ __forceinline__ void pickles_scalar_body(uint32_t batch, const FieldK &kp, const FieldK &kq, const PicklesIndexDev *__restrict__ ix, const KimchiToken *__restrict__ toks,
+                                                    const fe_t *__restrict__ lits, const PicklesIn &in, const fe_t *__restrict__ xe, uint32_t *__restrict__ pub_out,
+                                                    uint32_t *__restrict__ ok_out, uint32_t *lds /* KC_SLOTS * 8 * 64 words */) {
     constexpr int F = FIELD_FP;
-    __shared__ uint32_t lds[KC_SLOTS * 8 * 64];
     const uint32_t b = blockIdx.x * 64 + threadIdx.x;
     if (b >= batch) return;
     LdsStack st{lds + threadIdx.x};
@@ -415,7 +416,7 @@ pickles_scalar_kernel(uint32_t batch, FieldK kp, FieldK kq, const PicklesIndexDe
               k, ix->zk_rows, 21u, ix->n_tokens};
     env.features = feature_mask_of_flags(misc + 2);
     if (misc[10]) { const uint32_t *jc = (const uint32_t *)(misc + 16); env.joint = challenge_to_field<F>((uint64_t)jc[0] | ((uint64_t)jc[1] << 32), (uint64_t)jc[2] | ((uint64_t)jc[3] << 32), kp); }
-    const fe_t ft = ft_eval0_dev<F>(env, kp, p0, EV, st, ok, perm);
+    const fe_t ft = ft_eval0_dev<F, Inv>(env, kp, p0, EV, st, ok, perm);
     const fe_t xi = x[PX_XI], r = x[PX_R];
     // combined inner product: Horner in xi over [b_poly(old_a, pt)..., public, ft, the evaluations], both points, second scaled by r
     fe_t cip;
@@ -471,6 +472,18 @@ pickles_scalar_kernel(uint32_t batch, FieldK kp, FieldK kq, const PicklesIndexDe
     if (misc[10]) put128(39, (const uint32_t *)(misc + 16)); else put_small(39, 0u);
     if (!ok) ok_out[b] = 0u;
 }
+__global__ void __launch_bounds__(64)
+pickles_scalar_kernel(uint32_t batch, FieldK kp, FieldK kq, const PicklesIndexDev *__restrict__ ix, const KimchiToken *__restrict__ toks, const fe_t *__restrict__ lits,
+                      PicklesIn in, const fe_t *__restrict__ xe, uint32_t *__restrict__ pub_out, uint32_t *__restrict__ ok_out) { mb_wave_prio();
+    __shared__ uint32_t lds[KC_SLOTS * 8 * 64];
+    pickles_scalar_body<FeInvPow>(batch, kp, kq, ix, toks, lits, in, xe, pub_out, ok_out, lds);
+}
+__global__ void __launch_bounds__(64)
+pickles_scalar_gcd_kernel(uint32_t batch, FieldK kp, FieldK kq, const PicklesIndexDev *__restrict__ ix, const KimchiToken *__restrict__ toks, const fe_t *__restrict__ lits,
+                          PicklesIn in, const fe_t *__restrict__ xe, uint32_t *__restrict__ pub_out, uint32_t *__restrict__ ok_out) { mb_wave_prio();
+    __shared__ uint32_t lds[KC_SLOTS * 8 * 64];
+    pickles_scalar_body<FeInvGcd>(batch, kp, kq, ix, toks, lits, in, xe, pub_out, ok_out, lds);
+}
 
 }  // namespace mb
 
@@ -510,7 +523,8 @@ int mb_pickles_dev(mina_ctx *c, size_t batch, const mb::PicklesIn &in, uint32_t 
             mb::pickles_tick_kernel<LN><<<cdiv(coop_threads<LN>(batch), 64), 64, 0, L.stream>>>(B, kp, ppp, in, xe, d_ok);
             return MINA_OK;
         }))) return rc;
-    mb::pickles_scalar_kernel<<<cdiv(batch, 64), 64, 0, L.stream>>>(B, kp, kq, ix, c->pickles_tokens.as<mb::KimchiToken>(), c->pickles_literals.as<fe_t>(), in, xe, d_pub, d_ok);
+    if (c->gcd_launch()) mb::pickles_scalar_gcd_kernel<<<cdiv(batch, 64), 64, 0, L.stream>>>(B, kp, kq, ix, c->pickles_tokens.as<mb::KimchiToken>(), c->pickles_literals.as<fe_t>(), in, xe, d_pub, d_ok);
+    else mb::pickles_scalar_kernel<<<cdiv(batch, 64), 64, 0, L.stream>>>(B, kp, kq, ix, c->pickles_tokens.as<mb::KimchiToken>(), c->pickles_literals.as<fe_t>(), in, xe, d_pub, d_ok);
     HIPC(hipGetLastError());
     return MINA_OK;
 }

@@ -18,8 +18,9 @@ __global__ void field_sum_rows_kernel(uint32_t rows, uint32_t m, FieldK fk, cons
 }
 
 // sum of n affine points given as 17-word records {x, y, is_infinity} -> one record
-template <int F>
-__global__ void points_sum_kernel(uint32_t n, FieldK kb, const uint32_t *__restrict__ recs, uint32_t *__restrict__ out) {
+// (Inv: the one inversion by the power, FeInvPow, or by divsteps, FeInvGcd -- points_sum_gcd_kernel under mina_ctx_set_chain_inverse; fe_modinv.cuh)
+template <int F, class Inv>
+__device__ __forceinline__ void points_sum_body(uint32_t n, const FieldK &kb, const uint32_t *__restrict__ recs, uint32_t *__restrict__ out) {
     if (threadIdx.x || blockIdx.x) return;
     xyzz_t acc = xyzz_inf();
     for (uint32_t i = 0; i < n; ++i) {
@@ -29,11 +30,15 @@ __global__ void points_sum_kernel(uint32_t n, FieldK kb, const uint32_t *__restr
         xyzz_add_affine<F>(acc, fe_to_mont<F>(x, kb.r2), fe_to_mont<F>(y, kb.r2), kb.one);
     }
     if (xyzz_is_inf(acc)) { for (int i = 0; i < 16; ++i) out[i] = 0; out[16] = 1; return; }
-    const fe_t zi = fe_inv<F>(fe_mul<F>(acc.zz, acc.zzz), kb);
+    const fe_t zi = Inv::template inv<F>(fe_mul<F>(acc.zz, acc.zzz), kb);
     const fe_t x = fe_from_mont<F>(fe_mul<F>(acc.x, fe_mul<F>(zi, acc.zzz))), y = fe_from_mont<F>(fe_mul<F>(acc.y, fe_mul<F>(zi, acc.zz)));
     for (int i = 0; i < 8; ++i) { out[i] = x.v[i]; out[8 + i] = y.v[i]; }
     out[16] = 0;
 }
+template <int F>
+__global__ void points_sum_kernel(uint32_t n, FieldK kb, const uint32_t *__restrict__ recs, uint32_t *__restrict__ out) { points_sum_body<F, FeInvPow>(n, kb, recs, out); }
+template <int F>
+__global__ void points_sum_gcd_kernel(uint32_t n, FieldK kb, const uint32_t *__restrict__ recs, uint32_t *__restrict__ out) { points_sum_body<F, FeInvGcd>(n, kb, recs, out); }
 
 __global__ void records_equal_kernel(const uint32_t *__restrict__ a, const uint32_t *__restrict__ b, uint32_t *__restrict__ verdict) {
     if (threadIdx.x || blockIdx.x) return;
@@ -71,7 +76,8 @@ extern "C" int mina_points_sum_dev(mina_ctx *c, int curve, size_t n, const void 
     if (n == 0 || n > 65536) return fail(MINA_ERR_ARG, "bad n");
     HIPC(hipSetDevice(c->device));
     c->next_lane();
-    DISPATCH_FIELD(base_field_of(curve), { mb::points_sum_kernel<F_><<<1, 64, 0, c->L->stream>>>((uint32_t)n, c->fk[F_], (const uint32_t *)d_records, (uint32_t *)d_out); });
+    if (c->gcd_launch()) { DISPATCH_FIELD(base_field_of(curve), { mb::points_sum_gcd_kernel<F_><<<1, 64, 0, c->L->stream>>>((uint32_t)n, c->fk[F_], (const uint32_t *)d_records, (uint32_t *)d_out); }); }
+    else { DISPATCH_FIELD(base_field_of(curve), { mb::points_sum_kernel<F_><<<1, 64, 0, c->L->stream>>>((uint32_t)n, c->fk[F_], (const uint32_t *)d_records, (uint32_t *)d_out); }); }
     HIPC(hipGetLastError());
     return MINA_OK;
 }

@@ -211,7 +211,8 @@ static int run_lagrange(mina_ctx *c, SrsState &s, uint32_t k, uint8_t *out_host)
     lagrange_load_bitrev_kernel<FB><<<cdiv(n, 256), 256, 0, st>>>(n, k, kb, s.table.as<affine_t>(), c->L->tmp_b.as<xyzz_t>());
     for (uint32_t h = 1; h < n; h <<= 1)
         lagrange_stage_kernel<FB><<<cdiv((size_t)half * 4, 256), 256, 0, st>>>(n, h, half / h, c->L->tmp_a.as<uint32_t>(), c->L->tmp_b.as<xyzz_t>());
-    lagrange_finish_kernel<FB><<<cdiv((size_t)n * 4, 256), 256, 0, st>>>(n, kb, c->L->tmp_a.as<uint32_t>() + (size_t)half * 8, c->L->tmp_b.as<xyzz_t>(), c->L->tmp_c.as<affine_t>());
+    if (c->gcd_launch()) lagrange_finish_gcd_kernel<FB><<<cdiv((size_t)n * 4, 256), 256, 0, st>>>(n, kb, c->L->tmp_a.as<uint32_t>() + (size_t)half * 8, c->L->tmp_b.as<xyzz_t>(), c->L->tmp_c.as<affine_t>());
+    else lagrange_finish_kernel<FB><<<cdiv((size_t)n * 4, 256), 256, 0, st>>>(n, kb, c->L->tmp_a.as<uint32_t>() + (size_t)half * 8, c->L->tmp_b.as<xyzz_t>(), c->L->tmp_c.as<affine_t>());
     points_from_mont_kernel<FB><<<cdiv(n, 256), 256, 0, st>>>(n, c->L->tmp_c.as<affine_t>(), c->L->tmp_d.as<uint32_t>());
     HIPC(hipGetLastError());
     return d2h_sync(c, out_host, c->L->tmp_d, (size_t)n * 64);
@@ -294,7 +295,8 @@ template <int F> static int build_lagrange_table(mina_ctx *c, SrsState &s, uint3
     const uint32_t n_dig = std::min<uint32_t>(n_tab, mb::LAGD_MAX_POINTS);
     s.lagrange_digits_n = 0;
     if ((rc = s.lagrange_digits.ensure((size_t)n_dig * mb::LAGD_WINDOWS * mb::LAGD_DIGITS * sizeof(affine_t)))) return rc;
-    mb::lagrange_digit_table_kernel<F><<<cdiv(n_dig * mb::LAGD_WINDOWS, 64), 64, 0, c->L->stream>>>(n_dig, n_tab, fk, s.lagrange_table.as<affine_t>(), s.lagrange_digits.as<affine_t>());
+    if (c->gcd_launch()) mb::lagrange_digit_table_gcd_kernel<F><<<cdiv(n_dig * mb::LAGD_WINDOWS, 64), 64, 0, c->L->stream>>>(n_dig, n_tab, fk, s.lagrange_table.as<affine_t>(), s.lagrange_digits.as<affine_t>());
+    else mb::lagrange_digit_table_kernel<F><<<cdiv(n_dig * mb::LAGD_WINDOWS, 64), 64, 0, c->L->stream>>>(n_dig, n_tab, fk, s.lagrange_table.as<affine_t>(), s.lagrange_digits.as<affine_t>());
     HIPC(hipGetLastError());
     {   // ... and the digit table its 2^261-domain twin (the direct commitments add on 29-bit limbs)
         const size_t npts = (size_t)n_dig * mb::LAGD_WINDOWS * mb::LAGD_DIGITS;
@@ -378,7 +380,8 @@ extern "C" int mina_public_input_commitment_batch(mina_ctx *c, int curve, uint32
     if ((rc = w.out_words.ensure(batch * 17 * 4))) return rc;
     if ((rc = h2d(c, w.scalars, public_inputs, batch * npub * 32))) return rc;
     if ((rc = mb_lagrange_sums_dev(c, curve, (uint32_t)npub, batch, w.scalars.as<uint32_t>(), c->L->tmp_b.p))) return rc;
-    DISPATCH_FIELD(FB, { pubcomm_finish_kernel<F_><<<cdiv(batch, 64), 64, 0, c->L->stream>>>((uint32_t)batch, c->fk[F_], s.h.as<affine_t>(), c->L->tmp_b.as<xyzz_t>(), w.out_words.as<uint32_t>()); });
+    if (c->gcd_launch()) { DISPATCH_FIELD(FB, { pubcomm_finish_gcd_kernel<F_><<<cdiv(batch, 64), 64, 0, c->L->stream>>>((uint32_t)batch, c->fk[F_], s.h.as<affine_t>(), c->L->tmp_b.as<xyzz_t>(), w.out_words.as<uint32_t>()); }); }
+    else { DISPATCH_FIELD(FB, { pubcomm_finish_kernel<F_><<<cdiv(batch, 64), 64, 0, c->L->stream>>>((uint32_t)batch, c->fk[F_], s.h.as<affine_t>(), c->L->tmp_b.as<xyzz_t>(), w.out_words.as<uint32_t>()); }); }
     HIPC(hipGetLastError());
     std::vector<uint32_t> hw(batch * 17);
     if ((rc = d2h_sync(c, hw.data(), w.out_words, hw.size() * 4))) return rc;

@@ -210,9 +210,9 @@ __global__ void pstate_chain_check_kernel(uint32_t batch, const uint32_t *__rest
 }
 
 // public-input commitment h - A as canonical affine words (16 per proof, zeros = infinity): feeds ipa_prepare_kernel's override slot
-template <int FB>
-__global__ void __launch_bounds__(64)
-pubcomm_finish16_kernel(uint32_t batch, FieldK kb, const affine_t *__restrict__ h, const xyzz_t *__restrict__ a, uint32_t *__restrict__ out_words) { mb_wave_prio();
+// (Inv: the inversion by the power, FeInvPow, or by divsteps, FeInvGcd -- pubcomm_finish16_gcd_kernel under mina_ctx_set_chain_inverse; fe_modinv.cuh)
+template <int FB, class Inv>
+__device__ __forceinline__ void pubcomm_finish16_body(uint32_t batch, const FieldK &kb, const affine_t *__restrict__ h, const xyzz_t *__restrict__ a, uint32_t *__restrict__ out_words) {
     const uint32_t m = blockIdx.x * blockDim.x + threadIdx.x;
     if (m >= batch) return;
     xyzz_t t = a[m];
@@ -221,9 +221,19 @@ pubcomm_finish16_kernel(uint32_t batch, FieldK kb, const affine_t *__restrict__ 
     xyzz_add_affine<FB>(t, H.x, H.y, kb.one);
     uint32_t *o = out_words + (size_t)m * 16;
     if (xyzz_is_inf(t)) { for (int i = 0; i < 16; ++i) o[i] = 0; return; }
-    const fe_t zi = fe_inv<FB>(fe_mul<FB>(t.zz, t.zzz), kb);
+    const fe_t zi = Inv::template inv<FB>(fe_mul<FB>(t.zz, t.zzz), kb);
     const fe_t x = fe_from_mont<FB>(fe_mul<FB>(t.x, fe_mul<FB>(zi, t.zzz))), y = fe_from_mont<FB>(fe_mul<FB>(t.y, fe_mul<FB>(zi, t.zz)));
     for (int i = 0; i < 8; ++i) { o[i] = x.v[i]; o[8 + i] = y.v[i]; }
+}
+template <int FB>
+__global__ void __launch_bounds__(64)
+pubcomm_finish16_kernel(uint32_t batch, FieldK kb, const affine_t *__restrict__ h, const xyzz_t *__restrict__ a, uint32_t *__restrict__ out_words) { mb_wave_prio();
+    pubcomm_finish16_body<FB, FeInvPow>(batch, kb, h, a, out_words);
+}
+template <int FB>
+__global__ void __launch_bounds__(64)
+pubcomm_finish16_gcd_kernel(uint32_t batch, FieldK kb, const affine_t *__restrict__ h, const xyzz_t *__restrict__ a, uint32_t *__restrict__ out_words) { mb_wave_prio();
+    pubcomm_finish16_body<FB, FeInvGcd>(batch, kb, h, a, out_words);
 }
 
 __global__ void fill_u32_kernel(uint32_t n, uint32_t v, uint32_t *__restrict__ out) { const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; if (i < n) out[i] = v; }
@@ -475,7 +485,8 @@ int mb_pubcomm_dev(mina_ctx *c, size_t batch, uint32_t log2_domain, uint32_t npu
         if (s.lagrange_table_log2 != (int)log2_domain || s.lagrange_table_n < npub) return fail(MINA_ERR_STATE, "call mina_state_jobs_prepare(log2_domain, npub) first");
         if ((rc = mb_lagrange_sums_dev(c, CURVE_PALLAS, npub, batch, d_pub, L.st_pub_xyzz.p))) return rc;
     }
-    mb::pubcomm_finish16_kernel<FIELD_FP><<<cdiv(batch, 64), 64, 0, L.stream>>>((uint32_t)batch, c->fk[FIELD_FP], s.h.as<affine_t>(), L.st_pub_xyzz.as<xyzz_t>(), d_out16);
+    if (c->gcd_launch()) mb::pubcomm_finish16_gcd_kernel<FIELD_FP><<<cdiv(batch, 64), 64, 0, L.stream>>>((uint32_t)batch, c->fk[FIELD_FP], s.h.as<affine_t>(), L.st_pub_xyzz.as<xyzz_t>(), d_out16);
+    else mb::pubcomm_finish16_kernel<FIELD_FP><<<cdiv(batch, 64), 64, 0, L.stream>>>((uint32_t)batch, c->fk[FIELD_FP], s.h.as<affine_t>(), L.st_pub_xyzz.as<xyzz_t>(), d_out16);
     HIPC(hipGetLastError());
     return MINA_OK;
 }

@@ -242,6 +242,12 @@ struct mina_ctx : Installed {
     // fe_modinv.cuh instead of the power p - 2; the same bytes.  mina_ctx_inverse_stats: MSM finishes queued with either form, counted by the context that queued them
     // (an MSM whose reduction kernel hands out the XYZZ result itself has no finish and counts as neither).
     bool fast_inverse = false; uint64_t inv_gcd_finishes = 0, inv_fermat_finishes = 0;
+    // The chain inverse (mina_ctx_set_chain_inverse): the single-lane inversions of the wrap-proof chain's scalar stages and of the Lagrange set-up -- ft_eval0 (both
+    // sides), the public polynomial, the ft commitment, the public-input commitment finishes, the Lagrange basis and its digit table, mina_points_sum_dev -- run the
+    // `_gcd` twin of their kernel (fe_modinv.cuh) instead of the power p - 2; the same bytes.  Independent of fast_inverse, which stays the MSM finish alone.
+    // mina_ctx_chain_inverse_stats: launches of those kernels by form, counted by the context that queued them (gcd_launch() below, once per launch).
+    bool chain_inverse = false; uint64_t chain_gcd_launches = 0, chain_fermat_launches = 0;
+    bool gcd_launch() { ++(chain_inverse ? chain_gcd_launches : chain_fermat_launches); return chain_inverse; }
     uint64_t search_streams_made = 0;  // streams any culprit search of this context has created (the fan search, for the lanes it lacks): mina_ctx_lane_streams
     // mina_state_job_batch without its upload: per-proof verdicts (host bytes) of a job whose inputs are in HBM, on lane 0, waited for (api_state.hip
     // mb_state_job_each_host).  Filled by mina_ctx_create; the boundary hands a failed chunk's device staging to it under MINA_VERIFY_GROUPED_SEARCH, and a context
@@ -255,7 +261,7 @@ struct mina_ctx : Installed {
     void use_lane0() { L = &lanes[0]; }
     void next_lane() { L = pinned >= 0 ? &lanes[pinned] : &lanes[rr++ % (unsigned)nlanes]; }
 };
-static inline void mb_ctx_refresh_view(mina_ctx *view, mina_ctx *parent) { view->borrow_from(*parent); view->msm_fused_tail = parent->msm_fused_tail; view->fast_inverse = parent->fast_inverse; }
+static inline void mb_ctx_refresh_view(mina_ctx *view, mina_ctx *parent) { view->borrow_from(*parent); view->msm_fused_tail = parent->msm_fused_tail; view->fast_inverse = parent->fast_inverse; view->chain_inverse = parent->chain_inverse; }
 
 // waits for everything the `_dev` entry points have queued: the pipeline lanes and, for jobs that ran under plan B, the role streams
 static inline hipError_t mb_ctx_wait_all(mina_ctx *c) {

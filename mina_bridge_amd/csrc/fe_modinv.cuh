@@ -4,7 +4,7 @@
 // inverse of a field element is unique, so the two routines agree on every byte (tests/test_modinv_host.py on the host, tests/test_gpu_fast_inverse.py on the
 // device); tests/modinv_model.py restates this file limb by limb on integers.  fe_inv walks 254 dependent squarings and ~65 products; this file walks at most 25
 // batches of 30 branch-free divsteps and two 2 x 2 matrix updates over nine limbs.  Opt-in callers only: mina_field_inv_gcd and, under mina_ctx_set_fast_inverse,
-// the MSM finishes (msm.cuh).
+// the MSM finishes (msm.cuh), and under mina_ctx_set_chain_inverse the `_gcd` twins of the chain's scalar stages and the Lagrange set-up (FeInvGcd, at the end).
 //
 // THE ITERATION.  delta = 1, f = p, g = a (the Montgomery words read as an integer), d = 0, e = 1; f stays odd.  One divstep:
 //     delta > 0 and g odd:   (delta, f, g) <- (1 - delta, g, (g - f) / 2)
@@ -193,5 +193,10 @@ template <int F> MB_HD fe_t fe_inv_gcd_r2(const fe_t &a, const fe_t &r2) {
     return fe_mul<F>(fe_mul<F>(x, r2), r2);
 }
 template <int F> MB_HD fe_t fe_inv_gcd(const fe_t &a, const FieldK &k) { return fe_inv_gcd_r2<F>(a, k.r2); }
+
+// A kernel body's inversion as a type, over the FieldK the kernel already has (mina_ctx_set_chain_inverse): `foo_kernel` is its body with FeInvPow, `foo_gcd_kernel`
+// the same body with FeInvGcd; the host picks one per launch.  A kernel holds ONE of the two routines.
+struct FeInvPow { template <int F> static MB_HD fe_t inv(const fe_t &a, const FieldK &k) { return fe_inv<F>(a, k); } };
+struct FeInvGcd { template <int F> static MB_HD fe_t inv(const fe_t &a, const FieldK &k) { return fe_inv_gcd<F>(a, k); } };
 
 }  // namespace mb

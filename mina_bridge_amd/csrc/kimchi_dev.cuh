@@ -52,7 +52,8 @@ struct FtEnv {
 };
 // returns ft_eval0; `perm_scalar` = -z(zeta w) beta a0 zkpm prod_{i<6}(gamma + beta s_i + w_i); ok = false on a broken program.
 // EV(col, row): the proof's evaluation of column `col` at zeta (row 0) / zeta*omega (row 1), Montgomery.
-template <int F, class EvFn>
+// Inv: both inversions -- the permutation term's and the Lagrange token's -- by the power (FeInvPow) or by divsteps (FeInvGcd; fe_modinv.cuh).
+template <int F, class Inv, class EvFn>
 __device__ fe_t ft_eval0_dev(const FtEnv &e, const FieldK &fk, const fe_t &pub0, EvFn EV, LdsStack st, bool &ok, fe_t &perm_scalar) {
     const fe_t zm1 = fe_sub<F>(e.zeta_n, fk.one);
     const fe_t a0 = fe_pow_u64<F>(e.alpha, e.alpha0, fk.one);
@@ -74,7 +75,7 @@ __device__ fe_t ft_eval0_dev(const FtEnv &e, const FieldK &fk, const fe_t &pub0,
         const fe_t a1 = fe_mul<F>(a0, e.alpha), a2 = fe_mul<F>(a1, e.alpha);
         const fe_t dw = fe_sub<F>(e.zeta, e.omega_zk), d1 = fe_sub<F>(e.zeta, fk.one);
         const fe_t num = fe_mul<F>(fe_add<F>(fe_mul<F>(fe_mul<F>(zm1, a1), dw), fe_mul<F>(fe_mul<F>(zm1, a2), d1)), fe_sub<F>(fk.one, z0));
-        ft = fe_add<F>(ft, fe_mul<F>(num, fe_inv<F>(fe_mul<F>(dw, d1), fk)));
+        ft = fe_add<F>(ft, fe_mul<F>(num, Inv::template inv<F>(fe_mul<F>(dw, d1), fk)));
     }
     if (e.n_tokens) {   // linearization constant term: PolishToken stack machine (the program is uniform over the lanes: no divergence)
         int sp = 0, nc = 0; bool prog_ok = true; uint32_t skip = 0;      // `skip` is per lane (the proofs' feature flags differ); the token loop itself stays uniform
@@ -105,7 +106,7 @@ __device__ fe_t ft_eval0_dev(const FtEnv &e, const FieldK &fk, const fe_t &pub0,
                     const int32_t off = (int32_t)tk.a;
                     const uint64_t row = off >= 0 ? (uint64_t)off : ((uint64_t)1 << e.k) - e.zk_rows - (off == INT32_MIN ? 0 : (uint64_t)(-(int64_t)off));   // INT32_MIN: the first zero-knowledge row itself
                     const fe_t wr = fe_pow_u64<F>(e.omega, row, fk.one);
-                    st.put(sp++, fe_mul<F>(zm1, fe_inv<F>(fe_sub<F>(e.zeta, wr), fk))); break; }
+                    st.put(sp++, fe_mul<F>(zm1, Inv::template inv<F>(fe_sub<F>(e.zeta, wr), fk))); break; }
                 case MINA_TOK_STORE: st.put(KC_STACK + nc++, st.get(sp - 1)); break;
                 case MINA_TOK_LOAD: if ((int)tk.a >= nc) prog_ok = false; st.put(sp++, st.get(KC_STACK + ((int)tk.a < nc ? (int)tk.a : 0))); break;   // a slot no executed STORE filled: this proof fails
                 default: prog_ok = false;

@@ -11,6 +11,7 @@
 // factor, done by ONE DPP quad with the lane-cooperative group law (double: 3 dependent products, add: 4).
 #pragma once
 #include "groupmap.cuh"
+#include "fe_modinv.cuh"
 #include "ec29.cuh"
 
 namespace mb {
@@ -70,9 +71,9 @@ lagrange_stage_kernel(uint32_t n, uint32_t half, uint32_t tw_stride, const uint3
 }
 
 // scale by 1/n and normalise to affine (Montgomery): one quad per point for the scalar multiplication, lane 0 inverts
-template <int FB>
-__global__ void __launch_bounds__(256)
-lagrange_finish_kernel(uint32_t n, FieldK kb, const uint32_t *__restrict__ n_inv_words, const xyzz_t *__restrict__ a, affine_t *__restrict__ out) {
+// (Inv, here and below: the inversion by the power, FeInvPow, or by divsteps, FeInvGcd -- the `_gcd` twins that mina_ctx_set_chain_inverse selects; fe_modinv.cuh)
+template <int FB, class Inv>
+__device__ __forceinline__ void lagrange_finish_body(uint32_t n, const FieldK &kb, const uint32_t *__restrict__ n_inv_words, const xyzz_t *__restrict__ a, affine_t *__restrict__ out) {
     const uint32_t gid = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t i = gid >> 2;
     if (i >= n) return;
@@ -80,18 +81,27 @@ lagrange_finish_kernel(uint32_t n, FieldK kb, const uint32_t *__restrict__ n_inv
     if ((gid & 3u) != 0) return;
     affine_t r; r.x = fe_zero(); r.y = fe_zero();
     if (!xyzz_is_inf(t)) {
-        fe_t zi = fe_inv<FB>(fe_mul<FB>(t.zz, t.zzz), kb);
+        fe_t zi = Inv::template inv<FB>(fe_mul<FB>(t.zz, t.zzz), kb);
         r.x = fe_mul<FB>(t.x, fe_mul<FB>(zi, t.zzz));
         r.y = fe_mul<FB>(t.y, fe_mul<FB>(zi, t.zz));
     }
     out[i] = r;
 }
+template <int FB>
+__global__ void __launch_bounds__(256)
+lagrange_finish_kernel(uint32_t n, FieldK kb, const uint32_t *__restrict__ n_inv_words, const xyzz_t *__restrict__ a, affine_t *__restrict__ out) {
+    lagrange_finish_body<FB, FeInvPow>(n, kb, n_inv_words, a, out);
+}
+template <int FB>
+__global__ void __launch_bounds__(256)
+lagrange_finish_gcd_kernel(uint32_t n, FieldK kb, const uint32_t *__restrict__ n_inv_words, const xyzz_t *__restrict__ a, affine_t *__restrict__ out) {
+    lagrange_finish_body<FB, FeInvGcd>(n, kb, n_inv_words, a, out);
+}
 
 // batched public-input commitments: out[m] = h - A[m], A[m] = sum_i pub[m][i] * lagrange_i from the table MSM.
 // One lane per problem; 17 canonical words each (x || y, infinity flag).
-template <int FB>
-__global__ void __launch_bounds__(64)
-pubcomm_finish_kernel(uint32_t batch, FieldK kb, const affine_t *__restrict__ h, const xyzz_t *__restrict__ a, uint32_t *__restrict__ out_words) { mb_wave_prio();
+template <int FB, class Inv>
+__device__ __forceinline__ void pubcomm_finish_body(uint32_t batch, const FieldK &kb, const affine_t *__restrict__ h, const xyzz_t *__restrict__ a, uint32_t *__restrict__ out_words) {
     const uint32_t m = blockIdx.x * blockDim.x + threadIdx.x;
     if (m >= batch) return;
     xyzz_t t = a[m];
@@ -100,10 +110,20 @@ pubcomm_finish_kernel(uint32_t batch, FieldK kb, const affine_t *__restrict__ h,
     xyzz_add_affine<FB>(t, H.x, H.y, kb.one);
     uint32_t *o = out_words + (size_t)m * 17;
     if (xyzz_is_inf(t)) { for (int i = 0; i < 16; ++i) o[i] = 0; o[16] = 1; return; }
-    const fe_t zi = fe_inv<FB>(fe_mul<FB>(t.zz, t.zzz), kb);
+    const fe_t zi = Inv::template inv<FB>(fe_mul<FB>(t.zz, t.zzz), kb);
     const fe_t x = fe_from_mont<FB>(fe_mul<FB>(t.x, fe_mul<FB>(zi, t.zzz))), y = fe_from_mont<FB>(fe_mul<FB>(t.y, fe_mul<FB>(zi, t.zz)));
     for (int i = 0; i < 8; ++i) { o[i] = x.v[i]; o[8 + i] = y.v[i]; }
     o[16] = 0;
+}
+template <int FB>
+__global__ void __launch_bounds__(64)
+pubcomm_finish_kernel(uint32_t batch, FieldK kb, const affine_t *__restrict__ h, const xyzz_t *__restrict__ a, uint32_t *__restrict__ out_words) { mb_wave_prio();
+    pubcomm_finish_body<FB, FeInvPow>(batch, kb, h, a, out_words);
+}
+template <int FB>
+__global__ void __launch_bounds__(64)
+pubcomm_finish_gcd_kernel(uint32_t batch, FieldK kb, const affine_t *__restrict__ h, const xyzz_t *__restrict__ a, uint32_t *__restrict__ out_words) { mb_wave_prio();
+    pubcomm_finish_body<FB, FeInvGcd>(batch, kb, h, a, out_words);
 }
 
 // ---------------------------------------------------------------- direct public-input commitments (the batch's per-proof 40-term MSMs)
@@ -114,8 +134,8 @@ pubcomm_finish_kernel(uint32_t batch, FieldK kb, const affine_t *__restrict__ h,
 // the scalars round-robin (5 each at npub = 40) and their partial sums are added by shuffles.  Same signed-digit rule as msm_entry.
 static constexpr uint32_t LAGD_MAX_POINTS = 64, LAGD_WINDOWS = 32, LAGD_DIGITS = 128;
 // digits[((i * 32 + w) * 128) + (d - 1)] = d * window[w * stride + i], Montgomery affine, (0, 0) = infinity; one thread per (i, w)
-template <int F>
-__global__ void lagrange_digit_table_kernel(uint32_t n_pts, uint32_t stride, FieldK fk, const affine_t *__restrict__ window, affine_t *__restrict__ digits) {
+template <int F, class Inv>
+__device__ __forceinline__ void lagrange_digit_table_body(uint32_t n_pts, uint32_t stride, const FieldK &fk, const affine_t *__restrict__ window, affine_t *__restrict__ digits) {
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     if (t >= n_pts * LAGD_WINDOWS) return;
     const uint32_t i = t / LAGD_WINDOWS, w = t % LAGD_WINDOWS;
@@ -128,12 +148,21 @@ __global__ void lagrange_digit_table_kernel(uint32_t n_pts, uint32_t stride, Fie
         if (!aff_is_inf(P)) {
             xyzz_add_affine<F>(acc, P.x, P.y, fk.one);           // (d + 1) P
             if (!xyzz_is_inf(acc)) {
-                const fe_t zi = fe_inv<F>(fe_mul<F>(acc.zz, acc.zzz), fk);
+                const fe_t zi = Inv::template inv<F>(fe_mul<F>(acc.zz, acc.zzz), fk);
                 o.x = fe_mul<F>(acc.x, fe_mul<F>(zi, acc.zzz)); o.y = fe_mul<F>(acc.y, fe_mul<F>(zi, acc.zz));
             }
         }
         out[d] = o;
     }
+}
+template <int F>
+__global__ void lagrange_digit_table_kernel(uint32_t n_pts, uint32_t stride, FieldK fk, const affine_t *__restrict__ window, affine_t *__restrict__ digits) {
+    lagrange_digit_table_body<F, FeInvPow>(n_pts, stride, fk, window, digits);
+}
+template <int F>
+__global__ void __launch_bounds__(64)      // its one launch has 64 lanes per workgroup; under the default bound of 1024 (128 VGPRs) the divstep form parks 2 VGPRs in scratch
+lagrange_digit_table_gcd_kernel(uint32_t n_pts, uint32_t stride, FieldK fk, const affine_t *__restrict__ window, affine_t *__restrict__ digits) {
+    lagrange_digit_table_body<F, FeInvGcd>(n_pts, stride, fk, window, digits);
 }
 // out[b] = sum_i pub[b][i] * L_i (XYZZ); pub = canonical 32-byte scalars below 2^255 (words); LPP lanes per proof: 8 for chip-filling
 // batches (5 scalars = 160 additions per lane at npub = 40), 64 for small ones (one scalar = 32 additions per lane, then a 6-level sum)

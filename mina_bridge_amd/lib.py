@@ -39,7 +39,7 @@ EXPORTS = [
     "mina_protocol_state_pack_dev", "mina_state_frontend_dev", "mina_account_frontend_dev", "mina_account_job_dev",
     "mina_state_jobs_prepare", "mina_state_job_batch_dev", "mina_state_job_batch", "mina_state_job_fold_dev",
     "mina_challenge_to_field_dev", "mina_field_sum_rows_dev", "mina_msm_srs_range_dev", "mina_msm_dev", "mina_points_sum_dev", "mina_point_records_equal_dev",
-    "mina_msm_segments_dev", "mina_b_poly_fold_segments_dev", "mina_state_job_each_dev", "mina_ctx_set_search_groups", "mina_ctx_search_stats", "mina_ctx_set_seg_fold_mfma_min", "mina_ctx_seg_fold_stats", "mina_ctx_set_msm_fused_tail", "mina_ctx_msm_tail_stats", "mina_ctx_set_fast_inverse", "mina_ctx_inverse_stats", "mina_ctx_lane_streams", "mina_ctx_set_stream_budget",
+    "mina_msm_segments_dev", "mina_b_poly_fold_segments_dev", "mina_state_job_each_dev", "mina_ctx_set_search_groups", "mina_ctx_search_stats", "mina_ctx_set_seg_fold_mfma_min", "mina_ctx_seg_fold_stats", "mina_ctx_set_msm_fused_tail", "mina_ctx_msm_tail_stats", "mina_ctx_set_fast_inverse", "mina_ctx_inverse_stats", "mina_ctx_set_chain_inverse", "mina_ctx_chain_inverse_stats", "mina_ctx_lane_streams", "mina_ctx_set_stream_budget",
     "mina_step_index_install", "mina_step_index_load_json", "mina_polish_tokens_from_json", "mina_verifier_index_load_json", "mina_pickles_public_input",
     "mina_verifier_index_install", "mina_verifier_index_digest", "mina_kimchi_to_batch", "mina_pickles_public_inputs_batch", "mina_wrap_proof_flatten", "mina_state_proof_split",
     "mina_verify_state", "mina_verify_state_batch", "mina_verify_state_checks", "mina_verify_state_files", "mina_verify_account", "mina_verify_account_batch",
@@ -1197,6 +1197,18 @@ class MinaContext:
         a, b = ctypes.c_uint64(0), ctypes.c_uint64(0)
         self._ck(self._lib.mina_ctx_inverse_stats(self._h, ctypes.byref(a), ctypes.byref(b)), "mina_ctx_inverse_stats")
         return {"gcd_finishes": a.value, "fermat_finishes": b.value}
+
+    def set_chain_inverse(self, on: bool):
+        """the scalar stages of the wrap-proof chain and the Lagrange set-up queued after the call (ft_eval0 on both sides, the public polynomial, the ft and
+        public-input commitment finishes, the Lagrange basis and its digit table, points_sum_dev) launch the `_gcd` twin of their kernel: the divstep inversion
+        of fe_modinv.cuh; off, the default: the power p - 2.  The same bytes either way; independent of set_fast_inverse"""
+        self._ck(self._lib.mina_ctx_set_chain_inverse(self._h, ctypes.c_int(1 if on else 0)), "mina_ctx_set_chain_inverse")
+
+    def chain_inverse_stats(self) -> dict:
+        """launches of the kernels set_chain_inverse covers that this context has queued in the divstep form / in the power form since it was created"""
+        a, b = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self._ck(self._lib.mina_ctx_chain_inverse_stats(self._h, ctypes.byref(a), ctypes.byref(b)), "mina_ctx_chain_inverse_stats")
+        return {"gcd_launches": a.value, "fermat_launches": b.value}
 
     def lane_streams(self) -> dict:
         """test-facing: streams the context's lanes hold now, and streams its culprit searches have created so far"""
