@@ -89,6 +89,16 @@ func (c *Ctx) SetStreamBudget(n int) error {
 	return nil
 }
 
+// StreamPlanStats: the plan the context's last pipelined device-resident job was queued under: shared role streams or not, its state-hash streams (1 or 2),
+// its chain pairs and the streams it keeps busy; all zero for a fork per lane and before the first such job.
+func (c *Ctx) StreamPlanStats() (roles bool, carriers, sets, streams uint32, err error) {
+	var r, a, b, d C.uint32_t
+	if rc := C.mina_ctx_stream_plan_stats(c.p, &r, &a, &b, &d); rc != 0 {
+		return false, 0, 0, 0, lastError()
+	}
+	return r != 0, uint32(a), uint32(b), uint32(d), nil
+}
+
 // SearchStats: legs searched in groups, their rounds and the parts checked, since the context was created.
 func (c *Ctx) SearchStats() (searches, rounds, parts uint64, err error) {
 	var a, b, d C.uint64_t

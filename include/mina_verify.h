@@ -661,9 +661,15 @@ int mina_ctx_lane_streams(mina_ctx *ctx, uint32_t *live, uint64_t *made_by_searc
  * default budget is that value (1 .. 32) less one, read when the first such job is queued.  With `lanes` jobs in flight: 4 * lanes <= budget, a lone job and a
  * pinned context fork each job's three legs onto streams of its lane (plan A); otherwise the jobs of all lanes flow FIFO through shared role streams -- one for
  * the state hashes, and s = clamp((budget - 1) / 2, 1, lanes) pairs for the two stages of the wrap-proof chain, the accumulator check and the verdict (plan B).
+ * A budget with room for one stream more than those 1 + 2 s (4, 6, ...; any budget above 1 + 2 * lanes) gives plan B a second state-hash stream: the jobs of the
+ * odd lanes hash on it in equal pieces, and the opening check of every other job follows its kimchi stage on the first chain stream.  Where no budget is
+ * forced and four lanes or more are in flight, plan B may take the null stream's queue for that second stream (4 queues: two hash streams and one pair).
  * Verdicts are the same under every plan; mina_ctx_synchronize waits for either.  n in 1 .. 31 forces a budget (tests, tools), n <= 0 goes back to the
  * environment's.  Waits for what the context has queued. */
 int mina_ctx_set_stream_budget(mina_ctx *ctx, int n);
+/* The plan the context's last pipelined device-resident job was queued under: *roles = 1 under plan B, *carriers = its state-hash streams (1 or 2), *sets = its
+ * chain pairs, *streams = the streams it keeps busy; all 0 under plan A and before the first such job. */
+int mina_ctx_stream_plan_stats(mina_ctx *ctx, uint32_t *roles, uint32_t *carriers, uint32_t *sets, uint32_t *streams);
 
 /* ---- multi-GPU building blocks --------------------------------------------------------------------
  * One process per GPU; RCCL moves bytes (all-to-all of scalar slices, all-gather of partial points), these entry points are the

@@ -126,6 +126,13 @@ extern "C" int mina_ctx_set_stream_budget(mina_ctx *c, int n) {
     c->stream_budget = n > 0 ? n : 0;
     return MINA_OK;
 }
+// The plan the context's last forked device-resident job was queued under (ctx.h StreamPlan; state_job.hip dev_fork_lanes): all zero under plan A and before the first job
+extern "C" int mina_ctx_stream_plan_stats(mina_ctx *c, uint32_t *roles, uint32_t *carriers, uint32_t *sets, uint32_t *streams) {
+    if (!c || !roles || !carriers || !sets || !streams) return fail(MINA_ERR_ARG, "null argument");
+    const StreamPlan &p = c->last_plan;
+    *roles = p.roles ? 1u : 0u; *carriers = (uint32_t)p.carriers; *sets = (uint32_t)p.sets; *streams = (uint32_t)p.busy();
+    return MINA_OK;
+}
 extern "C" void *mina_ctx_stream(mina_ctx *c) { return c ? (void *)c->lanes[c->pinned >= 0 ? c->pinned : 0].stream : nullptr; }
 // Pin the `_dev` entry points to ONE pipeline lane (lane < 0: back to round-robin).  While pinned, everything they queue is ordered on mina_ctx_stream(): a caller
 // that queues its own kernels, copies and collectives on that stream (torch: ExternalStream) is ordered against the library by the stream itself -- no

@@ -144,10 +144,24 @@ struct Lane {
 //     for the jobs of the lanes with lane % sets == j (W1: Pickles statement -> public-input commitment -> kimchi to_batch; W2: accumulator check, opening check,
 //     verdict kernel): 1 + 2 sets streams, sets = clamp((budget - 1) / 2, 1, lanes).  A budget below 3 cannot hold the three roles apart: W1 and W2 of the one
 //     set share a stream at 2, and H joins them at 1 (or less), so that the plan never keeps more than max(budget, 1) streams busy.
+//     A budget that holds one stream more than those 1 + 2 sets (4, 6, 8 ..., and every budget the lane count clamps the sets under) gives the hashes a SECOND
+//     carrier, H1: the jobs of the odd lanes hash on it, so that the hash launches of two consecutive jobs are resident together and the workgroups of the later
+//     one fill the wave slots the earlier one frees as it drains (a whole leg is 4.25 workgroups per CU: alone on the chip its last fifth runs on a quarter of the
+//     CUs; profiles/r10_hash_carriers.md).  Once H no longer sets the pace the chain streams do: each is ONE FIFO stream that serves every job of its set, and W2
+//     carries half as much again as W1 (per job beside resident hashes: W1 36 ms, W2 55 ms, 18 ms of it the opening check).  With two carriers the opening check of
+//     every other job of a set therefore follows its kimchi stage on W1 (check_on_w1; W2 keeps the accumulator check, the joins and the verdict kernel of every
+//     job): all of them on W1 made W1 the slow stream instead (measured; same note).  sets, streams, w1 and w2 are what they are without H1.
+static constexpr int MB_DEV_FORK_MAX = 8;                  // pipelines of up to this many lanes fork the legs of a device-resident job (mina_verify_tuning.dev_fork)
+static constexpr int MB_ROLE_STREAMS = 2 + 2 * MB_DEV_FORK_MAX;      // H + a W1 / W2 pair per lane at the most + H1 (StreamPlan)
+static constexpr int MB_ROLE_H1 = MB_ROLE_STREAMS - 1;     // the second carrier's place among the role streams: behind every pair, whatever the budget
 struct StreamPlan {
-    bool roles = false; int sets = 0, streams = 0;            // streams: the role streams of plan B (index 0 = H); 0 under plan A
+    bool roles = false; int sets = 0, streams = 0;            // streams: the role streams of plan B less H1 (index 0 = H); 0 under plan A
+    int carriers = 0;                                         // streams that carry state hashes under plan B: 1 (H) or 2 (H and H1); 0 under plan A
     int w1(int lane) const { return streams >= 3 ? 1 + 2 * (lane % sets) : streams - 1; }
     int w2(int lane) const { return streams >= 3 ? 2 + 2 * (lane % sets) : streams - 1; }
+    int h(int lane) const { return carriers >= 2 && (lane % carriers) ? MB_ROLE_H1 : 0; }       // consecutive lanes alternate
+    int busy() const { return streams + (carriers >= 2 ? 1 : 0); }                              // streams the plan keeps busy
+    bool check_on_w1(int lane) const { return carriers >= 2 && ((lane / sets) & 1) == 0; }     // every other lane of a set
 };
 static inline StreamPlan stream_plan(int lanes_in_flight, int budget) {
     StreamPlan p;
@@ -155,7 +169,34 @@ static inline StreamPlan stream_plan(int lanes_in_flight, int budget) {
     p.roles = true;
     p.sets = std::min(std::max((budget - 1) / 2, 1), lanes_in_flight);
     p.streams = std::min(1 + 2 * p.sets, std::max(budget, 1));
+    p.carriers = (p.streams >= 3 && budget > p.streams) ? 2 : 1;
     return p;
+}
+// The plan of a context that forces no budget, from the environment's (env_stream_budget: the queues less the one the caller's null stream runs on).  Plan A is
+// decided on that budget.  The role plan may take the last queue as well where that buys the second carrier: under plan B the library queues nothing on the
+// caller's stream or on the lanes' own, so the queue held back for the caller carries nothing while jobs flow, and the one role stream that ends up beside the
+// caller's stream loses nothing to it unless the caller queues work of its own there -- which then waits behind that stream's kernels, as it did behind W1's
+// before (the runtime dealt W1 the caller's queue and left the fourth empty: profiles/r08_role_streams.md, r10_hash_carriers.md).  Taken with four lanes or more
+// in flight only: that is where the two-carrier plan was timed against the plain one (4 lanes; more lanes queue behind the same four streams), and with 2 or 3
+// lanes, which nobody timed, a context that forces no budget keeps the plan it had.  mina_ctx_set_stream_budget(4) gives two carriers at any lane count.
+static constexpr int MB_ENV_H1_MIN_LANES = 4;
+static inline StreamPlan stream_plan_env(int lanes_in_flight, int env_budget) {
+    const StreamPlan p = stream_plan(lanes_in_flight, env_budget);
+    if (!p.roles || p.carriers >= 2 || lanes_in_flight < MB_ENV_H1_MIN_LANES) return p;
+    const StreamPlan q = stream_plan(lanes_in_flight, env_budget + 1);
+    return (q.roles && q.carriers >= 2 && q.sets == p.sets) ? q : p;
+}
+// The piece, in waves, of a state-hash leg of `leg_waves` waves under plan B with two carriers (0: one launch).  Two carriers hold the pieces of two jobs resident
+// together, so pieces pay again (on a lone H they only idle wave slots between launches): 4 lanes, the leg of 4352 single-lane waves, one box -- whole 286 k
+// proofs/s, 3072: 306 - 308 k, 1792 / 1664 / 1536 / 1451: 311 / 311 / 312 - 313 / 310 k, beside the parent's 292 - 297 k; but 2048, 1408, 1280 and 1024, which
+// leave a last piece of 256, 128, 512 and 256 waves: 298 / 284 / 285 / 293 k -- a thin piece holds its carrier for as long as a full one.  Hence EQUAL pieces,
+// as many as a target of 6144 / lanes waves asks for (half plan A's 12 288 / lanes: 1536 at 4 lanes), and half that in the 3-lane form, whose waves hold a third
+// of the states (by plan A's ratio; not measured).  profiles/r10_hash_carriers.md.  Pure.
+static inline uint32_t role_piece_waves(size_t leg_waves, int lanes_in_flight, bool one_lane) {
+    const size_t target = (one_lane ? 6144u : 3072u) / (size_t)std::max(lanes_in_flight, 1);
+    if (target == 0 || leg_waves <= target) return 0;
+    const size_t n = (leg_waves + target - 1) / target;
+    return (uint32_t)((leg_waves + n - 1) / n);
 }
 // GPU_MAX_HW_QUEUES as the process has it (the library's load-time constructor sets a default where it is unset: api_core.hip), 1 .. 32, less the caller's null stream
 static inline int env_stream_budget() {
@@ -164,8 +205,6 @@ static inline int env_stream_budget() {
     return (int)std::min(std::max(q, 1L), 32L) - 1;
 }
 static constexpr int MB_PIPE_LANES = 32;                   // lanes a caller may pipeline over (mina_ctx_set_pipeline) = the fan-out of the culprit search
-static constexpr int MB_DEV_FORK_MAX = 8;                  // pipelines of up to this many lanes fork the legs of a device-resident job (mina_verify_tuning.dev_fork)
-static constexpr int MB_ROLE_STREAMS = 1 + 2 * MB_DEV_FORK_MAX;      // H + a W1 / W2 pair per lane at the most (StreamPlan)
 static constexpr int MB_DEV_HELPER0 = MB_PIPE_LANES + 3 * 16;   // helper lanes of pipeline lane i: MB_DEV_HELPER0 + 3 i .. (wrap-proof chain / accumulator / state hashes)
 // The helper lanes of the forked device-resident jobs own NO stream: their `stream` is an alias of one of the context's fork streams (mina_ctx::fork_own, plan A)
 // or role streams (mina_ctx::role, plan B), which the context creates and destroys once.
@@ -258,6 +297,7 @@ struct mina_ctx : Installed {
     // lane, and plan B's role streams.  stream_budget: forced by mina_ctx_set_stream_budget (> 0), else the environment's, read when the first job forks (-1: not yet).
     hipStream_t fork_own[3 * MB_DEV_FORK_MAX] = {}; hipStream_t role[MB_ROLE_STREAMS] = {};
     int stream_budget = 0, stream_budget_env = -1;
+    StreamPlan last_plan;            // the plan the last forked device-resident job was queued under (mina_ctx_stream_plan_stats); all zero before the first
     void use_lane0() { L = &lanes[0]; }
     void next_lane() { L = pinned >= 0 ? &lanes[pinned] : &lanes[rr++ % (unsigned)nlanes]; }
 };
@@ -368,8 +408,9 @@ struct StateJobPlan {
     const struct LegStreams *lent = nullptr;                    // device-resident jobs only (state_job.hip dev_fork_lanes): the streams lent to wrap / acc / states for this job
 };
 // What dev_fork_lanes lends the helper lanes of a device-resident job, which own no stream: plan A's three of the pipeline lane, or plan B's roles (StreamPlan:
-// wrap = W1, acc = W2, states = H).  acc_first: the accumulator leg shares the hashes' lane and goes AHEAD of them (mina_verify_tuning.dev_acc_lane = 2).
-struct LegStreams { hipStream_t wrap = nullptr, acc = nullptr, states = nullptr; bool roles = false, acc_first = false; };
+// wrap = W1, acc = W2, states = the lane's carrier, H or H1).  acc_first: the accumulator leg shares the hashes' lane and goes AHEAD of them
+// (mina_verify_tuning.dev_acc_lane = 2).  check_on_wrap: under the role plan the opening check stays on W1 (StreamPlan::check_on_w1).
+struct LegStreams { hipStream_t wrap = nullptr, acc = nullptr, states = nullptr; bool roles = false, acc_first = false, check_on_wrap = false; };
 int mb_state_jobs_on_lane(mina_ctx *c, const mina_state_jobs *j, uint32_t *d_verdicts, uint32_t *d_flags, const StateJobPlan &plan = {});
 int mb_verify_account_on(mina_ctx *c, size_t n, const uint8_t *const *proofs, const size_t *proof_lens, const uint8_t *const *pubs, const size_t *pub_lens,
                          uint32_t *passed, uint32_t *ran, Lane *lane, std::mutex *enq_mu);   // api_account.hip: Proof-of-Account on a lane of the caller's choice

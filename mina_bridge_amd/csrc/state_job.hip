@@ -156,13 +156,17 @@ static int wrap_leg(mina_ctx *c, const mina_state_jobs *j, Lane &L, const FoldEx
 // behind the jobs queued before it -- H: the state hashes, the chain check; W2: the accumulator check; W1: the first stage of the wrap-proof leg, then ONE event
 // W1 -> W2 (wrap_leg); W2: the opening check, ONE event H -> W2, the verdict kernel, the lane's `done` event.  The helper lanes lend their workspaces (each job in
 // flight has its own); the NEXT job of `lane` reuses them, so it begins with H, W1 and W2 waiting for `done` (long completed, with two lanes or more).
+// With two hash carriers (ctx.h StreamPlan::carriers) "H" is the carrier of the job's lane, H or H1 -- a lane keeps its carrier for as long as the plan holds, so
+// `done` covers its workspaces as before -- and the opening check of every other lane stays on W1 behind kimchi (check_on_wrap): W2 then joins W1 behind the
+// check, by the event that otherwise stands in front of it.
 // Invariant (held by tests/test_state_job_trace.py): every wait names an event recorded EARLIER in host submission order -- each record stands above the waits on
 // it, `done` was recorded by the lane's previous job (Lane::on_roles guards the first) -- and every stream is fed in submission order: the graph cannot cycle.
 struct JobRoute {
     Lane *lane, *wrap, *acc, *states;
     bool roles = false, acc_ahead = false;      // roles: begins with waits for `done` and ends by recording it, instead of fork and join on `lane`; acc_ahead: LegStreams::acc_first
+    bool check_on_wrap = false;                 // roles with two hash carriers, every other lane (ctx.h StreamPlan::check_on_w1): the opening check follows kimchi on W1, and W2 joins W1 as it joins H
     hipStream_t home() const { return roles ? acc->stream : lane->stream; }       // gets the joins and the verdict kernel: the lane's own stream, or W2
-    hipStream_t check() const { return roles ? acc->stream : wrap->stream; }      // the opening check's: the wrap-proof leg's own stream, or W2
+    hipStream_t check() const { return roles && !check_on_wrap ? acc->stream : wrap->stream; }      // the opening check's: the wrap-proof leg's own stream, or W2
 };
 // plan.wrap / .acc: helper lanes of the wrap-proof and accumulator legs (null = everything on the current lane, in order); plan.states: a lane of its own for the
 // protocol-state leg as well (the boundary gives the chain and the hashes streams with disjoint CU masks, api_verify.hip)
@@ -174,7 +178,7 @@ static JobRoute resolve_route(mina_ctx *c, const StateJobPlan &plan) {
     if (plan.states && plan.states != L0 && plan.states != r.wrap) r.states = plan.states;      // states == acc: the accumulator leg shares the hashes' stream (behind them, or ahead)
     if (const LegStreams *lent = plan.lent) {      // the ONE place a helper lane is handed a stream: it holds for this job
         r.wrap->stream = lent->wrap; r.acc->stream = lent->acc; r.states->stream = lent->states;
-        r.roles = lent->roles; r.acc_ahead = lent->acc_first && r.acc == r.states;
+        r.roles = lent->roles; r.acc_ahead = lent->acc_first && r.acc == r.states; r.check_on_wrap = lent->roles && lent->check_on_wrap;
     }
     return r;
 }
@@ -255,7 +259,8 @@ static int dev_fork_lanes(mina_ctx *c, size_t leg_states, StateJobPlan &plan, Le
     const int in_flight = c->pinned >= 0 ? 1 : c->nlanes;          // a pinned context runs one job at a time
     Lane *h = &c->lanes[MB_DEV_HELPER0 + 3 * li];
     if (c->stream_budget_env < 0) c->stream_budget_env = env_stream_budget();
-    const StreamPlan sp = stream_plan(in_flight, c->stream_budget > 0 ? c->stream_budget : c->stream_budget_env);
+    const StreamPlan sp = c->stream_budget > 0 ? stream_plan(in_flight, c->stream_budget) : stream_plan_env(in_flight, c->stream_budget_env);
+    c->last_plan = sp;
     const uint32_t mode = c->dev_fork_made ? c->dev_fork_made : tu.dev_fork;
     c->dev_fork_made = mode;
     int prio_lo = 0, prio_hi = 0;
@@ -276,10 +281,11 @@ static int dev_fork_lanes(mina_ctx *c, size_t leg_states, StateJobPlan &plan, Le
     int rc;
     if (sp.roles) {
         // plan B: the role streams are the context's, created once (H at the hashes' priority, the chain streams at the chain's; no CU masks: a role serves every job)
-        if (!c->role[sp.streams - 1]) (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);      // numerically lower = higher priority
+        if (!c->role[sp.streams - 1] || (sp.carriers >= 2 && !c->role[MB_ROLE_H1])) (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);      // numerically lower = higher priority
         for (int i = 0; i < sp.streams; ++i) if ((rc = make(c->role[i], true, false, (i == 0 && sp.streams > 1) ? prio_lo : prio_hi))) return rc;
+        if (sp.carriers >= 2 && (rc = make(c->role[MB_ROLE_H1], true, false, prio_lo))) return rc;      // the second carrier: at the hashes' priority, as H
         plan.wrap = &h[0]; plan.acc = &h[1]; plan.states = &h[2];
-        lend.wrap = c->role[sp.w1(li)]; lend.acc = c->role[sp.w2(li)]; lend.states = c->role[0]; lend.roles = true;
+        lend.wrap = c->role[sp.w1(li)]; lend.acc = c->role[sp.w2(li)]; lend.states = c->role[sp.h(li)]; lend.roles = true; lend.check_on_wrap = sp.check_on_w1(li);
     } else {
         hipStream_t *own = &c->fork_own[3 * li];
         if (!own[0] || !own[1] || !own[2]) {
@@ -298,8 +304,10 @@ static int dev_fork_lanes(mina_ctx *c, size_t leg_states, StateJobPlan &plan, Le
     // Under the role plan H holds nothing but hashes, one launch behind the other: a piece only leaves wave slots idle until the next one starts, and the leg is
     // best left whole (4 lanes at budget 3, one run each: pieces of 3072 waves 265 k proofs/s, the whole leg of 4352 waves 283 k; profiles/r08_role_streams.md).
     // Under plan A one size above 3072 was tried as well: the whole leg, 315 k against 318 - 321 k -- the default stays.
+    // Two carriers hold the pieces of two jobs resident together: equal pieces again (ctx.h role_piece_waves).
     uint32_t piece = tu.dev_piece_waves;
     if (piece == 0 && in_flight >= 2 && !sp.roles) piece = (hash_one_lane(c, leg_states) ? 12288u : 6144u) / (uint32_t)in_flight;
+    if (piece == 0 && sp.carriers >= 2) { const bool one = hash_one_lane(c, leg_states); piece = role_piece_waves((leg_states + (one ? 63 : 20)) / (one ? 64 : 21), in_flight, one); }
     if (piece == 0xffffffffu) piece = 0;
     plan.hash.piece_waves = piece;
     // A lone forked job: its hashes would hold every wave slot their 96 VGPRs allow (5 per SIMD) and the chain's waves would wait for one to retire (~13 ms): the

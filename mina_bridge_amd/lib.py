@@ -39,7 +39,7 @@ EXPORTS = [
     "mina_protocol_state_pack_dev", "mina_state_frontend_dev", "mina_account_frontend_dev", "mina_account_job_dev",
     "mina_state_jobs_prepare", "mina_state_job_batch_dev", "mina_state_job_batch", "mina_state_job_fold_dev",
     "mina_challenge_to_field_dev", "mina_field_sum_rows_dev", "mina_msm_srs_range_dev", "mina_msm_dev", "mina_points_sum_dev", "mina_point_records_equal_dev",
-    "mina_msm_segments_dev", "mina_b_poly_fold_segments_dev", "mina_state_job_each_dev", "mina_ctx_set_search_groups", "mina_ctx_search_stats", "mina_ctx_set_seg_fold_mfma_min", "mina_ctx_seg_fold_stats", "mina_ctx_set_msm_fused_tail", "mina_ctx_msm_tail_stats", "mina_ctx_set_fast_inverse", "mina_ctx_inverse_stats", "mina_ctx_set_chain_inverse", "mina_ctx_chain_inverse_stats", "mina_ctx_lane_streams", "mina_ctx_set_stream_budget",
+    "mina_msm_segments_dev", "mina_b_poly_fold_segments_dev", "mina_state_job_each_dev", "mina_ctx_set_search_groups", "mina_ctx_search_stats", "mina_ctx_set_seg_fold_mfma_min", "mina_ctx_seg_fold_stats", "mina_ctx_set_msm_fused_tail", "mina_ctx_msm_tail_stats", "mina_ctx_set_fast_inverse", "mina_ctx_inverse_stats", "mina_ctx_set_chain_inverse", "mina_ctx_chain_inverse_stats", "mina_ctx_lane_streams", "mina_ctx_set_stream_budget", "mina_ctx_stream_plan_stats",
     "mina_step_index_install", "mina_step_index_load_json", "mina_polish_tokens_from_json", "mina_verifier_index_load_json", "mina_pickles_public_input",
     "mina_verifier_index_install", "mina_verifier_index_digest", "mina_kimchi_to_batch", "mina_pickles_public_inputs_batch", "mina_wrap_proof_flatten", "mina_state_proof_split",
     "mina_verify_state", "mina_verify_state_batch", "mina_verify_state_checks", "mina_verify_state_files", "mina_verify_account", "mina_verify_account_batch",
@@ -1219,6 +1219,13 @@ class MinaContext:
     def set_stream_budget(self, n: int):
         """streams the pipelined device-resident jobs may keep busy (1 .. 31: forces the stream plan; <= 0: GPU_MAX_HW_QUEUES less the null stream's); waits for what is queued"""
         self._ck(self._lib.mina_ctx_set_stream_budget(self._h, ctypes.c_int(n)), "mina_ctx_set_stream_budget")
+
+    def stream_plan_stats(self) -> dict:
+        """the plan the context's last pipelined device-resident job was queued under: roles (shared role streams), carriers (state-hash streams, 1 or 2), sets
+        (chain pairs), streams (kept busy); all zero for a fork per lane and before the first such job"""
+        r, a, b, d = (ctypes.c_uint32(0) for _ in range(4))
+        self._ck(self._lib.mina_ctx_stream_plan_stats(self._h, ctypes.byref(r), ctypes.byref(a), ctypes.byref(b), ctypes.byref(d)), "mina_ctx_stream_plan_stats")
+        return {"roles": bool(r.value), "carriers": a.value, "sets": b.value, "streams": d.value}
 
     def state_job_each_dev(self, jobs, d_verdicts: int, d_flags: int = 0):
         """per-proof verdicts (u32 each) of a job whose inputs are in HBM (`jobs` as for state_job_batch_dev); waits for its lane"""
