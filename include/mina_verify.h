@@ -586,6 +586,31 @@ int mina_state_job_batch(mina_ctx *ctx, const mina_state_jobs *jobs, uint8_t *ve
  * d_verdicts[b] = 1 / 0 (u32 per proof) and, if d_flags is not NULL, the four words mina_state_job_batch_dev writes for the WHOLE job.  SYNCHRONISES ITS LANE: when
  * it returns the verdicts are in d_verdicts.  Call mina_state_jobs_prepare first. */
 int mina_state_job_each_dev(mina_ctx *ctx, const mina_state_jobs *jobs, void *d_verdicts /* batch u32 */, void *d_flags /* 4 u32 or NULL */);
+/* The masks form of the job: which checks ran and which passed (bit masks of MINA_CHECK_*, below) for EVERY proof of a batch, from ONE pass of the job -- what
+ * mina_verify_account_ctx / mina_account_job_dev answer for the account side.  `jobs` as for mina_state_job_batch_dev (device pointers); jobs->precheck is NOT read:
+ * the host checks have their own bits in d_front.  Per proof b the inputs are front = d_front[b] (the MINA_CHECK_FORMAT | _LEDGER | _CONSENSUS bits that passed, as
+ * mina_state_frontend_dev writes d_masks; d_front may be NULL: absent), deny = d_deny[b] (MINA_CHECK_* bits the caller has already decided fail; NULL: 0), the job's
+ * section flags, chain (all 17 hashes equal the expected ones and states 1..15 name their predecessor), stmt (the Pickles statement is well-formed) and ipa_each /
+ * acc_each (the proof is not a culprit of the opening leg / of the accumulator leg).  The rule (csrc/state_masks.h, one host/device function):
+ *   ran = FORMAT.
+ *   If `front` is present and lacks FORMAT, or `deny` has FORMAT: passed = 0, nothing else is in `ran`, and the proof is done.
+ *   Otherwise passed = FORMAT.
+ *   With `front` present: ran |= LEDGER | CONSENSUS and passed |= front & (LEDGER | CONSENSUS).  Without it, neither bit runs.
+ *   with_states: ran |= CHAIN; passed iff `chain`.
+ *   with_accumulator: ran |= ACCUMULATOR; passed iff `acc_each`.
+ *   with_ipa: ran |= KIMCHI; passed iff `stmt && ipa_each`.
+ *   Finally passed &= ~deny.  `ran` is not touched by `deny`.
+ * The job runs once with every requested leg, on the next pipeline lane (the pinned one under mina_ctx_pin_lane); a kernel then keeps the chain word of every proof
+ * apart from the folded verdicts.  Both folded checks good: the only host read is the four flag words.  A folded check failed: that leg is searched for its culprits
+ * as mina_state_job_each_dev searches it (in groups or over the fan, counted by mina_ctx_search_stats) -- and no state is hashed a second time.  Writes d_passed[b] /
+ * d_ran[b] and, if d_flags is not NULL, the four words mina_state_job_each_dev writes.  MINA_ERR_ARG for a null d_passed / d_ran or a pointer that is not 4-byte
+ * aligned, before any launch.  SYNCHRONISES ITS LANE.  Call mina_state_jobs_prepare first.
+ * mina_state_job_checks: the host-buffer form (every pointer a host pointer; uploads as mina_state_job_batch does, lane 0).
+ * mina_ctx_checks_stats: the full job passes the checks calls of the context have queued (one per call, whatever fails) and the proofs in them. */
+int mina_state_job_checks_dev(mina_ctx *ctx, const mina_state_jobs *jobs, const void *d_front /* batch u32 or NULL */, const void *d_deny /* batch u32 or NULL */,
+                              void *d_passed /* batch u32 */, void *d_ran /* batch u32 */, void *d_flags /* 4 u32 or NULL */);
+int mina_state_job_checks(mina_ctx *ctx, const mina_state_jobs *jobs, const uint32_t *front, const uint32_t *deny, uint32_t *passed, uint32_t *ran);
+int mina_ctx_checks_stats(mina_ctx *ctx, uint64_t *jobs, uint64_t *proofs);
 /* The grouped culprit search (off by default).  groups = 0: the fan search above.  groups = G in 2 .. 128: each failed leg starts with failing = {[0, batch)};
  * every round cuts every failing range [lo, lo + cnt) of more than one proof into g = min(G, cnt) parts [lo + cnt*q/g, lo + cnt*(q+1)/g), checks ALL parts of the
  * round in one pass on the job's own lane (mina_b_poly_fold_segments_dev's fold, the fixed-base MSM with one problem per part, mina_msm_segments_dev's MSM, one
@@ -904,6 +929,13 @@ int mina_verify_state_batch(size_t n, const uint8_t *const *proofs, const size_t
                             const size_t *pub_lens, uint8_t *verdicts_out /* n bytes 0/1 */);
 /* which steps ran and which passed (bit masks of MINA_CHECK_*) */
 int mina_verify_state_checks(const uint8_t *proof, size_t proof_len, const uint8_t *pub_input, size_t pub_len, uint32_t *passed_mask, uint32_t *ran_mask);
+/* The same masks for n pairs at once: (passed_masks[i], ran_masks[i]) is what mina_verify_state_checks answers for pair i under the same configuration, for every
+ * input, malformed ones included.  The pairs are grouped by evaluation shape; each group is parsed by the host pool (the protocol states on the GPU under
+ * MINA_VERIFY_PACK_ON_DEVICE) and runs, in chunks of at most mina_verify_tuning.chunk proofs, as ONE job with all three legs through mina_state_job_checks_dev's
+ * body, where the single-proof form runs three jobs per proof.  On device 0, under its lock: a checks call is not merged with other callers and not sharded over
+ * several GPUs.  n = 0 is MINA_OK; a call in which no pair parses is answered without a job.  Counted by mina_ctx_checks_stats of mina_verify_device_ctx(0). */
+int mina_verify_state_checks_batch(size_t n, const uint8_t *const *proofs, const size_t *proof_lens, const uint8_t *const *pub_inputs, const size_t *pub_lens,
+                                   uint32_t *passed_masks /* n */, uint32_t *ran_masks /* n */);
 /* the `--save-proof` files of the reference CLI (core/src/aligned.rs:60-69): mina_state.proof / mina_state.pub */
 bool mina_verify_state_files(const char *proof_path, const char *pub_path);
 bool mina_verify_account(const uint8_t *proof, size_t proof_len, const uint8_t *pub_input, size_t pub_len);

@@ -13,7 +13,7 @@ LIB = os.path.join(HERE, "libminaverify.so")
 OBJ_DIR = os.path.join(HERE, "build")
 
 SOURCES = ["host_core.hip", "api_core.hip", "api_selftest.hip", "api_msm.hip", "api_srs.hip", "api_sponge.hip", "api_ipa.hip", "api_wire.hip", "api_consensus.hip", "api_state.hip", "state_job.hip", "api_pack.hip", "api_kimchi.hip", "api_verify.hip", "api_account.hip", "api_account_dev.hip", "api_shard.hip", "api_pickles.hip", "api_loaders.hip"]
-HEADERS = ["fp.cuh", "fp29.cuh", "ec.cuh", "ec29.cuh", "msm.cuh", "msm_seg.cuh", "bpoly_seg.cuh", "segments.cuh", "groupmap.cuh", "fe_modinv.cuh", "sponge.cuh", "state_dedup.cuh", "state_pack.cuh", "pack_common.cuh", "account_pack.cuh", "consensus.cuh", "lagrange.cuh", "ctx.h", "wire_state.h", "wire_proof.h", "wire_account.h", "polish.h", "loaders_text.h", "wire_pub.h", "kimchi_dev.cuh", "bpoly_mfma.cuh", "bpoly_mfma_seg.cuh", "poseidon_tables.inc"]
+HEADERS = ["fp.cuh", "fp29.cuh", "ec.cuh", "ec29.cuh", "msm.cuh", "msm_seg.cuh", "bpoly_seg.cuh", "segments.cuh", "groupmap.cuh", "fe_modinv.cuh", "sponge.cuh", "state_dedup.cuh", "state_pack.cuh", "state_masks.h", "pack_common.cuh", "account_pack.cuh", "consensus.cuh", "lagrange.cuh", "ctx.h", "wire_state.h", "wire_proof.h", "wire_account.h", "polish.h", "loaders_text.h", "wire_pub.h", "kimchi_dev.cuh", "bpoly_mfma.cuh", "bpoly_mfma_seg.cuh", "poseidon_tables.inc"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wno-unused-result"] + os.environ.get("MINA_BUILD_EXTRA_FLAGS", "").split()   # experiments: -DMB_CHAIN_PRIO=0
 
 

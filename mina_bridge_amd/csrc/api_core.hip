@@ -68,6 +68,7 @@ extern "C" int mina_ctx_create(int device_id, mina_ctx **out) {
     c->state_frontend = mb_state_frontend_on_lane;
     c->account_on_device = mb_verify_account_dev_on;
     c->state_job_each = mb_state_job_each_host;
+    c->state_job_checks = mb_state_job_checks_host;
     *out = c;
     return MINA_OK;
 }

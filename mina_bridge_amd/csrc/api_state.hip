@@ -16,6 +16,7 @@
 #include "lagrange.cuh"
 #include "wire_state.h"
 #include "state_dedup.cuh"
+#include "state_masks.h"
 
 namespace mb {
 
@@ -248,6 +249,37 @@ __global__ void state_job_verdict_kernel(uint32_t batch, const uint32_t *__restr
     const uint32_t iv = (ipa_v ? ipa_v[0] : 1u) && !kb, av = acc_v ? acc_v[0] : 1u;
     if (b == 0 && flags) { flags[0] = iv; flags[1] = (ipa_v ? ipa_v[1] : 0u) | kb; flags[2] = av; flags[3] = 0u; }
     if (b < batch) { const uint32_t so = stmt_ok ? stmt_ok[b] : 1u; verdicts[b] = (chain_ok[b] && iv && av && so) ? 1u : 0u; if (stmt_out) stmt_out[b] = so; }
+}
+
+// ---- the masks form of the job (state_job_checks below; the rule: state_masks.h).  Both kernels: one lane per proof, pure comparisons and bit operations.
+// pstate_chain_check_kernel's comparisons with their own word per proof: chain[b] = the 17 hashes equal the expected ones and states 1..15 name their predecessor.
+// `precheck` is not read: the host checks have their own bits in the masks.
+__global__ void __launch_bounds__(64)
+pstate_chain_detail_kernel(uint32_t batch, const uint32_t *__restrict__ hashes /* b*17*8 */, const uint32_t *__restrict__ expected /* b*17*8 */,
+                           const uint32_t *__restrict__ records, uint32_t *__restrict__ chain) { mb_wave_prio();
+    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= batch) return;
+    bool good = true;
+    const uint32_t *h = hashes + (size_t)b * MINA_STATES_PER_PROOF * 8, *x = expected + (size_t)b * MINA_STATES_PER_PROOF * 8;
+    for (uint32_t i = 0; i < MINA_STATES_PER_PROOF * 8; ++i) good = good && (h[i] == x[i]);
+    for (uint32_t s = 1; s < MINA_STATES_PER_PROOF - 1; ++s) {          // candidate chain: states 0..15 (oldest .. tip); 16 = bridge tip (not linked)
+        const uint32_t *prev = records + ((size_t)b * MINA_STATES_PER_PROOF + s) * MINA_PSTATE_SLOTS * 8;   // slot 0 = previous_state_hash
+        for (int i = 0; i < 8; ++i) good = good && (prev[i] == h[(s - 1) * 8 + i]);
+    }
+    chain[b] = good ? 1u : 0u;
+}
+
+// passed[b] / ran[b] = state_masks_of(what the job left in HBM about proof b).  sections: bit 0 with_states, bit 1 with_accumulator, bit 2 with_ipa.  front / deny /
+// chain may be null (absent / 0 / no state leg); ipa_each / acc_each null = nobody is a culprit (both folded checks passed).
+__global__ void __launch_bounds__(64)
+state_job_masks_kernel(uint32_t batch, uint32_t sections, const uint32_t *__restrict__ front, const uint32_t *__restrict__ deny, const uint32_t *__restrict__ chain,
+                       const uint32_t *__restrict__ stmt, const uint32_t *__restrict__ ipa_each, const uint32_t *__restrict__ acc_each, uint32_t *__restrict__ passed,
+                       uint32_t *__restrict__ ran) { mb_wave_prio();
+    const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= batch) return;
+    const StateMasks m = state_masks_of(front != nullptr, front ? front[b] : 0u, deny ? deny[b] : 0u, (sections & 1u) != 0, (sections & 2u) != 0, (sections & 4u) != 0,
+                                        chain ? chain[b] != 0 : true, stmt[b] != 0, ipa_each ? ipa_each[b] != 0 : true, acc_each ? acc_each[b] != 0 : true);
+    passed[b] = m.passed; ran[b] = m.ran;
 }
 
 }  // namespace mb
@@ -515,39 +547,18 @@ void mb_launch_challenge_to_field_fq(hipStream_t stream, uint32_t n, FieldK fk, 
 
 namespace {
 struct Section { const void **slot; size_t bytes; };
-}
-// The body mina_state_job_batch (after its upload) and mina_state_job_each_dev share: the job on lane L from inputs in HBM (every pointer of `d` a device pointer),
-// one verdict byte per proof on the host.  When a folded check fails: a run without the folded legs for the per-proof chain verdicts, then the search for the
-// culprits of each failed leg -- in groups on lane L alone (mina_ctx_set_search_groups) or over the fan's lanes.  Waits for lane L.  flags: the four words of the
-// whole job's folded checks ([0] opening verdict, [1] malformed opening input, [2] accumulator verdict), or null.
-static int state_job_each(mina_ctx *c, Lane &L, const mina_state_jobs &d, uint8_t *verdicts, uint32_t *flags) {
-    c->L = &L;
+// The culprit searches of a job on lane L whose folded checks failed (every pointer of `d` a device pointer): what state_job_each and state_job_checks share.
+// malformed: word [1] of the failed job's flags (a malformed opening input: the rows it left cannot be re-checked).
+struct CulpritSearch {
+    mina_ctx *const c; Lane &L; const mina_state_jobs &d; const bool rows_ok;
     const size_t B = d.batch, k = d.k, m = d.n_comms, np = d.n_evalpoints;
-    int rc;
-    if ((rc = L.st_verdicts.ensure(2 * B * 4 + 16))) return rc;
-    uint32_t *dv = L.st_verdicts.as<uint32_t>(), *df = dv + B, *ds = df + 4;
-    // small, latency-bound batches: the three independent legs go to three lanes (lane 0 plus two helpers), joined by events
-    StateJobPlan plan; plan.d_stmt_out = ds;
-    if (B <= 1024 && c->nlanes == 1 && &L == &c->lanes[0]) { plan.wrap = &c->lanes[1]; plan.acc = &c->lanes[2]; }
-    if ((rc = mb_state_jobs_on_lane(c, &d, dv, df, plan))) return rc;
-    std::vector<uint32_t> hv(2 * B + 4);
-    if ((rc = d2h_sync(c, hv.data(), L.st_verdicts, (2 * B + 4) * 4))) return rc;
-    if (flags) memcpy(flags, &hv[B], 16);
-    std::vector<uint8_t> stmt_each(B); for (size_t b = 0; b < B; ++b) stmt_each[b] = hv[B + 4 + b] ? 1 : 0;
-    const bool ipa_ok = hv[B] != 0, acc_ok = hv[B + 2] != 0;
-    if (ipa_ok && acc_ok) { for (size_t b = 0; b < B; ++b) verdicts[b] = hv[b] ? 1 : 0; return MINA_OK; }
-    // a folded check failed somewhere: find the culprits.  chain_ok per proof comes from a run without the folded legs.
-    std::vector<uint8_t> ipa_each(B, 1), acc_each(B, 1), chain_each(B, 1);
-    {
-        mina_state_jobs only = d; only.with_ipa = 0; only.with_accumulator = 0; only.npub = 0; only.kimchi = nullptr;
-        if (only.with_states) {
-            if ((rc = mb_state_jobs_on_lane(c, &only, dv, df))) return rc;
-            if ((rc = d2h_sync(c, hv.data(), L.st_verdicts, B * 4))) return rc;
-            for (size_t b = 0; b < B; ++b) chain_each[b] = hv[b] ? 1 : 0;
-        }
-    }
     mina_kimchi_proofs kslice{}; mina_pickles_statements sslice{};
-    auto slice = [&](const mina_state_jobs &src, size_t lo, size_t cnt) {
+    // The opening leg of well-formed proofs does not repeat its transcripts: the prepared rows of the failed batch are still on their
+    // lane and any slice of them is the folded check of that slice (mb_ipa_recheck_rows): a round costs a fold + two MSMs per part.
+    CulpritSearch(mina_ctx *c_, Lane &L_, const mina_state_jobs &d_, bool malformed)
+        : c(c_), L(L_), d(d_), rows_ok(!malformed && c_->ipa_rows && c_->ipa_rows_batch == d_.batch && !mb_tune().search_full) {}
+    // proofs [lo, lo + cnt) of `src` as a job of their own, without the protocol-state leg
+    mina_state_jobs slice(const mina_state_jobs &src, size_t lo, size_t cnt) {
         mina_state_jobs s = src; s.batch = cnt; s.with_states = 0; s.precheck = nullptr;
         auto adv = [&](const void *&p, size_t stride) { if (p) p = (const uint8_t *)p + lo * stride; };
         if (s.kimchi) {
@@ -566,17 +577,14 @@ static int state_job_each(mina_ctx *c, Lane &L, const mina_state_jobs &d, uint8_
         adv(s.evalpoints, np * 32); adv(s.evalscale, 32); adv(s.polyscale, 32); adv(s.comms, m * 64);
         adv(s.acc_prechallenges, (size_t)s.acc_k * 16); adv(s.acc_sg, 64); adv(s.acc_rho, 32);
         return s;
-    };
+    }
     // the culprits of one folded leg: a failing range is cut into FAN parts whose jobs run CONCURRENTLY on lanes 0..FAN-1 of the context
     // (inputs stay where lane 0 uploaded them; every lane has its own verdict words); parts that fail are cut again: depth log_FAN(B) rounds
     // of ~one job latency each, where a bisection ran log2(B) jobs one after the other per culprit.  FAN = 4 (mina_verify_tuning.search_fan): with 32 -- the
     // fan-out until the end of round 3 -- a search over 8192 proofs took 370 ms instead of 165, and the 28 streams it created left the process
     // with more streams than the runtime has hardware queues: every later call of the boundary was 30 % slower, for the life of the process
     // (tools/after_search.py; destroying the streams afterwards does not undo it).
-    // The opening leg of well-formed proofs does not repeat its transcripts: the prepared rows of the failed batch are still on their
-    // lane and any slice of them is the folded check of that slice (mb_ipa_recheck_rows): a round costs a fold + two MSMs per part.
-    const bool rows_ok = hv[B + 1] == 0 && c->ipa_rows && c->ipa_rows_batch == B && !mb_tune().search_full;
-    auto search = [&](bool ipa_leg, std::vector<uint8_t> &each) -> int {
+    int search(bool ipa_leg, std::vector<uint8_t> &each) {
         const size_t FAN = std::min<size_t>(MB_PIPE_LANES, std::max<size_t>(2, (size_t)mb_tune().search_fan));
         static const bool timing = getenv("MINA_VERIFY_TIMING") != nullptr;
         // streams this search had to create are destroyed when it is done
@@ -622,13 +630,13 @@ static int state_job_each(mina_ctx *c, Lane &L, const mina_state_jobs &d, uint8_
                                 std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_round).count());
         }
         return MINA_OK;
-    };
+    }
     // The grouped search (mina_ctx_set_search_groups; off by default): a failing range is cut into min(G, cnt) parts by the same formula, and ALL parts of a round --
     // of every failing range -- are checked in one pass on lane L: one segmented fold, the fixed-base MSM with one problem per part, one segmented variable-base
     // MSM, one comparison launch, one wait and one read-back of the parts' flags.  Depth ceil(log_G B) rounds; no lane but L is used and no stream is created.  A
     // round goes out in several passes only beyond mb_search_parts_cap parts (or where the segmented MSM's limits ask for fewer), queued back to back.  The opening
     // leg needs the rows of the failed batch (rows_ok), else it keeps the fan search; the counters depend on (B, G, culprits) alone.
-    auto grouped = [&](bool ipa_leg, std::vector<uint8_t> &each) -> int {
+    int grouped(bool ipa_leg, std::vector<uint8_t> &each) {
         c->L = &L;
         const size_t G = c->search_groups;
         const int curve = ipa_leg ? CURVE_PALLAS : CURVE_VESTA;
@@ -665,32 +673,107 @@ static int state_job_each(mina_ctx *c, Lane &L, const mina_state_jobs &d, uint8_
             for (size_t p = 0; p < nparts; ++p) if (!f[p]) failing.push_back({lo[p], cnt[p]});
         }
         return MINA_OK;
-    };
-    const bool in_groups = c->search_groups >= 2 && !mb_tune().search_full;
-    if (!ipa_ok) { rc = (in_groups && rows_ok) ? grouped(true, ipa_each) : search(true, ipa_each); c->L = &L; if (rc) return rc; }
-    if (!acc_ok) { rc = (in_groups && B > 1 && d.acc_rho) ? grouped(false, acc_each) : search(false, acc_each); c->L = &L; if (rc) return rc; }
+    }
+    // the failed legs, each by the search the context's settings and the leg's inputs allow: each[b] = 0 for its culprits
+    int run(bool ipa_ok, bool acc_ok, std::vector<uint8_t> &ipa_each, std::vector<uint8_t> &acc_each) {
+        int rc;
+        const bool in_groups = c->search_groups >= 2 && !mb_tune().search_full;
+        if (!ipa_ok) { rc = (in_groups && rows_ok) ? grouped(true, ipa_each) : search(true, ipa_each); c->L = &L; if (rc) return rc; }
+        if (!acc_ok) { rc = (in_groups && B > 1 && d.acc_rho) ? grouped(false, acc_each) : search(false, acc_each); c->L = &L; if (rc) return rc; }
+        return MINA_OK;
+    }
+};
+}  // namespace
+
+// The body mina_state_job_batch (after its upload) and mina_state_job_each_dev share: the job on lane L from inputs in HBM (every pointer of `d` a device pointer),
+// one verdict byte per proof on the host.  When a folded check fails: a run without the folded legs for the per-proof chain verdicts, then the search for the
+// culprits of each failed leg -- in groups on lane L alone (mina_ctx_set_search_groups) or over the fan's lanes.  Waits for lane L.  flags: the four words of the
+// whole job's folded checks ([0] opening verdict, [1] malformed opening input, [2] accumulator verdict), or null.
+static int state_job_each(mina_ctx *c, Lane &L, const mina_state_jobs &d, uint8_t *verdicts, uint32_t *flags) {
+    c->L = &L;
+    const size_t B = d.batch;
+    int rc;
+    if ((rc = L.st_verdicts.ensure(2 * B * 4 + 16))) return rc;
+    uint32_t *dv = L.st_verdicts.as<uint32_t>(), *df = dv + B, *ds = df + 4;
+    // small, latency-bound batches: the three independent legs go to three lanes (lane 0 plus two helpers), joined by events
+    StateJobPlan plan; plan.d_stmt_out = ds;
+    if (B <= 1024 && c->nlanes == 1 && &L == &c->lanes[0]) { plan.wrap = &c->lanes[1]; plan.acc = &c->lanes[2]; }
+    if ((rc = mb_state_jobs_on_lane(c, &d, dv, df, plan))) return rc;
+    std::vector<uint32_t> hv(2 * B + 4);
+    if ((rc = d2h_sync(c, hv.data(), L.st_verdicts, (2 * B + 4) * 4))) return rc;
+    if (flags) memcpy(flags, &hv[B], 16);
+    std::vector<uint8_t> stmt_each(B); for (size_t b = 0; b < B; ++b) stmt_each[b] = hv[B + 4 + b] ? 1 : 0;
+    const bool ipa_ok = hv[B] != 0, acc_ok = hv[B + 2] != 0;
+    if (ipa_ok && acc_ok) { for (size_t b = 0; b < B; ++b) verdicts[b] = hv[b] ? 1 : 0; return MINA_OK; }
+    // a folded check failed somewhere: find the culprits.  chain_ok per proof comes from a run without the folded legs.
+    std::vector<uint8_t> ipa_each(B, 1), acc_each(B, 1), chain_each(B, 1);
+    {
+        mina_state_jobs only = d; only.with_ipa = 0; only.with_accumulator = 0; only.npub = 0; only.kimchi = nullptr;
+        if (only.with_states) {
+            if ((rc = mb_state_jobs_on_lane(c, &only, dv, df))) return rc;
+            if ((rc = d2h_sync(c, hv.data(), L.st_verdicts, B * 4))) return rc;
+            for (size_t b = 0; b < B; ++b) chain_each[b] = hv[b] ? 1 : 0;
+        }
+    }
+    CulpritSearch cs(c, L, d, hv[B + 1] != 0);
+    if ((rc = cs.run(ipa_ok, acc_ok, ipa_each, acc_each))) return rc;
     for (size_t b = 0; b < B; ++b) verdicts[b] = (chain_each[b] && ipa_each[b] && acc_each[b] && stmt_each[b]) ? 1 : 0;
     return MINA_OK;
 }
 
-// host-buffer form: one upload of every section, the pipeline, one download; when a folded check fails the proofs are
-// re-checked in parts (32-way cuts, the parts of a round concurrently) so that every proof gets its own verdict (README.md:281-310: every failure is `false`)
-extern "C" int mina_state_job_batch(mina_ctx *c, const mina_state_jobs *jobs, uint8_t *verdicts) {
-    int rc = mb_check_jobs(c, jobs);
-    if (rc) return rc;
-    if (!verdicts) return fail(MINA_ERR_ARG, "null argument");
-    HIPC(hipSetDevice(c->device));
-    c->use_lane0();
-    if ((rc = mina_state_jobs_prepare(c, jobs->log2_domain, jobs->npub))) return rc;
-    c->use_lane0();
-    Lane &L = *c->L;
-    mina_state_jobs d = *jobs;
+// The masks form of that body: `passed` / `ran` words of every proof (state_masks.h) from ONE pass of the job on lane L.  The job runs once with every requested
+// leg; the chain-detail kernel then reads the hashes the state leg left on L (st_hashes) and keeps the chain word apart from the folded verdicts, so that a
+// folded failure needs the culprit searches only -- no state is hashed a second time.  d.precheck is not read (the host checks have their own bits: d_front).
+// Both folded checks good: the only host read is the four flag words.  Otherwise the culprit vectors of the failed legs are uploaded for the masks kernel.
+// d_front / d_deny: batch u32 in HBM, or null.  d_passed / d_ran: batch u32 in HBM.  Waits for lane L.  Adds (1, B) to the checks counters.
+static int state_job_checks(mina_ctx *c, Lane &L, const mina_state_jobs &jobs, const uint32_t *d_front, const uint32_t *d_deny, uint32_t *d_passed, uint32_t *d_ran, uint32_t *flags) {
+    c->L = &L;
+    mina_state_jobs d = jobs; d.precheck = nullptr;
+    const size_t B = d.batch;
+    int rc;
+    if ((rc = L.st_verdicts.ensure(2 * B * 4 + 16)) || (rc = L.st_masks.ensure(8 * B * 4))) return rc;
+    uint32_t *dv = L.st_verdicts.as<uint32_t>(), *df = dv + B;
+    uint32_t *chain = L.st_masks.as<uint32_t>(), *stmt = chain + B, *d_ipa_each = stmt + B, *d_acc_each = d_ipa_each + B;      // (the searches reuse st_verdicts: the statement words live here)
+    StateJobPlan plan; plan.d_stmt_out = stmt;
+    if (B <= 1024 && c->nlanes == 1 && &L == &c->lanes[0]) { plan.wrap = &c->lanes[1]; plan.acc = &c->lanes[2]; }
+    if ((rc = mb_state_jobs_on_lane(c, &d, dv, df, plan))) return rc;
+    ++c->checks_jobs; c->checks_proofs += B;
+    // the state leg ran on L's own stream (the plan above names no lane for it): its hashes are in L.st_hashes, ahead of this launch in stream order
+    if (d.with_states) mb::pstate_chain_detail_kernel<<<cdiv(B, 64), 64, 0, L.stream>>>((uint32_t)B, L.st_hashes.as<uint32_t>(), (const uint32_t *)d.expected_hashes, (const uint32_t *)d.state_records, chain);
+    uint32_t hf[4];
+    HIPC(hipMemcpyAsync(hf, df, 16, hipMemcpyDeviceToHost, L.stream));
+    HIPC(hipGetLastError());
+    HIPC(hipStreamSynchronize(L.stream));
+    if (flags) memcpy(flags, hf, 16);
+    const bool ipa_ok = hf[0] != 0, acc_ok = hf[2] != 0;
+    std::vector<uint32_t> each;
+    if (!(ipa_ok && acc_ok)) {
+        std::vector<uint8_t> ipa_each(B, 1), acc_each(B, 1);
+        CulpritSearch cs(c, L, d, hf[1] != 0);
+        if ((rc = cs.run(ipa_ok, acc_ok, ipa_each, acc_each))) return rc;
+        each.resize(2 * B);
+        for (size_t b = 0; b < B; ++b) { each[b] = ipa_each[b]; each[B + b] = acc_each[b]; }
+        HIPC(hipMemcpyAsync(d_ipa_each, each.data(), 2 * B * 4, hipMemcpyHostToDevice, L.stream));
+    }
+    const uint32_t sections = (d.with_states ? 1u : 0u) | (d.with_accumulator ? 2u : 0u) | (d.with_ipa ? 4u : 0u);
+    mb::state_job_masks_kernel<<<cdiv(B, 64), 64, 0, L.stream>>>((uint32_t)B, sections, d_front, d_deny, d.with_states ? chain : nullptr, stmt, each.empty() ? nullptr : d_ipa_each,
+                                                                 each.empty() ? nullptr : d_acc_each, d_passed, d_ran);
+    HIPC(hipGetLastError());
+    HIPC(hipStreamSynchronize(L.stream));
+    return MINA_OK;
+}
+
+// The upload of mina_state_job_batch and mina_state_job_checks: every section of `jobs` (host pointers) in one copy through lane L's pinned staging into L.st_in;
+// d (with kd, sd behind its pointers) = the same job over the device copies.  more: further host sections that travel behind the job's (their slots rewritten likewise).
+static int upload_jobs(mina_ctx *c, Lane &L, const mina_state_jobs *jobs, mina_state_jobs &d, mina_kimchi_proofs &kd, mina_pickles_statements &sd, const std::vector<Section> &more = {}) {
+    int rc;
+    d = *jobs;
     const size_t B = jobs->batch, k = jobs->k, m = jobs->n_comms, np = jobs->n_evalpoints, S = MINA_STATES_PER_PROOF;
     std::vector<Section> secs;
     auto add = [&](const void *&slot, size_t bytes) { if (slot && bytes) secs.push_back({&slot, bytes}); };
     if (d.with_states) { add(d.state_records, B * S * MINA_PSTATE_SLOTS * 32); add(d.state_nfields, B * S * 4); add(d.expected_hashes, B * S * 32); add(d.precheck, B); }
     if (d.npub) add(d.public_inputs, B * d.npub * 32);
-    mina_kimchi_proofs kd{}; mina_pickles_statements sd{};
+    kd = mina_kimchi_proofs{}; sd = mina_pickles_statements{};
     if (d.with_ipa && d.kimchi) {
         kd = *d.kimchi; d.kimchi = &kd;
         kd.public_inputs = nullptr;                                   // the job's own public_inputs section is the one uploaded
@@ -710,6 +793,7 @@ extern "C" int mina_state_job_batch(mina_ctx *c, const mina_state_jobs *jobs, ui
         add(d.rand_base, 32); add(d.sg_rand_base, 32);
     }
     if (d.with_accumulator) { add(d.acc_prechallenges, B * d.acc_k * 16); add(d.acc_sg, B * 64); add(d.acc_rho, B * 32); }
+    for (const Section &s : more) if (*s.slot && s.bytes) secs.push_back(s);
     size_t total = 0;
     std::vector<size_t> offs;
     for (auto &s : secs) { offs.push_back(total); total += (s.bytes + 255) & ~(size_t)255; }
@@ -720,7 +804,91 @@ extern "C" int mina_state_job_batch(mina_ctx *c, const mina_state_jobs *jobs, ui
     HIPC(hipMemcpyAsync(L.st_in.p, blob, total, hipMemcpyHostToDevice, L.stream));
     for (size_t i = 0; i < secs.size(); ++i) *secs[i].slot = L.st_in.as<uint8_t>() + offs[i];
     if (d.kimchi) kd.public_inputs = d.public_inputs;
+    return MINA_OK;
+}
+
+// host-buffer form: one upload of every section, the pipeline, one download; when a folded check fails the proofs are
+// re-checked in parts (32-way cuts, the parts of a round concurrently) so that every proof gets its own verdict (README.md:281-310: every failure is `false`)
+extern "C" int mina_state_job_batch(mina_ctx *c, const mina_state_jobs *jobs, uint8_t *verdicts) {
+    int rc = mb_check_jobs(c, jobs);
+    if (rc) return rc;
+    if (!verdicts) return fail(MINA_ERR_ARG, "null argument");
+    HIPC(hipSetDevice(c->device));
+    c->use_lane0();
+    if ((rc = mina_state_jobs_prepare(c, jobs->log2_domain, jobs->npub))) return rc;
+    c->use_lane0();
+    Lane &L = *c->L;
+    mina_state_jobs d; mina_kimchi_proofs kd; mina_pickles_statements sd;
+    if ((rc = upload_jobs(c, L, jobs, d, kd, sd))) return rc;
     return state_job_each(c, L, d, verdicts, nullptr);
+}
+
+// The masks of a job whose inputs are host buffers: mina_state_job_batch's upload (front / deny behind the job's sections), state_job_checks, one download.
+extern "C" int mina_state_job_checks(mina_ctx *c, const mina_state_jobs *jobs, const uint32_t *front, const uint32_t *deny, uint32_t *passed, uint32_t *ran) {
+    int rc = mb_check_jobs(c, jobs);
+    if (rc) return rc;
+    if (!passed || !ran) return fail(MINA_ERR_ARG, "null argument");
+    HIPC(hipSetDevice(c->device));
+    c->use_lane0();
+    if ((rc = mina_state_jobs_prepare(c, jobs->log2_domain, jobs->npub))) return rc;
+    c->use_lane0();
+    Lane &L = *c->L;
+    const size_t B = jobs->batch;
+    const void *fr = front, *dn = deny;
+    mina_state_jobs d; mina_kimchi_proofs kd; mina_pickles_statements sd;
+    if ((rc = upload_jobs(c, L, jobs, d, kd, sd, {{&fr, B * 4}, {&dn, B * 4}}))) return rc;
+    if ((rc = L.st_masks.ensure(8 * B * 4))) return rc;
+    uint32_t *out = L.st_masks.as<uint32_t>() + 6 * B;
+    if ((rc = state_job_checks(c, L, d, (const uint32_t *)fr, (const uint32_t *)dn, out, out + B, nullptr))) return rc;
+    std::vector<uint32_t> hv(2 * B);
+    HIPC(hipMemcpy(hv.data(), out, 2 * B * 4, hipMemcpyDeviceToHost));
+    memcpy(passed, hv.data(), B * 4); memcpy(ran, &hv[B], B * 4);
+    return MINA_OK;
+}
+
+// the masks body on lane 0 with the words on the host: what the boundary's mina_verify_state_checks_batch runs over a chunk's device staging (mina_ctx::state_job_checks)
+int mb_state_job_checks_host(mina_ctx *c, const mina_state_jobs *jobs, const uint32_t *d_front, const uint32_t *front, const uint32_t *deny, uint32_t *passed, uint32_t *ran) {
+    int rc = mb_check_jobs(c, jobs);
+    if (rc) return rc;
+    if (!passed || !ran || (d_front && front)) return fail(MINA_ERR_ARG, "null argument / two front vectors");
+    HIPC(hipSetDevice(c->device));
+    c->use_lane0();
+    if ((rc = mina_state_jobs_prepare(c, jobs->log2_domain, jobs->npub))) return rc;
+    c->use_lane0();
+    Lane &L = *c->L;
+    const size_t B = jobs->batch;
+    if ((rc = L.st_masks.ensure(8 * B * 4))) return rc;
+    uint32_t *w = L.st_masks.as<uint32_t>(), *d_fr = w + 4 * B, *d_dn = w + 5 * B, *out = w + 6 * B;
+    if (front) HIPC(hipMemcpyAsync(d_fr, front, B * 4, hipMemcpyHostToDevice, L.stream));
+    if (deny) HIPC(hipMemcpyAsync(d_dn, deny, B * 4, hipMemcpyHostToDevice, L.stream));
+    if ((rc = state_job_checks(c, L, *jobs, front ? d_fr : d_front, deny ? d_dn : nullptr, out, out + B, nullptr))) return rc;
+    std::vector<uint32_t> hv(2 * B);
+    HIPC(hipMemcpy(hv.data(), out, 2 * B * 4, hipMemcpyDeviceToHost));
+    memcpy(passed, hv.data(), B * 4); memcpy(ran, &hv[B], B * 4);
+    return MINA_OK;
+}
+
+extern "C" int mina_state_job_checks_dev(mina_ctx *c, const mina_state_jobs *jobs, const void *d_front, const void *d_deny, void *d_passed, void *d_ran, void *d_flags) {
+    int rc = mb_check_jobs(c, jobs);
+    if (rc) return rc;
+    if (!d_passed || !d_ran) return fail(MINA_ERR_ARG, "null argument");
+    if (((uintptr_t)d_front | (uintptr_t)d_deny | (uintptr_t)d_passed | (uintptr_t)d_ran | (uintptr_t)d_flags) & 3u) return fail(MINA_ERR_ARG, "masks and flags are 32-bit words: 4-byte alignment");
+    if (!c->have_state_salts && jobs->with_states) return fail(MINA_ERR_STATE, "call mina_state_jobs_prepare first");
+    HIPC(hipSetDevice(c->device));
+    c->next_lane();
+    Lane &L = *c->L;
+    uint32_t hf[4];
+    rc = state_job_checks(c, L, *jobs, (const uint32_t *)d_front, (const uint32_t *)d_deny, (uint32_t *)d_passed, (uint32_t *)d_ran, hf);
+    c->L = &L;
+    if (rc) return rc;
+    if (d_flags) { HIPC(hipMemcpyAsync(d_flags, hf, 16, hipMemcpyHostToDevice, L.stream)); HIPC(hipStreamSynchronize(L.stream)); }
+    return MINA_OK;
+}
+
+extern "C" int mina_ctx_checks_stats(mina_ctx *c, uint64_t *jobs, uint64_t *proofs) {
+    if (!c || !jobs || !proofs) return fail(MINA_ERR_ARG, "null argument");
+    *jobs = c->checks_jobs; *proofs = c->checks_proofs;
+    return MINA_OK;
 }
 
 // the shared body on lane 0 with the verdict bytes on the host: what the boundary's fallback runs over a failed chunk's device staging (mina_ctx::state_job_each)

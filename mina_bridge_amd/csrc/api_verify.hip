@@ -20,6 +20,8 @@
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
+#include <map>
+#include <memory>
 #include <mutex>
 #include <thread>
 
@@ -1138,11 +1140,139 @@ int state_checks(const uint8_t *proof, size_t proof_len, const uint8_t *pub, siz
     *passed_out = passed; *ran_out = ran;
     return MINA_OK;
 }
+
+// ---- the batch form of state_checks (mina_verify_state_checks_batch): the masks of n pairs, one job per chunk of a shape group instead of three jobs per proof.
+// The sections a wrong-shape entry borrows: the kimchi and statement sections only.  copy_proof_half is right for the verdict path, whose `precheck` is 0 for such an
+// entry; here the entry must still report its OWN CHAIN and ACCUMULATOR, as the single-proof form does: its expected hashes and accumulator sections stay.
+void copy_kimchi_half(const Layout &lay, uint8_t *base, size_t dst, size_t src) {
+    for (int i = 0; i < NSEC; ++i)
+        if (lay.stride[i] && i != S_PRE && i != S_REC && i != S_NF && i != S_EXP && i != S_APRE && i != S_ASG && i != S_ARHO) memcpy(lay.at(base, i, dst), lay.at(base, i, src), lay.stride[i]);
+}
+// One chunk: the pairs idx[0..m) of the call, all of shape `sh`, through ONE job with every leg (mina_ctx::state_job_checks) under the device's lock.  passed / ran
+// of the call come in as (0, FORMAT) -- what an entry keeps when nothing of the chunk parses and no job runs.
+int checks_chunk(Device &D, uint32_t flags, const Shape &sh, const CallIn &in, const size_t *idx, size_t m, uint32_t *passed_out, uint32_t *ran_out) {
+    mina_ctx *c = D.c;
+    const bool pack = (flags & MINA_VERIFY_PACK_ON_DEVICE) && c->state_frontend;
+    Layout lay; lay.build(sh, m);
+    std::unique_ptr<uint8_t[]> stage_mem(new uint8_t[lay.total + 256]);      // every section of every entry is written below (parsed, borrowed or cleared) before it is read
+    uint8_t *stage = stage_mem.get();
+    std::vector<HostBits> hbs(m);
+    mb_parallel_for(m, [&](size_t b) {
+        const size_t q = idx[b];
+        if (pack) parse_proof_half(sh, lay, stage, b, in.proofs[q], in.proof_lens[q], in.pubs[q], in.pub_lens[q], hbs[b], c);
+        else parse_into(sh, lay, stage, b, in.proofs[q], in.proof_lens[q], in.pubs[q], in.pub_lens[q], hbs[b], c);
+    });
+    // donors: `kd` lends its kimchi and statement sections (an entry of the job's shape), `pd` a whole proof half (kd, or any entry whose wrap proof parsed)
+    size_t kd = SIZE_MAX, pd = SIZE_MAX;
+    for (size_t b = 0; b < m; ++b) { if (hbs[b].proof_ok && pd == SIZE_MAX) pd = b; if (hbs[b].proof_ok && hbs[b].shape && kd == SIZE_MAX) kd = b; }
+    if (kd != SIZE_MAX) pd = kd;
+    if (pd == SIZE_MAX) return MINA_OK;                                 // no entry parses: the host bits alone
+    const bool with_kimchi = sh.kimchi && kd != SIZE_MAX;
+    std::vector<uint32_t> front(pack ? 0 : m), deny(m, 0), passed(m), ran(m);
+    for (size_t b = 0; b < m; ++b) {
+        const HostBits &hb = hbs[b];
+        if (!hb.proof_ok || (!pack && !hb.parsed)) {                    // FORMAT failed: the whole donor, so that the entry fails no folded check for the others
+            if (b != pd) copy_proof_half(lay, stage, b, pd);
+            if (!pack) clear_states_half(lay, stage, b);
+            deny[b] = MINA_CHECK_FORMAT;
+        } else if (sh.kimchi && !hb.shape) {                            // wrong shape / network, or a lookup feature: the kimchi step ran and failed; CHAIN and ACCUMULATOR are its own
+            if (with_kimchi) copy_kimchi_half(lay, stage, b, kd);
+            deny[b] = MINA_CHECK_KIMCHI;
+        }
+        if (!pack) front[b] = hb.parsed ? (MINA_CHECK_FORMAT | (hb.ledger ? MINA_CHECK_LEDGER : 0u) | (hb.consensus ? MINA_CHECK_CONSENSUS : 0u)) : 0u;
+    }
+    if (!draw_randomisers(sh, lay, stage, m)) return fail(MINA_ERR_STATE, "no entropy for the folding randomisers");
+    // MINA_VERIFY_PACK_ON_DEVICE: the protocol-state bytes as they are (gather_states' block, without the `and` bytes: the masks do not read `precheck`)
+    PackStage pk; std::vector<uint8_t> hin;
+    if (pack) {
+        std::vector<uint64_t> at(m + 1, 0);
+        size_t total = 0;
+        for (size_t b = 0; b < m; ++b) { at[b] = total; if (hbs[b].proof_ok) total += in.proof_lens[idx[b]] - hbs[b].states_at; }
+        at[m] = total;
+        pk.build(m, total);
+        hin.assign(pk.total, 0);
+        for (size_t b = 0; b < m; ++b) {
+            const size_t q = idx[b];
+            pk.begin(hin.data())[b] = at[b]; pk.end(hin.data())[b] = hbs[b].proof_ok ? at[b + 1] : at[b];
+            if (hbs[b].proof_ok) { memcpy(pk.ledger(hin.data()) + 512 * b, in.pubs[q] + 545, 512); memcpy(pk.bytes(hin.data()) + at[b], in.proofs[q] + hbs[b].states_at, at[b + 1] - at[b]); }
+        }
+    }
+    {
+        std::lock_guard<std::mutex> lk(D.mu);
+        HIPC(hipSetDevice(c->device));
+        c->use_lane0();
+        Lane &L = *c->L;
+        int rc;
+        { const bool want = (flags & MINA_VERIFY_DEDUP_STATES) != 0; if (want != c->state_dedup && (rc = mb_ctx_state_dedup(c, want))) return rc; }
+        if ((rc = L.st_in.ensure(lay.total))) return rc;
+        uint8_t *dbase = L.st_in.as<uint8_t>();
+        const uint32_t *d_front = nullptr;
+        if (pack) {                                                     // records, field counts and the front-end masks are made on the GPU: nothing of them comes back
+            HIPC(hipMemcpyAsync(dbase + lay.off[S_EXP], stage + lay.off[S_EXP], lay.total - lay.off[S_EXP], hipMemcpyHostToDevice, L.stream));
+            if ((rc = h2d(c, L.tmp_a, hin.data(), hin.size())) || (rc = L.tmp_b.ensure(m * 4))) return rc;
+            uint8_t *di = L.tmp_a.as<uint8_t>();
+            if ((rc = c->state_frontend(c, m, pk.bytes(di), pk.total - pk.blob, pk.begin(di), pk.end(di), lay.at(dbase, S_EXP, 0), pk.ledger(di), nullptr, lay.at(dbase, S_REC, 0),
+                                        lay.at(dbase, S_NF, 0), lay.at(dbase, S_PRE, 0), L.tmp_b.p))) return rc;
+            d_front = L.tmp_b.as<uint32_t>();
+        } else
+            HIPC(hipMemcpyAsync(dbase, stage, lay.total, hipMemcpyHostToDevice, L.stream));
+        JobStructs js; make_jobs(sh, lay, dbase, m, true, true, with_kimchi, js);
+        const uint32_t keep = c->search_groups;
+        if (flags & MINA_VERIFY_GROUPED_SEARCH) c->search_groups = 64u;  // as the pipeline's fallback searches under the flag
+        rc = c->state_job_checks(c, &js.j, d_front, pack ? nullptr : front.data(), deny.data(), passed.data(), ran.data());
+        c->search_groups = keep;
+        if (rc) return rc;
+    }
+    for (size_t b = 0; b < m; ++b) {
+        if (sh.kimchi && !with_kimchi && (passed[b] & MINA_CHECK_FORMAT)) ran[b] |= MINA_CHECK_KIMCHI;      // nobody of the chunk has the index's shape: the step ran and failed for all
+        passed_out[idx[b]] = passed[b]; ran_out[idx[b]] = ran[b];
+    }
+    return MINA_OK;
+}
+
+int state_checks_batch(const CallIn &in, size_t n, uint32_t *passed_out, uint32_t *ran_out) {
+    if (n == 0) return MINA_OK;
+    Device *D; uint32_t flags; int network;
+    { std::lock_guard<std::mutex> lk(g_mu); auto &ds = devices(); if (ds.empty()) return MINA_ERR_HIP; D = ds[0]; flags = g_flags; network = g_network; }
+    for (size_t i = 0; i < n; ++i) { passed_out[i] = 0; ran_out[i] = MINA_CHECK_FORMAT; }
+    if (!D->c->state_job_checks) {                                      // a context that links no kernel: proof by proof, correct by definition
+        for (size_t i = 0; i < n; ++i) if (int rc = state_checks(in.proofs[i], in.proof_lens[i], in.pubs[i], in.pub_lens[i], &passed_out[i], &ran_out[i])) return rc;
+        return MINA_OK;
+    }
+    const Config cf = read_config(*D, flags | MINA_VERIFY_ALLOW_SURROGATE, network);
+    const Shape sh0 = shape_of_config(cf);
+    // the evaluation shape of every pair, as the single-proof form derives it; a pair whose wrap proof does not read keeps (0, FORMAT)
+    std::vector<uint32_t> key(n, 0);
+    if (sh0.statements)
+        mb_parallel_for(n, [&](size_t i) {
+            mw::StateProofContainer &box = tl_box();
+            mw::Bincode cur(in.proofs[i], in.proofs[i] ? in.proof_lens[i] : 0);
+            if (!in.proofs[i] || !mw::read_wrap_proof(cur, box.tip_proof)) { key[i] = 0xffffffffu; return; }
+            const uint32_t n_old = (uint32_t)std::min<size_t>(box.tip_proof.step_old_bulletproof_challenges.size(), 4), n_ev = (uint32_t)std::min<size_t>(std::max<size_t>(box.tip_proof.prev_evals.size(), 43), 62);
+            key[i] = n_old << 8 | n_ev;
+        });
+    std::map<uint32_t, std::vector<size_t>> groups;
+    for (size_t i = 0; i < n; ++i) if (key[i] != 0xffffffffu) groups[key[i]].push_back(i);
+    const size_t chunk = std::min<size_t>(std::max<size_t>(1, mb_tune().chunk), 65536);
+    for (const auto &g : groups) {
+        Shape sh = sh0;
+        if (sh0.statements) { sh.n_old = g.first >> 8; sh.n_ev = g.first & 0xffu; }
+        for (size_t lo = 0; lo < g.second.size(); lo += chunk)
+            if (int rc = checks_chunk(*D, flags, sh, in, g.second.data() + lo, std::min(chunk, g.second.size() - lo), passed_out, ran_out)) return rc;
+    }
+    return MINA_OK;
+}
 }  // namespace
 
 extern "C" int mina_verify_state_checks(const uint8_t *proof, size_t proof_len, const uint8_t *pub, size_t pub_len, uint32_t *passed_mask, uint32_t *ran_mask) {
     if (!passed_mask || !ran_mask) return fail(MINA_ERR_ARG, "null argument");
     return state_checks(proof, proof_len, pub, pub_len, passed_mask, ran_mask);
+}
+extern "C" int mina_verify_state_checks_batch(size_t n, const uint8_t *const *proofs, const size_t *proof_lens, const uint8_t *const *pubs, const size_t *pub_lens,
+                                              uint32_t *passed_masks, uint32_t *ran_masks) {
+    if (n && (!proofs || !proof_lens || !pubs || !pub_lens || !passed_masks || !ran_masks)) return fail(MINA_ERR_ARG, "null argument");
+    CallIn in{proofs, proof_lens, pubs, pub_lens};
+    return state_checks_batch(in, n, passed_masks, ran_masks);
 }
 
 // the merged job of single-proof callers (and of small batches)

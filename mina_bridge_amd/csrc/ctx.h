@@ -129,6 +129,7 @@ struct Lane {
     DevBuf bp_seg_ids; PinnedBuf bp_seg_stage;   // mina_b_poly_fold_segments_dev: the ids of its matrix-core segments and their pinned host side (written only behind that call's wait for the lane)
     DevBuf ipa_chals, ipa_folded, ipa_xyzz_a, ipa_xyzz_b, ipa_points, ipa_scalars, ipa_sigma, ipa_in_a, ipa_in_b, ipa_in_c, ipa_verdict, ipa_xfer, ipa_shared, ipa_shared_off, acc_rho_scaled /* exchange variant: the caller's acc_rho times the shard's own CSPRNG scalar */;
     DevBuf st_ok, st_hashes, st_pub_xyzz, st_pubcomm, st_flags, st_in, st_verdicts;   // Proof-of-State job (api_state.hip)
+    DevBuf st_masks;                         // its masks form (api_state.hip state_job_checks): chain | statement | opening culprits | accumulator culprits | front | deny | passed | ran, batch u32 each
     DevBuf dd_rep, dd_uniq, dd_table, dd_counts;  // its deduplicated state leg (state_dedup.cuh): 4 B x n each, the table 16 B x the power of two >= 2 n, counters + one word per 1024 states
     DevBuf pk_off, pk_len, pk_status, pk_info, pk_fmt;   // the packed-on-device front end (state_pack.cuh; api_pack.hip): 8 B + 4 B + 1 B per state, two info structs + 1 B per proof
     DevBuf ac_ws, ac_in;                     // the device path of a Proof-of-Account job (account_pack.cuh; api_account_dev.hip): its workspace (AccountWs), the uploaded bytes + verdict words of a boundary call
@@ -292,6 +293,12 @@ struct mina_ctx : Installed {
     // mb_state_job_each_host).  Filled by mina_ctx_create; the boundary hands a failed chunk's device staging to it under MINA_VERIFY_GROUPED_SEARCH, and a context
     // without it -- the stand-in contexts of the ThreadSanitizer tier -- keeps the host-buffer path.
     int (*state_job_each)(mina_ctx *c, const mina_state_jobs *dev_jobs, uint8_t *verdicts) = nullptr;
+    // The masks form of the job (api_state.hip mb_state_job_checks_host): `passed` / `ran` words (host) of a job whose inputs are in HBM, on lane 0, waited for.
+    // front: the front end's d_masks in HBM (d_front), or host words to upload (front), or neither; deny: host words or null.  Filled by mina_ctx_create; the boundary's
+    // mina_verify_state_checks_batch reaches the body through it, and a context without it -- the stand-in contexts of the ThreadSanitizer tier -- answers proof by
+    // proof through the single-proof form.  checks_jobs / checks_proofs (mina_ctx_checks_stats): the full job passes checks calls have queued, and the proofs in them.
+    int (*state_job_checks)(mina_ctx *c, const mina_state_jobs *dev_jobs, const uint32_t *d_front, const uint32_t *front, const uint32_t *deny, uint32_t *passed, uint32_t *ran) = nullptr;
+    uint64_t checks_jobs = 0, checks_proofs = 0;
     uint32_t dev_fork_made = 0;      // the dev_fork value the helper lanes' streams were created under (streams keep their mask / priority for life)
     // The streams behind the helper lanes of the forked jobs (StreamPlan), created on first use, destroyed once by mina_ctx_destroy: plan A's, three per pipeline
     // lane, and plan B's role streams.  stream_budget: forced by mina_ctx_set_stream_budget (> 0), else the environment's, read when the first job forks (-1: not yet).
@@ -419,6 +426,7 @@ int mb_state_frontend_on_lane(mina_ctx *c, size_t batch, const void *d_blob, siz
 int mb_verify_account_dev_on(mina_ctx *c, size_t n, const uint8_t *const *proofs, const size_t *proof_lens, const uint8_t *const *pubs, const size_t *pub_lens,
                              uint32_t *passed, uint32_t *ran, Lane *lane, std::mutex *enq_mu);   // api_account_dev.hip: the same on the device, from the bytes as they are
 int mb_state_job_each_host(mina_ctx *c, const mina_state_jobs *dev_jobs, uint8_t *verdicts);   // api_state.hip
+int mb_state_job_checks_host(mina_ctx *c, const mina_state_jobs *dev_jobs, const uint32_t *d_front, const uint32_t *front, const uint32_t *deny, uint32_t *passed, uint32_t *ran);   // api_state.hip
 int mb_state_hashes_early(mina_ctx *c, Lane *LS, size_t ns_total, size_t lo, size_t cnt, const uint32_t *d_records, const uint32_t *d_nfields, hipEvent_t after, HashLaunch hash);   // state_job.hip
 // The device layer under state_job.hip, defined where the kernels are (api_state.hip): the argument checks of a job, the state hashes of a leg on the current
 // lane (plain, or each distinct record once), and one launch function per kernel the legs launch themselves -- the same grid and block on the stream given, nothing else.

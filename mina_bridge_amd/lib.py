@@ -38,11 +38,12 @@ EXPORTS = [
     "mina_protocol_state_dedup_dev", "mina_protocol_state_hash_batch_dedup", "mina_ctx_set_state_dedup", "mina_ctx_state_dedup_stats",
     "mina_protocol_state_pack_dev", "mina_state_frontend_dev", "mina_account_frontend_dev", "mina_account_job_dev",
     "mina_state_jobs_prepare", "mina_state_job_batch_dev", "mina_state_job_batch", "mina_state_job_fold_dev",
+    "mina_state_job_checks_dev", "mina_state_job_checks", "mina_ctx_checks_stats",
     "mina_challenge_to_field_dev", "mina_field_sum_rows_dev", "mina_msm_srs_range_dev", "mina_msm_dev", "mina_points_sum_dev", "mina_point_records_equal_dev",
     "mina_msm_segments_dev", "mina_b_poly_fold_segments_dev", "mina_state_job_each_dev", "mina_ctx_set_search_groups", "mina_ctx_search_stats", "mina_ctx_set_seg_fold_mfma_min", "mina_ctx_seg_fold_stats", "mina_ctx_set_msm_fused_tail", "mina_ctx_msm_tail_stats", "mina_ctx_set_fast_inverse", "mina_ctx_inverse_stats", "mina_ctx_set_chain_inverse", "mina_ctx_chain_inverse_stats", "mina_ctx_lane_streams", "mina_ctx_set_stream_budget", "mina_ctx_stream_plan_stats",
     "mina_step_index_install", "mina_step_index_load_json", "mina_polish_tokens_from_json", "mina_verifier_index_load_json", "mina_pickles_public_input",
     "mina_verifier_index_install", "mina_verifier_index_digest", "mina_kimchi_to_batch", "mina_pickles_public_inputs_batch", "mina_wrap_proof_flatten", "mina_state_proof_split",
-    "mina_verify_state", "mina_verify_state_batch", "mina_verify_state_checks", "mina_verify_state_files", "mina_verify_account", "mina_verify_account_batch",
+    "mina_verify_state", "mina_verify_state_batch", "mina_verify_state_checks", "mina_verify_state_checks_batch", "mina_verify_state_files", "mina_verify_account", "mina_verify_account_batch",
     "mina_verify_account_files", "mina_verify_account_checks", "mina_verify_account_ctx", "mina_account_hash_batch", "mina_account_abi_encode", "mina_verify_configure", "mina_verify_shutdown", "mina_verify_global_ctx", "mina_poseidon_params_name",
     "mina_verify_device_count", "mina_verify_device_ctx", "mina_verify_set_network", "mina_verify_install_verifier_index", "mina_verify_install_step_index", "mina_verify_set_poseidon_params",
     "mina_poseidon_install_default_params",
@@ -310,6 +311,18 @@ def verify_state_batch(proofs: list, pubs: list) -> np.ndarray:
     if rc != 0:
         raise MinaError(f"mina_verify_state_batch failed ({rc}): {lib.mina_last_error().decode()}")
     return out[:n]
+
+
+def verify_state_checks_batch(proofs: list, pubs: list):
+    """(passed, ran) masks (uint32 each) of every pair of a batch: what verify_state_checks answers pair by pair, from one job per evaluation shape"""
+    lib = load_library()
+    n = len(proofs)
+    pa, PP, PL = _ptr_arrays(proofs); qa, QQ, QL = _ptr_arrays(pubs)
+    passed = np.zeros(max(n, 1), np.uint32); ran = np.zeros(max(n, 1), np.uint32)
+    rc = lib.mina_verify_state_checks_batch(ctypes.c_size_t(n), PP, PL, QQ, QL, _p(passed), _p(ran))
+    if rc != 0:
+        raise MinaError(f"mina_verify_state_checks_batch failed ({rc}): {lib.mina_last_error().decode()}")
+    return passed[:n], ran[:n]
 
 
 def verify_state_files(proof_path: str, pub_path: str) -> bool:
@@ -1230,6 +1243,31 @@ class MinaContext:
     def state_job_each_dev(self, jobs, d_verdicts: int, d_flags: int = 0):
         """per-proof verdicts (u32 each) of a job whose inputs are in HBM (`jobs` as for state_job_batch_dev); waits for its lane"""
         self._ck(self._lib.mina_state_job_each_dev(self._h, ctypes.byref(jobs), ctypes.c_void_p(d_verdicts), ctypes.c_void_p(d_flags or None)), "mina_state_job_each_dev")
+
+    def state_job_checks(self, jobs, front=None, deny=None):
+        """(passed, ran) MINA_CHECK_* masks (uint32 per proof) of a host-side job from ONE pass of it; front: the FORMAT / LEDGER / CONSENSUS bits that passed per
+        proof, or None (those two checks then do not run); deny: bits the caller has decided fail, or None.  `precheck` of the job is not read"""
+        j, keep = jobs
+        B = j.batch
+        f = None if front is None else np.ascontiguousarray(front, np.uint32)
+        d = None if deny is None else np.ascontiguousarray(deny, np.uint32)
+        if (f is not None and f.size != B) or (d is not None and d.size != B):
+            raise ValueError("front / deny: one word per proof")
+        passed = np.zeros(B, np.uint32); ran = np.zeros(B, np.uint32)
+        self._ck(self._lib.mina_state_job_checks(self._h, ctypes.byref(j), None if f is None else _p(f), None if d is None else _p(d), _p(passed), _p(ran)), "mina_state_job_checks")
+        return passed, ran
+
+    def state_job_checks_dev(self, d_jobs, d_front: int, d_deny: int, d_passed: int, d_ran: int, d_flags: int = 0):
+        """the masks of a job whose inputs are in HBM (`d_jobs` as for state_job_batch_dev; d_front / d_deny 0 = absent); waits for its lane"""
+        v = ctypes.c_void_p
+        self._ck(self._lib.mina_state_job_checks_dev(self._h, ctypes.byref(d_jobs), v(d_front or None), v(d_deny or None), v(d_passed or None), v(d_ran or None), v(d_flags or None)),
+                 "mina_state_job_checks_dev")
+
+    def checks_stats(self) -> dict:
+        """full job passes the checks calls of this context have queued, and the proofs in them, since it was created"""
+        a, b = ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self._ck(self._lib.mina_ctx_checks_stats(self._h, ctypes.byref(a), ctypes.byref(b)), "mina_ctx_checks_stats")
+        return {"jobs": a.value, "proofs": b.value}
 
     def state_jobs_prepare(self, log2_domain: int, npub: int):
         self._ck(self._lib.mina_state_jobs_prepare(self._h, ctypes.c_uint32(log2_domain), ctypes.c_uint32(npub)), "mina_state_jobs_prepare")
