@@ -303,6 +303,67 @@ func VerifyAccountInclusionFFI(proof, pub []byte) bool {
 	return bool(C.mina_verify_account((*C.uint8_t)(unsafe.Pointer(&proof[0])), C.size_t(len(proof)), (*C.uint8_t)(unsafe.Pointer(&pub[0])), C.size_t(len(pub))))
 }
 
+// Queue: the completion queue (mina_verify_queue_*): Submit from any goroutine, one goroutine owns Wait and feeds a channel (INTEGRATION.md has the sketch).
+type Queue struct{ p *C.mina_verify_queue }
+
+// Completion: Tag is the submission's; Verdict is false whenever Rc != 0.
+type Completion struct {
+	Tag     uint64
+	Verdict bool
+	Rc      int
+	Kind    uint8
+}
+
+func NewQueue(capacity, workers uint32) (*Queue, error) {
+	var p *C.mina_verify_queue
+	if rc := C.mina_verify_queue_create(C.uint32_t(capacity), C.uint32_t(workers), &p); rc != 0 {
+		return nil, lastError()
+	}
+	return &Queue{p}, nil
+}
+
+// Close runs what is still pending, waits for it and frees the queue; no other call on the queue may be in flight.
+func (q *Queue) Close() { C.mina_verify_queue_destroy(q.p) }
+
+// Submit: the queue copies both slices before it returns.  accepted = false: every slot is held (MINA_ERR_FULL), take completions first.
+func (q *Queue) Submit(kind uint32, proof, pub []byte, tag uint64, more bool) (accepted bool, err error) {
+	var pp, qq *C.uint8_t
+	if len(proof) > 0 {
+		pp = (*C.uint8_t)(unsafe.Pointer(&proof[0]))
+	}
+	if len(pub) > 0 {
+		qq = (*C.uint8_t)(unsafe.Pointer(&pub[0]))
+	}
+	flags := C.uint32_t(0)
+	if more {
+		flags = C.MINA_SUBMIT_MORE
+	}
+	rc := C.mina_verify_queue_submit(q.p, C.uint32_t(kind), pp, C.size_t(len(proof)), qq, C.size_t(len(pub)), C.uint64_t(tag), flags)
+	if rc == C.MINA_ERR_FULL {
+		return false, nil
+	}
+	if rc != 0 {
+		return false, lastError()
+	}
+	return true, nil
+}
+
+func (q *Queue) Flush() { C.mina_verify_queue_flush(q.p) }
+
+// Wait blocks until a completion is available or timeoutUs has passed (negative: for ever) and returns up to max of them.
+func (q *Queue) Wait(max int, timeoutUs int64) []Completion {
+	buf := make([]C.mina_verify_completion, max)
+	var n C.size_t
+	if max == 0 || C.mina_verify_queue_wait(q.p, &buf[0], C.size_t(max), &n, C.int64_t(timeoutUs)) != 0 {
+		return nil
+	}
+	out := make([]Completion, int(n))
+	for i := range out {
+		out[i] = Completion{uint64(buf[i].tag), buf[i].verdict == 1, int(buf[i].rc), uint8(buf[i].kind)}
+	}
+	return out
+}
+
 // VerifyAccountInclusion: the Merkle part of verify_account_inclusion_ffi on the reference's byte contract.
 func (c *Ctx) VerifyAccountInclusion(proof, pub, leafHash []byte) (bool, error) {
 	var verdict C.uint8_t

@@ -71,3 +71,36 @@ pub fn verify_mina_state_batch(proofs: &[&[u8]], pub_inputs: &[&[u8]]) -> Vec<bo
 impl Drop for Ctx {
     fn drop(&mut self) { unsafe { mina_ctx_destroy(self.0) } }
 }
+
+/// Completion queue (`mina_verify_queue_*`): submit from any task, take `(tag, verdict)` pairs later; `fd()` is what a tokio `AsyncFd` registers
+/// (INTEGRATION.md has the sketch).  Never compiled either (see above).
+pub struct Queue(*mut mina_verify_queue);
+unsafe impl Send for Queue {}
+unsafe impl Sync for Queue {}        // every call but the drop is safe from any number of threads
+impl Queue {
+    pub fn new(capacity: u32, workers: u32) -> Result<Self, MinaError> {
+        let mut p = std::ptr::null_mut();
+        check(unsafe { mina_verify_queue_create(capacity, workers, &mut p) })?;
+        Ok(Queue(p))
+    }
+    /// Ok(true) = accepted, Ok(false) = every slot is held (MINA_ERR_FULL): take completions first.
+    pub fn submit(&self, kind: u32, proof: &[u8], pub_input: &[u8], tag: u64, more: bool) -> Result<bool, MinaError> {
+        let rc = unsafe { mina_verify_queue_submit(self.0, kind, proof.as_ptr(), proof.len(), pub_input.as_ptr(), pub_input.len(), tag, more as u32) };
+        if rc == -5 { Ok(false) } else { check(rc).map(|_| true) }
+    }
+    pub fn flush(&self) { unsafe { mina_verify_queue_flush(self.0); } }
+    pub fn poll(&self, out: &mut [mina_verify_completion]) -> usize {
+        let mut n = 0usize;
+        unsafe { mina_verify_queue_poll(self.0, out.as_mut_ptr(), out.len(), &mut n); }
+        n
+    }
+    pub fn wait(&self, out: &mut [mina_verify_completion], timeout_us: i64) -> usize {
+        let mut n = 0usize;
+        unsafe { mina_verify_queue_wait(self.0, out.as_mut_ptr(), out.len(), &mut n, timeout_us); }
+        n
+    }
+    pub fn fd(&self) -> i32 { unsafe { mina_verify_queue_fd(self.0) } }
+}
+impl Drop for Queue {
+    fn drop(&mut self) { unsafe { mina_verify_queue_destroy(self.0) } }
+}

@@ -953,6 +953,64 @@ bool verify_mina_state_ffi(const uint8_t *proof_buffer, size_t proof_len, const 
 bool verify_account_inclusion_ffi(const uint8_t *proof_buffer, size_t proof_len, const uint8_t *pub_input_buffer, size_t pub_input_len);
 bool verify_mina_state_ffi_u32(const uint8_t *proof_buffer, uint32_t proof_len, const uint8_t *pub_input_buffer, uint32_t pub_input_len);
 bool verify_account_inclusion_ffi_u32(const uint8_t *proof_buffer, uint32_t proof_len, const uint8_t *pub_input_buffer, uint32_t pub_input_len);
+/* ---- completion queue: submit proofs, collect verdicts later -----------------------------------------------------------
+ * The entry points above block one OS thread per proof in flight.  An async caller (a tokio task, a goroutine) submits to a queue instead and takes the verdicts
+ * later, from `poll`, `wait`, or when the queue's descriptor turns readable: thousands of proofs in flight from a few threads.  The queue adds no verification path
+ * of its own: its workers hand their submissions to the same merged jobs the synchronous entry points feed, so a verdict is the synchronous one by construction.
+ *
+ * submit    copies both byte strings into storage the queue owns -- the caller may free or overwrite its buffers as soon as it returns --, never blocks on the
+ *           GPU and never runs a job on the calling thread.  A null queue, an unknown `kind`, an unknown bit in `flags`, a null pointer with a non-zero length or a
+ *           length above 1 MiB (the cap of the `_files` forms) is MINA_ERR_ARG and consumes no slot.  Zero lengths are legal: an empty proof is a `false` verdict,
+ *           as it is for mina_verify_state.  `tag` is the caller's; it comes back in the completion.
+ * slots     a submission holds one of the queue's `capacity` (1 .. 65 536) slots from `submit` until its completion has been HANDED OUT by `poll` or `wait`.  With
+ *           every slot held `submit` returns MINA_ERR_FULL and changes nothing.  That is the only back-pressure: it bounds the queue's memory to `capacity` x the
+ *           submitted bytes, and completions can never overflow.  A slot keeps its byte buffer: a queue in steady state stops allocating.
+ * completions  one per accepted submission, exactly once, in no particular order.  `verdict` is 0 or 1; `rc` is the code the synchronous batch entry point would
+ *           have returned for the job the submission rode in (MINA_OK, or e.g. MINA_ERR_HIP without a device), and the verdict is 0 whenever rc != MINA_OK.  For
+ *           every input, malformed ones included, and under every mina_verify_configure flag set, `verdict` equals mina_verify_state / mina_verify_account called
+ *           with the same bytes at the same moment.
+ * dispatch  `workers` (1 .. 4) threads belong to the queue, created by `create` and joined by `destroy`.  A free worker takes every dispatchable submission of ONE
+ *           kind, at most 8192, and passes them as one group to the merger of concurrent callers, the way mina_verify_state_batch / _account_batch pass a small
+ *           batch: queue submissions merge with synchronous callers' proofs and obey mina_verify_tuning.merge, .max_jobs and .linger_us exactly as a thread calling
+ *           the batch entry point with those proofs would.  While a job runs, new submissions pile up and leave together as the next job: the merger's group commit
+ *           with no thread per proof.  A submission with MINA_SUBMIT_MORE is not dispatchable until a later submission of the same queue (of either kind) arrives
+ *           without the flag, or `flush` or `destroy` is called: a caller that knows its burst puts it into one job.  (A burst that meets MINA_ERR_FULL must
+ *           `flush`: what it holds back may be all the queue holds, and nothing else would start it.)  workers = 1 is the recommendation: the
+ *           measured table (tools/bench_queue.py) shows no consistent gain from two workers or from two overlapping jobs.
+ * poll / wait  `poll` never blocks; `wait` blocks until at least one completion is available or `timeout_us` has passed (negative: for ever).  Both write at most
+ *           `cap` completions, set *n_out (which may be 0) and return MINA_OK unless an argument is bad (null queue or n_out, null `out` with cap > 0).
+ * fd        an eventfd (non-blocking, close-on-exec) that is readable whenever completions are pending -- what a tokio `AsyncFd` or Go's netpoller registers.  The
+ *           queue owns the descriptor (never close it); it is written once per finished job.  The consumer reads it (8 bytes) to clear it and then polls until
+ *           *n_out == 0.  `poll` / `wait` clear it themselves when they hand out the last pending completion.
+ * stats     submissions accepted, completions published (taken or not), groups the workers handed to the merger (jobs they led or joined), the largest group.
+ *           Any output may be NULL.
+ * threads   every call except `destroy` is safe from any number of threads at once.  `destroy` must not race with other calls on the same queue: it makes
+ *           everything pending dispatchable, waits for the jobs that are running, discards completions not yet taken and frees everything.  destroy(NULL) is a no-op.
+ * shutdown  a worker stands towards mina_verify_shutdown and mina_verify_install_* / _set_poseidon_params exactly where a synchronous caller thread stands: same locks,
+ *           same order (g_mu, search_mu, mu), taken inside the job only.  The installers may run beside a busy queue.  mina_verify_shutdown does NOT wait for a
+ *           running merged job -- it is for a process with no verification in flight --, so call it on an IDLE queue only (stats: submitted == completed); the queue
+ *           stays usable afterwards, the process-wide contexts come back with the next job as they do for mina_verify_state.  Creating a queue touches no device. */
+typedef struct mina_verify_queue mina_verify_queue;
+typedef struct {
+    uint64_t tag;       /* the submission's */
+    int32_t rc;         /* MINA_OK or the job's error code */
+    uint8_t verdict;    /* 0 / 1 */
+    uint8_t kind;       /* MINA_QUEUE_STATE / MINA_QUEUE_ACCOUNT */
+    uint8_t pad[2];
+} mina_verify_completion;                        /* 16 bytes */
+#define MINA_QUEUE_STATE 0u
+#define MINA_QUEUE_ACCOUNT 1u
+#define MINA_SUBMIT_MORE 1u      /* more submissions follow at once: do not start a job for this one yet */
+#define MINA_ERR_FULL (-5)       /* the queue holds `capacity` submissions whose completions have not been taken */
+int mina_verify_queue_create(uint32_t capacity, uint32_t workers, mina_verify_queue **out);
+void mina_verify_queue_destroy(mina_verify_queue *q);
+int mina_verify_queue_submit(mina_verify_queue *q, uint32_t kind, const uint8_t *proof, size_t proof_len, const uint8_t *pub_input, size_t pub_len, uint64_t tag,
+                             uint32_t flags);
+int mina_verify_queue_flush(mina_verify_queue *q);
+int mina_verify_queue_poll(mina_verify_queue *q, mina_verify_completion *out, size_t cap, size_t *n_out);
+int mina_verify_queue_wait(mina_verify_queue *q, mina_verify_completion *out, size_t cap, size_t *n_out, int64_t timeout_us);
+int mina_verify_queue_fd(mina_verify_queue *q);
+int mina_verify_queue_stats(mina_verify_queue *q, uint64_t *submitted, uint64_t *completed, uint64_t *jobs, uint64_t *max_job);
 int mina_verify_account_checks(const uint8_t *proof, size_t proof_len, const uint8_t *pub_input, size_t pub_len, uint32_t *passed_mask, uint32_t *ran_mask);
 /* the same on a caller-owned context (n pairs, masks per pair) */
 int mina_verify_account_ctx(mina_ctx *ctx, size_t n, const uint8_t *const *proofs, const size_t *proof_lens, const uint8_t *const *pub_inputs,

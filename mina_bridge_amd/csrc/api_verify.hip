@@ -25,6 +25,9 @@
 #include <mutex>
 #include <thread>
 
+#include <sys/eventfd.h>
+#include <unistd.h>
+
 #include "ctx.h"
 #include "sponge.cuh"
 #include "wire_proof.h"
@@ -1474,4 +1477,156 @@ extern "C" bool verify_mina_state_ffi_u32(const uint8_t *proof_buffer, uint32_t 
 }
 extern "C" bool verify_account_inclusion_ffi_u32(const uint8_t *proof_buffer, uint32_t proof_len, const uint8_t *pub_input_buffer, uint32_t pub_input_len) {
     return verify_account_inclusion_ffi(proof_buffer, (size_t)proof_len, pub_input_buffer, (size_t)pub_input_len);
+}
+
+// ------------------------------------------------------------------------------------------------ completion queue: submit proofs, collect verdicts later
+// The merger above costs one blocked OS thread per proof in flight; an async caller (a tokio task, a goroutine) has none to spare.  A queue owns its submissions'
+// bytes and 1 .. 4 worker threads: a free worker takes every dispatchable submission of one kind (at most CallMerger::MAX_JOB) and hands them to the merger as ONE
+// group, exactly as mina_verify_state_batch / _account_batch hand over a small batch -- so they share jobs with synchronous callers, obey .merge / .max_jobs /
+// .linger_us as such a caller does, and a worker stands where a synchronous caller thread stands towards mina_verify_shutdown and the installers (it takes the
+// boundary's locks only inside exec_*: g_mu, search_mu, mu).  Pure host code: mutex, condition variables, an eventfd; no runtime call outside exec_*.
+// Semantics: include/mina_verify.h.  Everything below `mu`; the lists are threaded through the slab (`next`), so a queue in steady state allocates nothing.
+struct mina_verify_queue {
+    enum : uint8_t { Q_FREE, Q_PENDING, Q_RUNNING, Q_DONE };
+    static constexpr uint32_t NIL = 0xffffffffu;
+    struct Entry { PendingCall call{nullptr, 0, nullptr, 0}; uint64_t tag = 0; uint32_t next = NIL; uint8_t kind = 0, state = Q_FREE; std::vector<uint8_t> bytes; };
+    struct List {
+        uint32_t head = NIL, tail = NIL; size_t n = 0;
+        void push(std::vector<Entry> &slab, uint32_t i) { slab[i].next = NIL; if (tail == NIL) head = i; else slab[tail].next = i; tail = i; ++n; }
+        uint32_t pop(std::vector<Entry> &slab) { const uint32_t i = head; head = slab[i].next; if (head == NIL) tail = NIL; --n; return i; }
+    };
+    std::mutex mu; std::condition_variable work_cv, done_cv;
+    std::vector<Entry> slab;
+    List free_list, pending[2], completed;
+    size_t ready[2] = {0, 0};            // how many entries at the head of pending[kind] are dispatchable (MINA_SUBMIT_MORE holds the rest back)
+    uint64_t n_submitted = 0, n_completed = 0, n_jobs = 0, n_max_job = 0;
+    unsigned next_kind = 0;              // the kinds take turns when both have work
+    bool stopping = false, signalled = false;   // signalled: the descriptor has been written since it was last cleared here
+    int efd = -1;
+    std::vector<std::thread> workers;
+
+    void release_all() { ready[0] = pending[0].n; ready[1] = pending[1].n; if (ready[0] || ready[1]) work_cv.notify_all(); }      // caller holds mu
+    // hands out up to `cap` completions and frees their slots; keeps the descriptor's level right (readable iff completions are pending).  Caller holds mu.
+    size_t take(mina_verify_completion *out, size_t cap) {
+        size_t k = 0;
+        while (k < cap && completed.n) {
+            const uint32_t i = completed.pop(slab); Entry &e = slab[i];
+            out[k].tag = e.tag; out[k].rc = e.call.rc; out[k].verdict = e.call.verdict; out[k].kind = e.kind; out[k].pad[0] = out[k].pad[1] = 0; ++k;
+            e.state = Q_FREE; free_list.push(slab, i);
+        }
+        uint64_t v = 1;                                                          // (the consumer may have read the descriptor itself: a second read finds nothing, a second write only counts)
+        if (completed.n == 0) { if (signalled) { (void)!read(efd, &v, sizeof v); signalled = false; } }
+        else if (k) { (void)!write(efd, &v, sizeof v); signalled = true; }
+        return k;
+    }
+    void work() {
+        std::vector<uint32_t> taken; std::vector<PendingCall> calls;
+        std::unique_lock<std::mutex> lk(mu);
+        for (;;) {
+            work_cv.wait(lk, [&] { return ready[0] || ready[1] || stopping; });
+            unsigned k = next_kind; if (!ready[k]) k ^= 1u;
+            if (!ready[k]) return;                                            // stopping, and destroy has made everything dispatchable: nothing is left
+            next_kind = k ^ 1u;
+            const size_t n = std::min(ready[k], CallMerger::MAX_JOB);
+            taken.clear(); calls.clear();
+            for (size_t i = 0; i < n; ++i) {
+                const uint32_t ix = pending[k].pop(slab); Entry &e = slab[ix];
+                e.state = Q_RUNNING; taken.push_back(ix); calls.push_back(PendingCall{e.call.proof, e.call.proof_len, e.call.pub, e.call.pub_len});
+            }
+            ready[k] -= n;
+            lk.unlock();
+            int thrown = MINA_OK;
+            try {
+                if (k == MINA_QUEUE_STATE) g_state_calls.run_group(exec_state_calls, calls.data(), n); else g_account_calls.run_group(exec_account_calls, calls.data(), n);
+            } catch (...) { thrown = MINA_ERR_STATE; }                         // (allocation failure: nothing else throws; as the _ffi forms, the answer is `false`)
+            lk.lock();
+            for (size_t i = 0; i < n; ++i) {
+                Entry &e = slab[taken[i]];
+                e.call.rc = thrown ? thrown : calls[i].rc; e.call.verdict = e.call.rc == MINA_OK && calls[i].verdict == 1 ? 1 : 0;
+                e.state = Q_DONE; completed.push(slab, taken[i]);
+            }
+            n_completed += n; ++n_jobs; n_max_job = std::max<uint64_t>(n_max_job, n);
+            const uint64_t one = 1; (void)!write(efd, &one, sizeof one); signalled = true;      // once per job
+            done_cv.notify_all();
+        }
+    }
+};
+
+extern "C" int mina_verify_queue_create(uint32_t capacity, uint32_t workers, mina_verify_queue **out) {
+    if (!out) return fail(MINA_ERR_ARG, "null argument");
+    *out = nullptr;
+    if (capacity < 1 || capacity > 65536) return fail(MINA_ERR_ARG, "queue capacity must be 1 .. 65536");
+    if (workers < 1 || workers > 4) return fail(MINA_ERR_ARG, "queue workers must be 1 .. 4");
+    mina_verify_queue *q = nullptr;
+    try {
+        q = new mina_verify_queue();
+        q->slab.resize(capacity);
+        for (uint32_t i = 0; i < capacity; ++i) q->free_list.push(q->slab, i);
+        if ((q->efd = eventfd(0, EFD_NONBLOCK | EFD_CLOEXEC)) < 0) { delete q; return fail(MINA_ERR_STATE, "eventfd failed"); }
+        q->workers.reserve(workers);
+        for (uint32_t w = 0; w < workers; ++w) q->workers.emplace_back([q] { q->work(); });
+    } catch (...) {
+        if (q) { mina_verify_queue_destroy(q); }
+        return fail(MINA_ERR_STATE, "could not create the queue");
+    }
+    *out = q;
+    return MINA_OK;
+}
+extern "C" void mina_verify_queue_destroy(mina_verify_queue *q) {
+    if (!q) return;
+    { std::lock_guard<std::mutex> lk(q->mu); q->stopping = true; q->release_all(); q->work_cv.notify_all(); }
+    for (auto &t : q->workers) t.join();
+    if (q->efd >= 0) (void)close(q->efd);
+    delete q;
+}
+extern "C" int mina_verify_queue_submit(mina_verify_queue *q, uint32_t kind, const uint8_t *proof, size_t proof_len, const uint8_t *pub, size_t pub_len, uint64_t tag, uint32_t flags) {
+    if (!q) return fail(MINA_ERR_ARG, "null argument");
+    if (kind != MINA_QUEUE_STATE && kind != MINA_QUEUE_ACCOUNT) return fail(MINA_ERR_ARG, "unknown queue kind");
+    if (flags & ~(uint32_t)MINA_SUBMIT_MORE) return fail(MINA_ERR_ARG, "unknown submit flag");
+    if ((!proof && proof_len) || (!pub && pub_len)) return fail(MINA_ERR_ARG, "null pointer with a non-zero length");
+    if (proof_len > (1u << 20) || pub_len > (1u << 20)) return fail(MINA_ERR_ARG, "a submission's byte strings are at most 1 MiB each");
+    std::lock_guard<std::mutex> lk(q->mu);
+    if (q->free_list.n == 0) return fail(MINA_ERR_FULL, "the queue is full: take completions first");
+    try {
+        mina_verify_queue::Entry &e = q->slab[q->free_list.head];
+        e.bytes.resize(std::max<size_t>(1, proof_len + pub_len));             // (keeps its capacity: a slot that has held a proof of this size allocates nothing)
+        if (proof_len) memcpy(e.bytes.data(), proof, proof_len);
+        if (pub_len) memcpy(e.bytes.data() + proof_len, pub, pub_len);
+        e.call = PendingCall{e.bytes.data(), proof_len, e.bytes.data() + proof_len, pub_len};
+        e.tag = tag; e.kind = (uint8_t)kind; e.state = mina_verify_queue::Q_PENDING;
+    } catch (...) { return fail(MINA_ERR_STATE, "out of memory"); }             // the slot has not left the free list
+    q->pending[kind].push(q->slab, q->free_list.pop(q->slab));
+    ++q->n_submitted;
+    if (!(flags & MINA_SUBMIT_MORE)) q->release_all();
+    return MINA_OK;
+}
+extern "C" int mina_verify_queue_flush(mina_verify_queue *q) {
+    if (!q) return fail(MINA_ERR_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(q->mu);
+    q->release_all();
+    return MINA_OK;
+}
+extern "C" int mina_verify_queue_poll(mina_verify_queue *q, mina_verify_completion *out, size_t cap, size_t *n_out) {
+    if (!q || !n_out || (!out && cap)) return fail(MINA_ERR_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(q->mu);
+    *n_out = q->take(out, cap);
+    return MINA_OK;
+}
+extern "C" int mina_verify_queue_wait(mina_verify_queue *q, mina_verify_completion *out, size_t cap, size_t *n_out, int64_t timeout_us) {
+    if (!q || !n_out || (!out && cap)) return fail(MINA_ERR_ARG, "null argument");
+    std::unique_lock<std::mutex> lk(q->mu);
+    if (timeout_us < 0) q->done_cv.wait(lk, [&] { return q->completed.n > 0; });
+    else (void)q->done_cv.wait_until(lk, std::chrono::steady_clock::now() + std::chrono::microseconds(timeout_us), [&] { return q->completed.n > 0; });
+    *n_out = q->take(out, cap);
+    return MINA_OK;
+}
+extern "C" int mina_verify_queue_fd(mina_verify_queue *q) { return q ? q->efd : fail(MINA_ERR_ARG, "null argument"); }
+extern "C" int mina_verify_queue_stats(mina_verify_queue *q, uint64_t *submitted, uint64_t *completed, uint64_t *jobs, uint64_t *max_job) {
+    if (!q) return fail(MINA_ERR_ARG, "null argument");
+    std::lock_guard<std::mutex> lk(q->mu);
+    if (submitted) *submitted = q->n_submitted;
+    if (completed) *completed = q->n_completed;
+    if (jobs) *jobs = q->n_jobs;
+    if (max_job) *max_job = q->n_max_job;
+    return MINA_OK;
 }

@@ -48,6 +48,7 @@ EXPORTS = [
     "mina_verify_device_count", "mina_verify_device_ctx", "mina_verify_set_network", "mina_verify_install_verifier_index", "mina_verify_install_step_index", "mina_verify_set_poseidon_params",
     "mina_poseidon_install_default_params",
     "verify_mina_state_ffi", "verify_account_inclusion_ffi", "verify_mina_state_ffi_u32", "verify_account_inclusion_ffi_u32",
+    "mina_verify_queue_create", "mina_verify_queue_destroy", "mina_verify_queue_submit", "mina_verify_queue_flush", "mina_verify_queue_poll", "mina_verify_queue_wait", "mina_verify_queue_fd", "mina_verify_queue_stats",
     "mina_verify_tuning_default", "mina_verify_tuning_get", "mina_verify_configure_ex", "mina_verify_retired_env",
     "mina_consensus_select_secure_chain", "mina_parse_state_pub_inputs", "mina_parse_account_pub_inputs", "mina_parse_merkle_path", "mina_verify_account_inclusion",
 ]
@@ -363,6 +364,117 @@ def verify_account_files(proof_path: str, pub_path: str) -> bool:
     lib = load_library()
     lib.mina_verify_account_files.restype = ctypes.c_bool
     return bool(lib.mina_verify_account_files(proof_path.encode(), pub_path.encode()))
+
+
+QUEUE_STATE, QUEUE_ACCOUNT = 0, 1
+SUBMIT_MORE = 1
+ERR_ARG, ERR_FULL = -1, -5
+
+
+class Completion(ctypes.Structure):
+    _fields_ = [("tag", ctypes.c_uint64), ("rc", ctypes.c_int32), ("verdict", ctypes.c_uint8), ("kind", ctypes.c_uint8), ("pad", ctypes.c_uint8 * 2)]
+
+
+def _queue_lib():
+    lib = load_library()
+    if not getattr(lib, "_queue_typed", False):
+        vp, u32, u64, sz = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_size_t
+        lib.mina_verify_queue_create.argtypes = [u32, u32, ctypes.POINTER(vp)]
+        lib.mina_verify_queue_destroy.argtypes = [vp]; lib.mina_verify_queue_destroy.restype = None
+        lib.mina_verify_queue_submit.argtypes = [vp, u32, vp, sz, vp, sz, u64, u32]
+        lib.mina_verify_queue_flush.argtypes = [vp]
+        lib.mina_verify_queue_poll.argtypes = [vp, ctypes.POINTER(Completion), sz, ctypes.POINTER(sz)]
+        lib.mina_verify_queue_wait.argtypes = [vp, ctypes.POINTER(Completion), sz, ctypes.POINTER(sz), ctypes.c_int64]
+        lib.mina_verify_queue_fd.argtypes = [vp]
+        lib.mina_verify_queue_stats.argtypes = [vp] + [ctypes.POINTER(u64)] * 4
+        lib._queue_typed = True
+    return lib
+
+
+class VerifyQueue:
+    """mina_verify_queue_*: submit serialized proofs from any thread, take the verdicts later (`poll`, `wait`, or when `fileno()` turns readable).  The queue copies the
+    bytes it is given; its `workers` threads feed the same merged jobs `verify_state` / `verify_account` feed, so the verdicts are theirs.  A submission holds one of
+    `capacity` slots until its completion has been handed out: `submit_*` return 0, or ERR_FULL when every slot is held (take completions, then submit again)."""
+
+    def __init__(self, capacity: int = 1024, workers: int = 1):
+        self._lib = _queue_lib()
+        self._h = ctypes.c_void_p()
+        rc = self._lib.mina_verify_queue_create(int(capacity), int(workers), ctypes.byref(self._h))
+        if rc != 0:
+            self._h = None
+            raise MinaError(f"mina_verify_queue_create failed ({rc}): {self._lib.mina_last_error().decode()}")
+        self.capacity = int(capacity)
+        self._buf = (Completion * min(self.capacity, 4096))()
+
+    def submit_raw(self, kind: int, proof_ptr, proof_len: int, pub_ptr, pub_len: int, tag: int, flags: int) -> int:
+        """the C call as it is (pointers as integers or None); returns its code, raises nothing"""
+        return int(self._lib.mina_verify_queue_submit(self._h, int(kind), proof_ptr, int(proof_len), pub_ptr, int(pub_len), int(tag), int(flags)))
+
+    def _submit(self, kind, proof, pub, tag, more):
+        # (the C side copies before it returns: a temporary view of the caller's buffer is enough)
+        p = proof if type(proof) is bytes else bytes(proof)
+        q = pub if type(pub) is bytes else bytes(pub)
+        rc = self.submit_raw(kind, ctypes.cast(ctypes.c_char_p(p), ctypes.c_void_p), len(p), ctypes.cast(ctypes.c_char_p(q), ctypes.c_void_p), len(q), tag, SUBMIT_MORE if more else 0)
+        if rc not in (0, ERR_FULL):
+            raise MinaError(f"mina_verify_queue_submit failed ({rc}): {self._lib.mina_last_error().decode()}")
+        return rc
+
+    def submit_state(self, proof, pub, tag: int, more: bool = False) -> int:
+        return self._submit(QUEUE_STATE, proof, pub, tag, more)
+
+    def submit_account(self, proof, pub, tag: int, more: bool = False) -> int:
+        return self._submit(QUEUE_ACCOUNT, proof, pub, tag, more)
+
+    def flush(self):
+        self._ck(self._lib.mina_verify_queue_flush(self._h), "mina_verify_queue_flush")
+
+    def _ck(self, rc, what):
+        if rc != 0:
+            raise MinaError(f"{what} failed ({rc}): {self._lib.mina_last_error().decode()}")
+
+    def _out(self, n):
+        return [(int(c.tag), int(c.verdict), int(c.rc), int(c.kind)) for c in self._buf[:n]]
+
+    def poll(self, max_items: int | None = None) -> list:
+        """completions available now, as (tag, verdict, rc, kind); never blocks"""
+        cap = len(self._buf) if max_items is None else min(int(max_items), len(self._buf))
+        n = ctypes.c_size_t(0)
+        self._ck(self._lib.mina_verify_queue_poll(self._h, self._buf, cap, ctypes.byref(n)), "mina_verify_queue_poll")
+        return self._out(n.value)
+
+    def wait(self, timeout_us: int = -1, max_items: int | None = None) -> list:
+        """blocks until at least one completion is available or `timeout_us` has passed (negative: for ever); the GIL is released while it waits"""
+        cap = len(self._buf) if max_items is None else min(int(max_items), len(self._buf))
+        n = ctypes.c_size_t(0)
+        self._ck(self._lib.mina_verify_queue_wait(self._h, self._buf, cap, ctypes.byref(n), int(timeout_us)), "mina_verify_queue_wait")
+        return self._out(n.value)
+
+    def fileno(self) -> int:
+        """the queue's eventfd: readable whenever completions are pending (read 8 bytes to clear it, then `poll` until it returns nothing)"""
+        return int(self._lib.mina_verify_queue_fd(self._h))
+
+    def stats(self) -> dict:
+        v = [ctypes.c_uint64(0) for _ in range(4)]
+        self._ck(self._lib.mina_verify_queue_stats(self._h, *[ctypes.byref(x) for x in v]), "mina_verify_queue_stats")
+        return dict(zip(("submitted", "completed", "jobs", "max_job"), (int(x.value) for x in v)))
+
+    def close(self):
+        """runs whatever is still pending, waits for it, discards completions not taken, frees the queue; not while another thread is inside a call on it"""
+        if self._h is not None:
+            self._lib.mina_verify_queue_destroy(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 def account_abi_encode(account: bytes, encoding: int) -> bytes:
