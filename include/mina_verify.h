@@ -176,7 +176,9 @@ int mina_challenge_to_field(mina_ctx *ctx, int field, size_t n, const uint8_t *c
 /* ---- a16: Merkle-path fold of Proof-of-Account (core/src/proof/account_proof.rs:9-14,30-35; README.md:358-362) ------
  * roots[i] = fold of leaves[i] along its path: node <- H_h(node, sib) for dirs = 0 (`MerkleNode::Left(sib)`: the node is
  * the left input) or H_h(sib, node) for dirs = 1 (`MerkleNode::Right(sib)`), h = 0..depth-1, with the per-height salt
- * "MinaMklTree%03d" (mina `hash_with_kimchi`).  depth <= 64.  Runs 4 lanes per path (cooperative Poseidon). */
+ * "MinaMklTree%03d" (mina `hash_with_kimchi`).  depth <= 64.  Cooperative Poseidon in one of three lane forms: 16 lanes
+ * per path while n x the context's pipeline lanes <= mina_verify_tuning.coop16_max (64), 8 lanes per path up to 8192
+ * paths, wave-packed triples (21 paths per wave) above. */
 int mina_merkle_roots(mina_ctx *ctx, int field, size_t n, uint32_t depth, const uint8_t *leaves /* n*32 */,
                       const uint8_t *siblings /* n*depth*32 */, const uint8_t *dirs /* n*depth */, uint8_t *roots_out /* n*32 */);
 /* verdicts[i] = (root of path i == expected_roots[i]) -- the ledger-hash comparison of verify_account_inclusion */

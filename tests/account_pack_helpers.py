@@ -65,6 +65,19 @@ def well_formed_pairs(seed=SEED, ledger_of=None):
     return out
 
 
+def well_formed_pairs_at(depths, ledger_of, seed=SEED):
+    """-> [(name, proof, pub, account, path)] as well_formed_pairs, pair i behind a random path of depths[i]: the accounts above going round.
+    ledger_of(account, path) -> the ledger hash to write (tests/test_gpu_account_forms.py: the CPU model of the fold over the oracle's account hash)"""
+    rng = random.Random(seed + 2)
+    accts = accounts(seed)
+    out = []
+    for i, depth in enumerate(depths):
+        name, a = accts[i % len(accts)]
+        path = random_path(rng, depth)
+        out.append(("%s depth%d" % (name, depth), A.write_account_proof(path, a), pub_input(ledger_of(a, path), A.abi_encode_account(a)), a, path))
+    return out
+
+
 def sweep_values(x):
     return sorted({x ^ 0x01, x ^ 0x80, 0xff} - {x})
 

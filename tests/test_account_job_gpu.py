@@ -3,7 +3,8 @@
 mina_parse_merkle_path / mina_parse_account_pub_inputs / mina_account_abi_encode and the oracle's `to_input` fields (tests/account_pack_helpers.py) -- for
 well-formed pairs of every account shape and depth, for every truncation and byte position of a proof and of a public input in one launch each, for a shuffled
 mixed batch, across a change of Poseidon tables, and through the boundary with the flag off and on.  Every sweep asserts on the checker's output that all four
-outcomes (FORMAT fails; FORMAT passes, ABI fails; ABI passes, MERKLE fails; everything passes) occur."""
+outcomes (FORMAT fails; FORMAT passes, ABI fails; ABI passes, MERKLE fails; everything passes) occur.
+Jobs of more than 8192 pairs and forced lane forms, against the CPU oracle and the CPU model of the fold: tests/test_gpu_account_forms.py."""
 import os
 import random
 import sys

@@ -1,5 +1,6 @@
 """a16 (Proof-of-Account Merkle-path fold, BASELINE config C4 shape: 256 paths of depth 35) and the lane-cooperative
-Poseidon: GPU vs the Python big-int restatement; CPU leg checks the restatement's own structure."""
+Poseidon: GPU vs the Python big-int restatement; CPU leg checks the restatement's own structure.
+The fold in each of its three lane forms, every root compared: tests/test_gpu_merkle_forms.py (reference: tests/merkle_model.py)."""
 import numpy as np
 import pytest
 
