@@ -41,7 +41,8 @@ def install_index(ctx, index):
 
 
 def kimchi_arrays(proofs, publics):
-    """list of oracle proofs (same shape) -> dict of arrays for MinaContext.make_kimchi_proofs + the opening arrays (lr, delta, sg, z1, z2)"""
+    """list of oracle proofs (same shape) -> dict of arrays for MinaContext.make_kimchi_proofs + the opening arrays (lr, delta, sg, z1, z2; None where the
+    proofs carry no opening).  A point may be None (infinity, the encoding (0, 0)); a scalar may be any value below 2^256, a coordinate likewise."""
     from oracle import oracle as O
     cat = lambda xs: np.concatenate(xs)
     a = {
@@ -54,6 +55,8 @@ def kimchi_arrays(proofs, publics):
     }
     if publics and len(publics[0]):
         a["public_inputs"] = cat([O.ints_to_le(pi).reshape(-1) for pi in publics])
+    if proofs[0].get("opening") is None:
+        return a, None
     op = {
         "lr": cat([cat([cat([O.point_to_bytes(L), O.point_to_bytes(R)]) for L, R in p["opening"]["lr"]]) for p in proofs]),
         "delta": cat([O.point_to_bytes(p["opening"]["delta"]) for p in proofs]), "sg": cat([O.point_to_bytes(p["opening"]["sg"]) for p in proofs]),
