@@ -680,6 +680,16 @@ int mina_ctx_inverse_stats(mina_ctx *ctx, uint64_t *gcd_finishes, uint64_t *ferm
  * mina_ctx_chain_inverse_stats: launches of the kernels listed above this context has queued in the divstep form and in the power form since it was created. */
 int mina_ctx_set_chain_inverse(mina_ctx *ctx, int on);       /* default 0; takes effect for the calls queued after it */
 int mina_ctx_chain_inverse_stats(mina_ctx *ctx, uint64_t *gcd_launches, uint64_t *fermat_launches);
+/* Two INDEX SETS per context.  Everything that belongs to an installed (wrap index, step index) pair -- device buffers, digest, commitments, the derived Tick sponge
+ * state -- is one index set; a context holds two, numbered 0 and 1, and one of them is SELECTED (set 0 when the context is created).  Every installer, loader and
+ * getter (mina_verifier_index_install, _load_json, _digest, mina_step_index_install, _load_json, mina_polish_tokens_from_json where it installs) and every job acts on
+ * the selected set; field constants, both SRS with their Lagrange tables, the Poseidon tables and the salts are shared by both.  The boundary keeps one set per Mina
+ * network (mina_verify_install_verifier_index_net).
+ * Selecting is host bookkeeping only: no HIP call, no allocation, no synchronisation; launches already queued keep the buffers they captured.  Installing into a set
+ * frees that set's old buffers -- the hazard of a re-install, with the same remedy.  mina_poseidon_set_params invalidates the table-derived state of BOTH sets.
+ * Like the installers, not to be called while another thread queues work on the context.  set: 0 | 1, MINA_ERR_ARG otherwise. */
+int mina_ctx_select_index_set(mina_ctx *ctx, uint32_t set);
+uint32_t mina_ctx_index_set(const mina_ctx *ctx);
 /* Test-facing: *live = the streams the context's lanes hold now, *made_by_searches = the streams its culprit searches have created since the context was created
  * (the fan search creates the streams its lanes lack and destroys them when it is done; the grouped search creates none and queues on the job's lane only). */
 int mina_ctx_lane_streams(mina_ctx *ctx, uint32_t *live, uint64_t *made_by_searches);
@@ -1124,12 +1134,31 @@ mina_ctx *mina_verify_global_ctx(void);          /* the first device's context, 
  * its proofs into contiguous shards, one per device, each with its own folding randomisers and its own culprit search; merged single-proof
  * jobs are dealt round-robin.  The installers below put the same data on EVERY device. */
 /* which network the installed indexes belong to: 0 = mainnet, 1 = devnet, -1 (default) = not declared.  Once declared, a proof whose public
- * input claims the other network (`is_state_proof_from_devnet`, core/src/proof/state_proof.rs:10-25) fails the kimchi step. */
+ * input claims the other network (`is_state_proof_from_devnet`, core/src/proof/state_proof.rs:10-25) fails the kimchi step.
+ * This is the form for a process that holds ONE index pair.  A process that serves both networks installs a pair per network instead
+ * (mina_verify_install_verifier_index_net / mina_verify_install_step_index_net, below); in that mode this call returns MINA_ERR_STATE and changes nothing. */
 int mina_verify_set_network(int devnet);
 int mina_verify_device_count(void);
 mina_ctx *mina_verify_device_ctx(int i);
 int mina_verify_install_verifier_index(const mina_verifier_index *index);
 int mina_verify_install_step_index(const mina_step_index *index);
+/* An index pair PER NETWORK (the reference verifier picks the devnet or the mainnet blockchain-snark index per proof, by `is_state_proof_from_devnet`).
+ * The `_net` installers write index set `devnet` (0 = mainnet, 1 = devnet; mina_ctx_select_index_set) on EVERY device, under the locks of the installers above.
+ * The first successful one puts the process into NETWORK MODE; mina_verify_drop_network_indexes (which empties both sets) and mina_verify_shutdown end it.
+ * In network mode, for every Proof-of-State entry point (mina_verify_state, _files, _batch, _checks, _checks_batch, verify_mina_state_ffi, the completion queue):
+ *   - a proof's network is the parsed flag of its public input, and its kimchi step runs against the set of that network;
+ *   - if that set lacks what a full configuration needs (a wrap index, plus a step index unless MINA_VERIFY_ALLOW_UNBOUND_STATEMENT), the proof is rejected as a
+ *     wrong-network proof is under mina_verify_set_network: KIMCHI is in `ran` and not in `passed`, CHAIN and ACCUMULATOR keep their own bits, no other verdict changes;
+ *   - the proofs of one call are verified network by network, one pass after the other (the majority network first), as proofs of different evaluation shapes are;
+ *   - mina_verify_set_network, mina_verify_install_verifier_index and mina_verify_install_step_index return MINA_ERR_STATE and change nothing.
+ * A `_net` call while a network is declared (mina_verify_set_network(0 | 1)) returns MINA_ERR_STATE: a process declares one network or installs per network,
+ * never both.  devnet outside {0, 1} or a null index: MINA_ERR_ARG, before any device is touched.  Outside network mode nothing changes.
+ * mina_verify_networks: which networks are ready (1) -- hold a full configuration -- on the first device; (0, 0) outside network mode; either pointer may be NULL.
+ * Proof-of-Account carries no network flag and is not affected. */
+int mina_verify_install_verifier_index_net(int devnet, const mina_verifier_index *index);
+int mina_verify_install_step_index_net(int devnet, const mina_step_index *index);
+int mina_verify_drop_network_indexes(void);
+int mina_verify_networks(int *mainnet_ready, int *devnet_ready);
 int mina_verify_set_poseidon_params(int field, const uint8_t *params /* (9+165)*32 */);
 /* the Poseidon constant set compiled into the library (name contains "UNPINNED" while it is a surrogate for fp_kimchi/fq_kimchi) */
 const char *mina_poseidon_params_name(void);

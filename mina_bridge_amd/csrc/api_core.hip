@@ -88,8 +88,7 @@ extern "C" void mina_ctx_destroy(mina_ctx *c) {
     for (int i = 0; i < MB_DEV_HELPER0; ++i) if (c->lanes[i].stream) (void)hipStreamSynchronize(c->lanes[i].stream);
     for (hipStream_t s : c->fork_own) if (s) (void)hipStreamSynchronize(s);
     for (hipStream_t s : c->role) if (s) (void)hipStreamSynchronize(s);
-    if (c->step_host && c->step_host_free) c->step_host_free(c->step_host);
-    c->step_host = nullptr;
+    c->free_step_host(); c->parked.free_step_host();
     for (auto &r : c->prof.recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
     for (int i = 0; i < MB_MAX_LANES; ++i) {
         Lane &L = c->lanes[i];
@@ -110,6 +109,16 @@ extern "C" void mina_ctx_destroy(mina_ctx *c) {
 // proofs per mina_verify_state_batch call: 4 - 16 queues 54.6 - 56 ms, 24 queues 68.4 ms.  A process that pipelines device-resident jobs
 // itself (bench.py's headline: 4 lanes x 4 streams since round 6; the test-suite) sets 24 -- one queue per stream plus a few; a process should never hold more streams than that.
 __attribute__((constructor)) static void mb_default_hw_queues() { setenv("GPU_MAX_HW_QUEUES", "16", 0); }
+
+// The index set (0 | 1) every installer, loader, getter and job of the context acts on (ctx.h IndexSet).  Host bookkeeping only: no HIP call, no allocation, no
+// synchronisation; launches already queued keep the buffers they captured.  Like an install, not to be called while another thread queues work on the context.
+extern "C" int mina_ctx_select_index_set(mina_ctx *c, uint32_t set) {
+    if (!c) return fail(MINA_ERR_ARG, "null ctx");
+    if (set > 1) return fail(MINA_ERR_ARG, "index set: 0 or 1");
+    c->select_index_set(set);
+    return MINA_OK;
+}
+extern "C" uint32_t mina_ctx_index_set(const mina_ctx *c) { return c ? c->index_set : 0; }
 
 extern "C" int mina_ctx_synchronize(mina_ctx *c) {
     if (!c) return fail(MINA_ERR_ARG, "null ctx");

@@ -291,7 +291,7 @@ extern "C" int mina_poseidon_set_params(mina_ctx *c, int field, const uint8_t *p
     c->pparams_rows1[field] = both.q1.ok != 0;
     c->pparams_surrogate[field] = mb_params_are_surrogate(field, params);
     c->merkle_depth[field] = 0;
-    if (field == FIELD_FP) { c->have_state_salts = false; c->have_acct_defaults = false; }
+    if (field == FIELD_FP) { c->have_state_salts = false; c->have_acct_defaults = false; c->invalidate_table_derived(); }
     return MINA_OK;
 }
 

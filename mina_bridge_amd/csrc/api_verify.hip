@@ -29,6 +29,7 @@
 #include <unistd.h>
 
 #include "ctx.h"
+#include "net_route.h"
 #include "sponge.cuh"
 #include "wire_proof.h"
 #include "poseidon_tables.inc"
@@ -96,6 +97,10 @@ std::mutex g_mu;                           // guards the device list, the flags 
 std::vector<Device *> g_devs; bool g_init_failed = false;
 uint32_t g_flags = 0;
 int g_network = -1;                        // which network the installed indexes belong to: -1 = not declared, 0 = mainnet, 1 = devnet (mina_verify_set_network)
+// NETWORK MODE (mina_verify_install_*_net): index set n of every device's context holds network n's pair (0 = mainnet, 1 = devnet), a proof's network is the flag
+// of its public input and its kimchi step runs against that set (net_route.h).  Entered by the first successful `_net` install, left by
+// mina_verify_drop_network_indexes and mina_verify_shutdown.  Outside it set 0 is the only one in use and stays selected.
+bool g_net_mode = false;
 std::atomic<unsigned> g_rr{0};
 
 int create_device(int ordinal, Device **out) {
@@ -140,10 +145,17 @@ void destroy_devices() {                    // caller holds g_mu
 
 extern "C" int mina_verify_configure(uint32_t flags) { std::lock_guard<std::mutex> lk(g_mu); g_flags = flags; return MINA_OK; }
 // `is_state_proof_from_devnet` of the public input (core/src/proof/state_proof.rs:10-25) selects, upstream, the devnet or the mainnet
-// verifier index.  This library holds ONE index pair: declare which network it belongs to and proofs that claim the other one are rejected
+// verifier index.  A process that holds ONE index pair declares which network it belongs to, and proofs that claim the other one are rejected
 // at the kimchi step (their own verdict only); -1 (the default) = not declared, the flag is not looked at.
-extern "C" int mina_verify_set_network(int devnet) { if (devnet < -1 || devnet > 1) return fail(MINA_ERR_ARG, "network must be -1, 0 or 1"); std::lock_guard<std::mutex> lk(g_mu); g_network = devnet; return MINA_OK; }
-extern "C" int mina_verify_shutdown(void) { std::lock_guard<std::mutex> lk(g_mu); destroy_devices(); return MINA_OK; }
+// A process that serves BOTH networks installs a pair per network instead (mina_verify_install_verifier_index_net / _step_index_net, below): a proof is then
+// verified against the pair of the network its flag names.  The two are exclusive: in network mode this call answers MINA_ERR_STATE and changes nothing.
+extern "C" int mina_verify_set_network(int devnet) {
+    if (devnet < -1 || devnet > 1) return fail(MINA_ERR_ARG, "network must be -1, 0 or 1");
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (g_net_mode) return fail(MINA_ERR_STATE, "indexes are installed per network (mina_verify_install_*_net): no single network to declare");
+    g_network = devnet; return MINA_OK;
+}
+extern "C" int mina_verify_shutdown(void) { std::lock_guard<std::mutex> lk(g_mu); destroy_devices(); g_net_mode = false; return MINA_OK; }
 // the first device's context (a process with one GPU: THE context), e.g. to install a verifier index or other Poseidon tables; NULL if no
 // GPU / set-up failed.  Install before the first verification: installing is not synchronised against calls in flight.
 extern "C" mina_ctx *mina_verify_global_ctx(void) { std::lock_guard<std::mutex> lk(g_mu); auto &d = devices(); return d.empty() ? nullptr : d[0]->c; }
@@ -152,6 +164,7 @@ extern "C" mina_ctx *mina_verify_device_ctx(int i) { std::lock_guard<std::mutex>
 // the same data on EVERY device of the process (what a multi-GPU deployment calls instead of the per-context installers)
 extern "C" int mina_verify_install_verifier_index(const mina_verifier_index *ix) {
     std::lock_guard<std::mutex> lk(g_mu);
+    if (g_net_mode) return fail(MINA_ERR_STATE, "indexes are installed per network: use mina_verify_install_verifier_index_net");
     auto &ds = devices(); if (ds.empty()) return fail(MINA_ERR_HIP, "no device");
     for (Device *d : ds) {
         std::lock_guard<std::mutex> sl(d->search_mu);      // no culprit search is reading the buffers being replaced (lock order: g_mu, search_mu, mu)
@@ -161,11 +174,51 @@ extern "C" int mina_verify_install_verifier_index(const mina_verifier_index *ix)
 }
 extern "C" int mina_verify_install_step_index(const mina_step_index *ix) {
     std::lock_guard<std::mutex> lk(g_mu);
+    if (g_net_mode) return fail(MINA_ERR_STATE, "indexes are installed per network: use mina_verify_install_step_index_net");
     auto &ds = devices(); if (ds.empty()) return fail(MINA_ERR_HIP, "no device");
     for (Device *d : ds) {
         std::lock_guard<std::mutex> sl(d->search_mu);      // no culprit search is reading the buffers being replaced (lock order: g_mu, search_mu, mu)
         std::lock_guard<std::mutex> dl(d->mu); int rc = mina_step_index_install(d->c, ix); if (rc) return rc;
     }
+    return MINA_OK;
+}
+// ---- an index pair PER NETWORK: set `devnet` (0 = mainnet, 1 = devnet) of every device's context.  Same locks, same order as the installers above.
+namespace {
+template <class Install> int install_net(int devnet, Install install) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (g_network != -1) return fail(MINA_ERR_STATE, "a network is declared (mina_verify_set_network): a process declares one network or installs per network, never both");
+    auto &ds = devices(); if (ds.empty()) return fail(MINA_ERR_HIP, "no device");
+    for (Device *d : ds) {
+        std::lock_guard<std::mutex> sl(d->search_mu);      // no culprit search is reading the buffers being replaced (lock order: g_mu, search_mu, mu)
+        std::lock_guard<std::mutex> dl(d->mu);
+        d->c->select_index_set((uint32_t)devnet);
+        int rc = install(d->c); if (rc) return rc; d->prepared_npub = 0xffffffffu;
+    }
+    g_net_mode = true;
+    return MINA_OK;
+}
+}  // namespace
+extern "C" int mina_verify_install_verifier_index_net(int devnet, const mina_verifier_index *ix) {
+    if ((devnet != 0 && devnet != 1) || !ix) return fail(MINA_ERR_ARG, "network must be 0 or 1, the index not null");
+    return install_net(devnet, [ix](mina_ctx *c) { return mina_verifier_index_install(c, ix); });
+}
+extern "C" int mina_verify_install_step_index_net(int devnet, const mina_step_index *ix) {
+    if ((devnet != 0 && devnet != 1) || !ix) return fail(MINA_ERR_ARG, "network must be 0 or 1, the index not null");
+    return install_net(devnet, [ix](mina_ctx *c) { return mina_step_index_install(c, ix); });
+}
+// Leaves network mode: both sets of every device emptied, set 0 selected -- the process is as it was before the first install.
+extern "C" int mina_verify_drop_network_indexes(void) {
+    std::lock_guard<std::mutex> lk(g_mu);
+    if (!g_net_mode) return MINA_OK;
+    for (Device *d : g_devs) {
+        std::lock_guard<std::mutex> sl(d->search_mu);
+        std::lock_guard<std::mutex> dl(d->mu);
+        (void)hipSetDevice(d->c->device);
+        d->sc->select_index_set(0); d->sc->IndexSet::clear(); d->sc->parked.clear();      // the view first: it borrows c's buffers
+        d->c->select_index_set(0); d->c->IndexSet::clear(); d->c->parked.clear();
+        d->prepared_npub = 0xffffffffu;
+    }
+    g_net_mode = false;
     return MINA_OK;
 }
 extern "C" int mina_verify_set_poseidon_params(int field, const uint8_t *params) {
@@ -266,7 +319,10 @@ static inline void launch_words_out(hipStream_t st, uint32_t words, const uint32
 //   inside); up to four chunks are on the GPU at a time, verdict words come back through page-locked memory.  No per-call allocation, no gather
 //   copy.  A chunk whose folded check fails goes through the culprit search of mina_state_job_batch from the same staging.
 namespace {
-struct Shape { bool kimchi = false, statements = false, feature_aware = false; uint32_t k = 0, n_prev = 2, n_old = 0, n_ev = 0; int network = -1; };
+// network: the DECLARED network (legacy mode; -1 = none).  net_mode / set / ready: network mode -- the job serves index set `set` (= the network of its proofs), and
+// ready[n] says whether set n holds a full configuration (net_route.h); outside network mode set = 0.
+struct Shape { bool kimchi = false, statements = false, feature_aware = false; uint32_t k = 0, n_prev = 2, n_old = 0, n_ev = 0; int network = -1;
+               bool net_mode = false; int set = 0; bool ready[2] = {false, false}; };
 enum Sec : int { S_REC = 0, S_NF, S_EXP, S_PRE, S_APRE, S_ASG, S_ARHO, S_LR, S_DELTA, S_SG, S_Z1, S_Z2, S_PCM, S_WC, S_ZC, S_TC, S_EV, S_FT1, S_PCH,
                  S_PLONK, S_BP, S_OLD, S_CM, S_WOLD, S_WSG, S_DG, S_SEV, S_PI, S_SFT, S_APP, S_MISC, S_RB, S_SB, NSEC };
 struct Layout {
@@ -342,9 +398,12 @@ void parse_proof_half(const Shape &sh, const Layout &lay, uint8_t *base, size_t 
     if (sh.kimchi) {
         // the wrap proof must have the shape of the installed index: k rounds, n_prev step-side accumulators, no lookup features; a well-formed
         // proof of another evaluation / recursion shape is verified in a job of its own (`deferred`), a malformed one fails here
+        // (network mode: a proof of the OTHER network, when that network's set is ready, has a pass of its own as well -- against that set; net_route.h)
         const size_t n_old = w.step_old_bulletproof_challenges.size(), n_ev = w.prev_evals.size();
-        if (w.lr.size() != sh.k || w.step_challenge_polynomial_commitments.size() != sh.n_prev || (uses_lookups(w) && !sh.feature_aware) || n_old > 4 || n_ev < 43 || n_ev > 62 ||
-            w.prev_public_input.zeta.empty() || w.prev_public_input.zeta_omega.empty() || (sh.network >= 0 && (int)pi.is_state_proof_from_devnet != sh.network)) hb.shape = 0;
+        const mb::NetRoute rt = mb::net_route(sh.net_mode ? mb::NET_NETWORK : mb::NET_LEGACY, sh.network, sh.ready, (int)pi.is_state_proof_from_devnet);
+        if (!rt.reject && rt.set != sh.set) { hb.shape = 0; hb.deferred = 1; }
+        else if (w.lr.size() != sh.k || w.step_challenge_polynomial_commitments.size() != sh.n_prev || (uses_lookups(w) && !sh.feature_aware) || n_old > 4 || n_ev < 43 || n_ev > 62 ||
+            w.prev_public_input.zeta.empty() || w.prev_public_input.zeta_omega.empty() || rt.reject) hb.shape = 0;
         else if (sh.statements && (n_old != sh.n_old || n_ev != sh.n_ev)) { hb.shape = 0; hb.deferred = 1; }
     }
     if (sh.kimchi && hb.shape) {
@@ -489,12 +548,14 @@ void copy_proof_half(const Layout &lay, uint8_t *base, size_t dst, size_t src) {
 }
 void clear_states_half(const Layout &lay, uint8_t *base, size_t b) { memset(lay.at(base, S_REC, b), 0, lay.stride[S_REC]); memset(lay.at(base, S_NF, b), 0, lay.stride[S_NF]); *lay.at(base, S_PRE, b) = 0; }
 
-struct Config { bool usable = false, kimchi = false, statements = false, feature_aware = false; uint32_t k = 0; int network = -1; };
+struct Config { bool usable = false, kimchi = false, statements = false, feature_aware = false; uint32_t k = 0; int network = -1; int set = 0; };
 // Lock order everywhere: g_mu, then a device's mu.  `network` (and `flags`) are copied under g_mu by the caller BEFORE this takes D.mu -- the
 // installers hold g_mu while they take every D.mu, so taking g_mu in here would invert the order (a job and an install in flight: deadlock).
-Config read_config(Device &D, uint32_t flags, int network) {
+// `set`: the index set the configuration is read from; it is left selected (whoever queues a job selects its own set first, under D.mu: queue sites below).
+Config read_config(Device &D, uint32_t flags, int network, int set = 0) {
     std::lock_guard<std::mutex> lk(D.mu);
     mina_ctx *c = D.c; Config cf;
+    c->select_index_set((uint32_t)set); cf.set = set;
     // a deployment on the library's surrogate Poseidon tables agrees with nothing on the Mina network: refuse unless the caller said so
     const bool surrogate = c->pparams_surrogate[0] || c->pparams_surrogate[1];
     cf.usable = !surrogate || (flags & MINA_VERIFY_ALLOW_SURROGATE);
@@ -509,8 +570,23 @@ Config read_config(Device &D, uint32_t flags, int network) {
 }
 
 Shape shape_of_config(const Config &cf) {      // what the installed indexes say of a job's shape (n_old / n_ev: the proofs')
-    Shape sh; sh.kimchi = cf.kimchi; sh.statements = cf.kimchi && cf.statements; sh.k = cf.k; sh.network = cf.network; sh.feature_aware = cf.feature_aware;
+    Shape sh; sh.kimchi = cf.kimchi; sh.statements = cf.kimchi && cf.statements; sh.k = cf.k; sh.network = cf.network; sh.feature_aware = cf.feature_aware; sh.set = cf.set;
     return sh;
+}
+// Network mode: the configurations of both sets of a device, and which of them are READY -- hold what a full configuration needs (a wrap index, plus a step index
+// unless MINA_VERIFY_ALLOW_UNBOUND_STATEMENT: Config::kimchi).  serve(n): the Shape of a job that serves network n.
+struct NetConfigs {
+    Config cf[2]; bool ready[2] = {false, false};
+    void read(Device &D, uint32_t flags) { for (int n = 0; n < 2; ++n) { cf[n] = read_config(D, flags, -1, n); ready[n] = cf[n].kimchi; } }
+    Shape serve(int n) const { Shape sh = shape_of_config(cf[n]); sh.net_mode = true; sh.ready[0] = ready[0]; sh.ready[1] = ready[1]; return sh; }
+    // the set a proof's job runs against: its network's when ready; a proof of a network that is not ready fails the kimchi step in a job of a ready one
+    int set_for(int flag) const { const mb::NetRoute rt = mb::net_route(mb::NET_NETWORK, -1, ready, flag); return !rt.reject ? rt.set : (ready[0] ? 0 : (ready[1] ? 1 : (flag ? 1 : 0))); }
+};
+// the network flag of a serialized public input; -1 where it does not parse
+int pub_network(const uint8_t *pub, size_t pub_len) {
+    mina_state_pub_inputs pi;
+    if (!pub || mina_parse_state_pub_inputs(pub, pub_len, &pi) != MINA_OK) return -1;
+    return pi.is_state_proof_from_devnet ? 1 : 0;
 }
 struct CallIn { const uint8_t *const *proofs; const size_t *proof_lens; const uint8_t *const *pubs; const size_t *pub_lens; };
 
@@ -540,7 +616,7 @@ const bool g_timing = getenv("MINA_VERIFY_TIMING") != nullptr;
 double ms_since(std::chrono::steady_clock::time_point t) { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t).count(); }
 
 // what a caller of the pipeline copied under g_mu (lock order: g_mu before any D.mu) + the tuning of the call
-struct CallEnv { uint32_t flags = 0; int network = -1; mina_verify_tuning tu; };
+struct CallEnv { uint32_t flags = 0; int network = -1; bool net_mode = false; mina_verify_tuning tu; };
 
 // evaluation / recursion shape of the job over the proofs idx[..] of a call (Mina's blockchain proofs all share one): the most frequent shape among up to 9
 // proofs spread over the call -- one odd-shaped proof at the head of a merged job must not send every other caller's proof through a second job --
@@ -575,14 +651,14 @@ bool vote_shape(const CallIn &in, const std::vector<size_t> &idx, Shape &sh) {
 // the job's SHAPE is vote_shape's.  The pool's jobs hold `this` and a Chunk *: `chunks` is sized once, before the first of them is submitted.
 struct ShapePass {
     Device &D; const CallIn &in; const std::vector<size_t> &idx; uint8_t *const verdicts; std::vector<size_t> &deferred;
-    const uint32_t flags; const int network; const mina_verify_tuning &tu; const size_t m; mina_ctx *const c;
+    const uint32_t flags; const int network; const bool net_mode; const mina_verify_tuning &tu; const size_t m; mina_ctx *const c;
     const std::chrono::steady_clock::time_point t_call = std::chrono::steady_clock::now();
     const size_t chunk_target, single_max, nchunks; const double pace_ms; const size_t head_min; const int nslot; const size_t ahead, window, early_min, early_sub; const bool own_up, pack;
     const HashLaunch hash_launch; std::vector<Chunk> chunks;
     Shape sh; uint32_t prep_key = 0; Layout lay; int rc_all = MINA_OK;
 
     ShapePass(Device &D_, const CallIn &in_, const std::vector<size_t> &idx_, uint8_t *verdicts_, const CallEnv &env, std::vector<size_t> &deferred_)
-        : D(D_), in(in_), idx(idx_), verdicts(verdicts_), deferred(deferred_), flags(env.flags), network(env.network), tu(env.tu), m(idx_.size()), c(D_.c),
+        : D(D_), in(in_), idx(idx_), verdicts(verdicts_), deferred(deferred_), flags(env.flags), network(env.network), net_mode(env.net_mode), tu(env.tu), m(idx_.size()), c(D_.c),
           // read per call (tests force tiny chunks / shards to drive the pipeline's slot recycling with a handful of proofs)
           // Measured on one MI355X (tools/boundary_sweep.sh, bench.py --boundary-only): 8192 full-size proofs as ONE chunk 55 - 58 ms, 2 x 4096: 74 ms,
           // 8 x 1024: 87 ms, 16 x 512: 92 ms -- a job is a ~30 ms dependent chain of small kernels whatever its size, and jobs that start together do
@@ -764,6 +840,7 @@ struct ShapePass {
     }
     // a phase of the chunk's job, over the device staging, on the chunk's lane (the caller made it the current one)
     int queue_job(Chunk &ch, uint32_t phase) {
+        c->select_index_set((uint32_t)sh.set);                        // network mode: the pass's set, per job (the caller holds D.mu); otherwise set 0, which is selected already
         JobStructs js; make_jobs(sh, lay, ch.slot->dev.as<uint8_t>(), ch.n, true, true, true, js);
         uint32_t *dv = verdict_words(ch), *df = dv + ch.n, *ds = df + 4;
         const int rc = mb_state_jobs_on_lane(c, &js.j, dv, df, chunk_plan(ch, phase, ds));
@@ -902,6 +979,7 @@ struct ShapePass {
         std::vector<uint8_t> v(ch.n, 0);
         // (under X's lock)  The flag asks for groups of 64 for THIS search; without it the context keeps whatever its owner set (mina_ctx_set_search_groups on the device's context)
         auto search_job = [&]() {
+            X->select_index_set((uint32_t)sh.set);                    // the failed pass's set, on the view (its own selection) or on `c` (under D.mu)
             if (!from_dev) return mina_state_job_batch(X, &js.j, v.data());
             const uint32_t keep = X->search_groups;
             X->search_groups = 64u;
@@ -978,11 +1056,22 @@ struct ShapePass {
         deferred.clear();
         for (size_t i = 0; i < m; ++i) verdicts[idx[i]] = 0;
         if (m == 0) return MINA_OK;
-        const Config cf = read_config(D, flags, network);
+        Config cf; std::vector<size_t> mine;                           // mine: network mode -- the proofs this pass serves (the shape vote is theirs)
+        if (net_mode) {
+            // ONE network per pass: the one most proofs of the pass claim, among the networks whose set is ready (a proof of a network that is not ready fails the
+            // kimchi step in whichever pass it meets); well-formed proofs of the other ready network leave through `deferred`, as those of another shape do
+            NetConfigs nc; nc.read(D, flags);
+            std::vector<int> net(m);
+            mb_parallel_for(m, [&](size_t i) { const int f = pub_network(in.pubs[idx[i]], in.pub_lens[idx[i]]); net[i] = f < 0 ? -1 : nc.set_for(f); });
+            size_t votes[2] = {0, 0};
+            for (size_t i = 0; i < m; ++i) if (net[i] >= 0) ++votes[net[i]];
+            const int serve = (votes[0] || votes[1]) ? (votes[1] > votes[0] ? 1 : 0) : nc.set_for(0);
+            cf = nc.cf[serve]; sh = nc.serve(serve);
+            for (size_t i = 0; i < m; ++i) if (net[i] == serve) mine.push_back(idx[i]);
+        } else { cf = read_config(D, flags, network); sh = shape_of_config(cf); }
         if (!cf.usable) return MINA_OK;
         if (!cf.kimchi && !(flags & MINA_VERIFY_ALLOW_MISSING_KIMCHI)) return MINA_OK;          // the kimchi step cannot run: nothing can pass
-        sh = shape_of_config(cf);
-        if (sh.statements && !vote_shape(in, idx, sh)) return MINA_OK;                          // nothing parses
+        if (sh.statements && !vote_shape(in, net_mode ? mine : idx, sh)) return MINA_OK;        // nothing parses
         prep_key = ((sh.k ? sh.k : 15u) << 16) | (sh.statements ? 40u : 0u);          // the Lagrange table belongs to (domain, npub): another index -> prepare again
         for (size_t q = 0; q < nchunks; ++q) { chunks[q].lo = m * q / nchunks; chunks[q].n = m * (q + 1) / nchunks - chunks[q].lo; chunks[q].hb.resize(chunks[q].n); }
         lay.build(sh, (m + nchunks - 1) / nchunks);
@@ -1046,7 +1135,7 @@ int run_device(Device &D, const CallIn &in, const std::vector<size_t> &idx, uint
 // n proofs over the devices of the process: contiguous shards, one host thread per extra device
 int verify_state_many(const CallIn &in, size_t n, uint8_t *verdicts) {
     std::vector<Device *> devs; CallEnv env;
-    { std::lock_guard<std::mutex> lk(g_mu); devs = devices(); env.flags = g_flags; env.network = g_network; }
+    { std::lock_guard<std::mutex> lk(g_mu); devs = devices(); env.flags = g_flags; env.network = g_network; env.net_mode = g_net_mode; }
     env.tu = mb_tune();
     for (size_t i = 0; i < n; ++i) verdicts[i] = 0;
     if (devs.empty()) return MINA_ERR_HIP;
@@ -1073,10 +1162,14 @@ int verify_state_many(const CallIn &in, size_t n, uint8_t *verdicts) {
 
 // single-proof diagnostic form: one job per step so that every step gets its own bit
 int state_checks(const uint8_t *proof, size_t proof_len, const uint8_t *pub, size_t pub_len, uint32_t *passed_out, uint32_t *ran_out) {
-    Device *D; uint32_t flags; int network;
-    { std::lock_guard<std::mutex> lk(g_mu); auto &ds = devices(); if (ds.empty()) return MINA_ERR_HIP; D = ds[0]; flags = g_flags; network = g_network; }
-    const Config cf = read_config(*D, flags | MINA_VERIFY_ALLOW_SURROGATE, network);
-    Shape sh = shape_of_config(cf);
+    Device *D; uint32_t flags; int network; bool net_mode;
+    { std::lock_guard<std::mutex> lk(g_mu); auto &ds = devices(); if (ds.empty()) return MINA_ERR_HIP; D = ds[0]; flags = g_flags; network = g_network; net_mode = g_net_mode; }
+    Shape sh;
+    if (net_mode) {       // against the set of the proof's own network (net_route.h); a proof whose public input does not parse fails FORMAT whatever the set
+        NetConfigs nc; nc.read(*D, flags | MINA_VERIFY_ALLOW_SURROGATE);
+        const int f = pub_network(pub, pub_len);
+        sh = nc.serve(nc.set_for(f < 0 ? 0 : f));
+    } else sh = shape_of_config(read_config(*D, flags | MINA_VERIFY_ALLOW_SURROGATE, network));
     uint32_t passed = 0, ran = MINA_CHECK_FORMAT;
     *passed_out = 0; *ran_out = ran;
     if (sh.statements) {
@@ -1125,6 +1218,7 @@ int state_checks(const uint8_t *proof, size_t proof_len, const uint8_t *pub, siz
     if (!draw_randomisers(sh, lay, stage.data(), 1)) return fail(MINA_ERR_STATE, "no entropy for the folding randomisers");
     std::lock_guard<std::mutex> lk(D->mu);
     mina_ctx *c = D->c;
+    c->select_index_set((uint32_t)sh.set);
     auto leg = [&](bool st, bool acc, bool kim, uint32_t bit, bool extra_ok) -> int {
         JobStructs js; make_jobs(sh, lay, stage.data(), 1, st, acc, kim, js);
         uint8_t v = 0;
@@ -1220,6 +1314,7 @@ int checks_chunk(Device &D, uint32_t flags, const Shape &sh, const CallIn &in, c
         } else
             HIPC(hipMemcpyAsync(dbase, stage, lay.total, hipMemcpyHostToDevice, L.stream));
         JobStructs js; make_jobs(sh, lay, dbase, m, true, true, with_kimchi, js);
+        c->select_index_set((uint32_t)sh.set);
         const uint32_t keep = c->search_groups;
         if (flags & MINA_VERIFY_GROUPED_SEARCH) c->search_groups = 64u;  // as the pipeline's fallback searches under the flag
         rc = c->state_job_checks(c, &js.j, d_front, pack ? nullptr : front.data(), deny.data(), passed.data(), ran.data());
@@ -1235,31 +1330,38 @@ int checks_chunk(Device &D, uint32_t flags, const Shape &sh, const CallIn &in, c
 
 int state_checks_batch(const CallIn &in, size_t n, uint32_t *passed_out, uint32_t *ran_out) {
     if (n == 0) return MINA_OK;
-    Device *D; uint32_t flags; int network;
-    { std::lock_guard<std::mutex> lk(g_mu); auto &ds = devices(); if (ds.empty()) return MINA_ERR_HIP; D = ds[0]; flags = g_flags; network = g_network; }
+    Device *D; uint32_t flags; int network; bool net_mode;
+    { std::lock_guard<std::mutex> lk(g_mu); auto &ds = devices(); if (ds.empty()) return MINA_ERR_HIP; D = ds[0]; flags = g_flags; network = g_network; net_mode = g_net_mode; }
     for (size_t i = 0; i < n; ++i) { passed_out[i] = 0; ran_out[i] = MINA_CHECK_FORMAT; }
     if (!D->c->state_job_checks) {                                      // a context that links no kernel: proof by proof, correct by definition
         for (size_t i = 0; i < n; ++i) if (int rc = state_checks(in.proofs[i], in.proof_lens[i], in.pubs[i], in.pub_lens[i], &passed_out[i], &ran_out[i])) return rc;
         return MINA_OK;
     }
-    const Config cf = read_config(*D, flags | MINA_VERIFY_ALLOW_SURROGATE, network);
-    const Shape sh0 = shape_of_config(cf);
+    // sh0[s]: the job shape of index set s.  Outside network mode there is one, set 0's; in network mode a pair belongs to the set of its own network (net_route.h),
+    // so the groups are by evaluation shape AND network
+    Shape sh0[2];
+    NetConfigs nc;
+    if (net_mode) { nc.read(*D, flags | MINA_VERIFY_ALLOW_SURROGATE); sh0[0] = nc.serve(0); sh0[1] = nc.serve(1); }
+    else sh0[0] = shape_of_config(read_config(*D, flags | MINA_VERIFY_ALLOW_SURROGATE, network));
     // the evaluation shape of every pair, as the single-proof form derives it; a pair whose wrap proof does not read keeps (0, FORMAT)
     std::vector<uint32_t> key(n, 0);
-    if (sh0.statements)
-        mb_parallel_for(n, [&](size_t i) {
-            mw::StateProofContainer &box = tl_box();
-            mw::Bincode cur(in.proofs[i], in.proofs[i] ? in.proof_lens[i] : 0);
-            if (!in.proofs[i] || !mw::read_wrap_proof(cur, box.tip_proof)) { key[i] = 0xffffffffu; return; }
-            const uint32_t n_old = (uint32_t)std::min<size_t>(box.tip_proof.step_old_bulletproof_challenges.size(), 4), n_ev = (uint32_t)std::min<size_t>(std::max<size_t>(box.tip_proof.prev_evals.size(), 43), 62);
-            key[i] = n_old << 8 | n_ev;
-        });
+    mb_parallel_for(n, [&](size_t i) {
+        uint32_t set = 0;
+        if (net_mode) { const int f = pub_network(in.pubs[i], in.pub_lens[i]); set = (uint32_t)nc.set_for(f < 0 ? 0 : f); }
+        key[i] = set << 16;
+        if (!sh0[set].statements) return;
+        mw::StateProofContainer &box = tl_box();
+        mw::Bincode cur(in.proofs[i], in.proofs[i] ? in.proof_lens[i] : 0);
+        if (!in.proofs[i] || !mw::read_wrap_proof(cur, box.tip_proof)) { key[i] = 0xffffffffu; return; }
+        const uint32_t n_old = (uint32_t)std::min<size_t>(box.tip_proof.step_old_bulletproof_challenges.size(), 4), n_ev = (uint32_t)std::min<size_t>(std::max<size_t>(box.tip_proof.prev_evals.size(), 43), 62);
+        key[i] |= n_old << 8 | n_ev;
+    });
     std::map<uint32_t, std::vector<size_t>> groups;
     for (size_t i = 0; i < n; ++i) if (key[i] != 0xffffffffu) groups[key[i]].push_back(i);
     const size_t chunk = std::min<size_t>(std::max<size_t>(1, mb_tune().chunk), 65536);
     for (const auto &g : groups) {
-        Shape sh = sh0;
-        if (sh0.statements) { sh.n_old = g.first >> 8; sh.n_ev = g.first & 0xffu; }
+        Shape sh = sh0[g.first >> 16];
+        if (sh.statements) { sh.n_old = (g.first >> 8) & 0xffu; sh.n_ev = g.first & 0xffu; }
         for (size_t lo = 0; lo < g.second.size(); lo += chunk)
             if (int rc = checks_chunk(*D, flags, sh, in, g.second.data() + lo, std::min(chunk, g.second.size() - lo), passed_out, ran_out)) return rc;
     }
@@ -1267,6 +1369,16 @@ int state_checks_batch(const CallIn &in, size_t n, uint32_t *passed_out, uint32_
 }
 }  // namespace
 
+// which networks a proof can pass for: set n is ready when it holds what a full configuration needs (device 0's; the installers write every device).  (0, 0) outside network mode.
+extern "C" int mina_verify_networks(int *mainnet_ready, int *devnet_ready) {
+    Device *D; uint32_t flags; bool net_mode;
+    { std::lock_guard<std::mutex> lk(g_mu); net_mode = g_net_mode; D = (net_mode && !g_devs.empty()) ? g_devs[0] : nullptr; flags = g_flags; }
+    NetConfigs nc;
+    if (D) nc.read(*D, flags);
+    if (mainnet_ready) *mainnet_ready = nc.ready[0] ? 1 : 0;
+    if (devnet_ready) *devnet_ready = nc.ready[1] ? 1 : 0;
+    return MINA_OK;
+}
 extern "C" int mina_verify_state_checks(const uint8_t *proof, size_t proof_len, const uint8_t *pub, size_t pub_len, uint32_t *passed_mask, uint32_t *ran_mask) {
     if (!passed_mask || !ran_mask) return fail(MINA_ERR_ARG, "null argument");
     return state_checks(proof, proof_len, pub, pub_len, passed_mask, ran_mask);

@@ -55,6 +55,7 @@ struct DevBuf {
     }
     void release() { if (p && !borrowed) (void)hipFree(p); p = nullptr; cap = 0; borrowed = false; }
     void alias(const DevBuf &o) { release(); p = o.p; cap = o.cap; borrowed = o.p != nullptr; }
+    void swap(DevBuf &o) { std::swap(p, o.p); std::swap(cap, o.cap); std::swap(borrowed, o.borrowed); }   // the two handles change places; nothing is allocated or freed
     template <class T> T *as() { return reinterpret_cast<T *>(p); }
 };
 
@@ -212,27 +213,23 @@ static constexpr int MB_DEV_HELPER0 = MB_PIPE_LANES + 3 * 16;   // helper lanes 
 static constexpr int MB_MAX_LANES = MB_DEV_HELPER0 + 3 * MB_DEV_FORK_MAX;  // pipeline lanes + the helper lanes of the boundary's 16 slots (api_verify.hip: legs of slot s on lanes 32 + 3 s ..) + those of the forked device-resident jobs
 enum : int { MB_SALT_PSTATE_BODY = 0, MB_SALT_PSTATE, MB_SALT_ACCOUNT, MB_SALT_ZKAPP_ACCOUNT, MB_SALT_ZKAPP_URI, MB_SALT_SIDE_LOADED_VK, MB_N_PREFIX_SALTS };
 
-// Everything INSTALLED on a context: what a view context borrows from its parent -- borrow_from, directly under the fields it must stay in step with.
-struct Installed {
-    FieldK fk[2];
-    SrsState srs[2];
-    DevBuf pparams[2]; bool have_pparams[2] = {false, false};
-    bool pparams_surrogate[2] = {false, false};                  // the installed Poseidon tables are the library's UNPINNED surrogate set
-    bool pparams_rows1[2] = {false, false};                      // the installed tables have the single-lane form's normalised rows (sponge.cuh PoseidonRows1: no zero on the MDS diagonal)
-    DevBuf merkle_salts[2]; uint32_t merkle_depth[2] = {0, 0};   // salted initial states of the Merkle hash per height
+// An INDEX SET: everything that belongs to one installed (wrap index, step index) pair.  A context holds two, numbered 0 and 1 -- the boundary keeps one per Mina
+// network (api_verify.hip, net_route.h) -- and one of them is SELECTED: its fields are the ones below, inherited by Installed under their old names, so that every
+// installer, getter and launch site reads the selected set without knowing of the other, which is parked beside them (Installed::parked).
+struct IndexSet {
     DevBuf kimchi_index, kimchi_tokens, kimchi_literals; bool have_kimchi = false; uint32_t kimchi_log2 = 0; uint8_t kimchi_digest[32] = {0};   // installed wrap verifier index
     uint8_t kimchi_comms_host[28 * 64] = {0};   // its commitments as installed: sigma 7, coefficients 15, selectors 6 (messages_for_next_step_proof hashes them)
     DevBuf pickles_index, pickles_tokens, pickles_literals; bool have_pickles_dev = false, pickles_ms_valid = false;   // installed step index (api_pickles.hip); ms = the Tick sponge after the wrap index commitments
     void *step_host = nullptr; void (*step_host_free)(void *) = nullptr;   // host half of the installed step index (api_pickles.hip), owned by the context
-    DevBuf state_salts; bool have_state_salts = false;           // salted initial states of the named hash prefixes (Fp): MB_SALT_*
-    inline void borrow_from(const Installed &p) {
-        Installed *const v = this;
-        for (int i = 0; i < 2; ++i) {
-            v->fk[i] = p.fk[i];
-            v->srs[i].borrow_from(p.srs[i]);
-            v->pparams[i].alias(p.pparams[i]); v->have_pparams[i] = p.have_pparams[i]; v->pparams_surrogate[i] = p.pparams_surrogate[i]; v->pparams_rows1[i] = p.pparams_rows1[i];
-            v->merkle_salts[i].alias(p.merkle_salts[i]); v->merkle_depth[i] = p.merkle_depth[i];
-        }
+    inline void swap_set(IndexSet &o) {          // handles and host fields change places: no HIP call, no allocation; launches already queued keep the pointers they captured
+        kimchi_index.swap(o.kimchi_index); kimchi_tokens.swap(o.kimchi_tokens); kimchi_literals.swap(o.kimchi_literals);
+        std::swap(have_kimchi, o.have_kimchi); std::swap(kimchi_log2, o.kimchi_log2); std::swap(kimchi_digest, o.kimchi_digest); std::swap(kimchi_comms_host, o.kimchi_comms_host);
+        pickles_index.swap(o.pickles_index); pickles_tokens.swap(o.pickles_tokens); pickles_literals.swap(o.pickles_literals);
+        std::swap(have_pickles_dev, o.have_pickles_dev); std::swap(pickles_ms_valid, o.pickles_ms_valid);
+        std::swap(step_host, o.step_host); std::swap(step_host_free, o.step_host_free);
+    }
+    inline void borrow_set(const IndexSet &p) {  // a view context's: the buffers aliased, the host half borrowed
+        IndexSet *const v = this;
         v->kimchi_index.alias(p.kimchi_index); v->kimchi_tokens.alias(p.kimchi_tokens); v->kimchi_literals.alias(p.kimchi_literals);
         v->have_kimchi = p.have_kimchi; v->kimchi_log2 = p.kimchi_log2; memcpy(v->kimchi_digest, p.kimchi_digest, sizeof v->kimchi_digest); memcpy(v->kimchi_comms_host, p.kimchi_comms_host, sizeof v->kimchi_comms_host);
         v->pickles_index.alias(p.pickles_index); v->pickles_tokens.alias(p.pickles_tokens); v->pickles_literals.alias(p.pickles_literals);
@@ -240,6 +237,42 @@ struct Installed {
         // borrowed: the parent frees it.  A host half the view had built for itself (step_of(view) before the parent had one) is freed first (it leaked)
         if (v->step_host && v->step_host_free && v->step_host != p.step_host) v->step_host_free(v->step_host);
         v->step_host = p.step_host; v->step_host_free = nullptr;
+    }
+    inline void free_step_host() { if (step_host && step_host_free) step_host_free(step_host); step_host = nullptr; step_host_free = nullptr; }
+    inline void clear() {                        // back to "nothing installed": the buffers freed; the hazard and the locking are an install's
+        kimchi_index.release(); kimchi_tokens.release(); kimchi_literals.release(); pickles_index.release(); pickles_tokens.release(); pickles_literals.release();
+        have_kimchi = false; kimchi_log2 = 0; memset(kimchi_digest, 0, sizeof kimchi_digest); memset(kimchi_comms_host, 0, sizeof kimchi_comms_host);
+        have_pickles_dev = false; pickles_ms_valid = false;
+        free_step_host();
+    }
+};
+
+// Everything INSTALLED on a context: what a view context borrows from its parent -- borrow_from, directly under the fields it must stay in step with.
+// The two index sets are per pair; everything else -- field constants, both SRS and their Lagrange tables, Poseidon tables, salts -- is shared by both.
+struct Installed : IndexSet {
+    FieldK fk[2];
+    SrsState srs[2];
+    DevBuf pparams[2]; bool have_pparams[2] = {false, false};
+    bool pparams_surrogate[2] = {false, false};                  // the installed Poseidon tables are the library's UNPINNED surrogate set
+    bool pparams_rows1[2] = {false, false};                      // the installed tables have the single-lane form's normalised rows (sponge.cuh PoseidonRows1: no zero on the MDS diagonal)
+    DevBuf merkle_salts[2]; uint32_t merkle_depth[2] = {0, 0};   // salted initial states of the Merkle hash per height
+    IndexSet parked; uint32_t index_set = 0;                     // the index set that is NOT selected, and the number (0 | 1) of the one that is (mina_ctx_select_index_set)
+    DevBuf state_salts; bool have_state_salts = false;           // salted initial states of the named hash prefixes (Fp): MB_SALT_*
+    inline IndexSet &set_at(uint32_t k) { return k == index_set ? static_cast<IndexSet &>(*this) : parked; }
+    inline const IndexSet &set_at(uint32_t k) const { return k == index_set ? static_cast<const IndexSet &>(*this) : parked; }
+    // Host bookkeeping only: no HIP call, no allocation, no synchronisation.  The caller holds whatever serialises installs and jobs on the context.
+    inline void select_index_set(uint32_t k) { if (k != index_set) { swap_set(parked); index_set = k; } }
+    // what the Poseidon tables of Fp went into, in BOTH sets: the Tick sponge after the wrap index commitments (mina_poseidon_set_params)
+    inline void invalidate_table_derived() { pickles_ms_valid = false; parked.pickles_ms_valid = false; }
+    inline void borrow_from(const Installed &p) {                // set k of the view borrows set k of the parent; the view keeps its own selection
+        Installed *const v = this;
+        for (int i = 0; i < 2; ++i) {
+            v->fk[i] = p.fk[i];
+            v->srs[i].borrow_from(p.srs[i]);
+            v->pparams[i].alias(p.pparams[i]); v->have_pparams[i] = p.have_pparams[i]; v->pparams_surrogate[i] = p.pparams_surrogate[i]; v->pparams_rows1[i] = p.pparams_rows1[i];
+            v->merkle_salts[i].alias(p.merkle_salts[i]); v->merkle_depth[i] = p.merkle_depth[i];
+        }
+        for (uint32_t k = 0; k < 2; ++k) v->set_at(k).borrow_set(p.set_at(k));
         v->state_salts.alias(p.state_salts); v->have_state_salts = p.have_state_salts;
     }
 };

@@ -46,6 +46,7 @@ EXPORTS = [
     "mina_verify_state", "mina_verify_state_batch", "mina_verify_state_checks", "mina_verify_state_checks_batch", "mina_verify_state_files", "mina_verify_account", "mina_verify_account_batch",
     "mina_verify_account_files", "mina_verify_account_checks", "mina_verify_account_ctx", "mina_account_hash_batch", "mina_account_abi_encode", "mina_verify_configure", "mina_verify_shutdown", "mina_verify_global_ctx", "mina_poseidon_params_name",
     "mina_verify_device_count", "mina_verify_device_ctx", "mina_verify_set_network", "mina_verify_install_verifier_index", "mina_verify_install_step_index", "mina_verify_set_poseidon_params",
+    "mina_verify_install_verifier_index_net", "mina_verify_install_step_index_net", "mina_verify_drop_network_indexes", "mina_verify_networks", "mina_ctx_select_index_set", "mina_ctx_index_set",
     "mina_poseidon_install_default_params",
     "verify_mina_state_ffi", "verify_account_inclusion_ffi", "verify_mina_state_ffi_u32", "verify_account_inclusion_ffi_u32",
     "mina_verify_queue_create", "mina_verify_queue_destroy", "mina_verify_queue_submit", "mina_verify_queue_flush", "mina_verify_queue_poll", "mina_verify_queue_wait", "mina_verify_queue_fd", "mina_verify_queue_stats",
@@ -647,6 +648,45 @@ class AllDevices:
 
 def verify_all_devices() -> AllDevices:
     return AllDevices()
+
+
+class NetworkDevices(AllDevices):
+    """the installers of ONE network's index pair (mina_verify_install_*_net: index set `devnet` of every device; 0 = mainnet, 1 = devnet).  The first
+    successful install puts the process into network mode: every Proof-of-State proof is then verified against the pair of the network its public input
+    names.  Same method names as MinaContext / AllDevices"""
+    def __init__(self, devnet: int):
+        super().__init__()
+        self.devnet = int(devnet)
+
+    def verifier_index_install(self, *a):
+        vi, keep = MinaContext._verifier_index_struct(*a)
+        self._ck(self._lib.mina_verify_install_verifier_index_net(ctypes.c_int(self.devnet), ctypes.byref(vi)), "mina_verify_install_verifier_index_net")
+
+    def step_index_install(self, *a):
+        si, keep = MinaContext._step_index_struct(*a)
+        self._ck(self._lib.mina_verify_install_step_index_net(ctypes.c_int(self.devnet), ctypes.byref(si)), "mina_verify_install_step_index_net")
+
+
+def verify_network_devices(devnet: int) -> NetworkDevices:
+    return NetworkDevices(devnet)
+
+
+def verify_drop_network_indexes():
+    """leaves network mode: both index sets of every device emptied, set 0 selected"""
+    lib = load_library()
+    rc = lib.mina_verify_drop_network_indexes()
+    if rc != 0:
+        raise MinaError(f"mina_verify_drop_network_indexes failed ({rc}): {lib.mina_last_error().decode()}")
+
+
+def verify_networks():
+    """(mainnet_ready, devnet_ready): which networks hold a full configuration in network mode; (0, 0) outside it"""
+    lib = load_library()
+    a, b = ctypes.c_int(0), ctypes.c_int(0)
+    rc = lib.mina_verify_networks(ctypes.byref(a), ctypes.byref(b))
+    if rc != 0:
+        raise MinaError(f"mina_verify_networks failed ({rc}): {lib.mina_last_error().decode()}")
+    return a.value, b.value
 
 
 def poseidon_params_name() -> str:
@@ -1334,6 +1374,15 @@ class MinaContext:
         a, b = ctypes.c_uint64(0), ctypes.c_uint64(0)
         self._ck(self._lib.mina_ctx_chain_inverse_stats(self._h, ctypes.byref(a), ctypes.byref(b)), "mina_ctx_chain_inverse_stats")
         return {"gcd_launches": a.value, "fermat_launches": b.value}
+
+    def select_index_set(self, index_set: int):
+        """the index set (0 | 1) every installer, loader, getter and job of this context acts on from now on: a context holds two (wrap index, step index)
+        pairs and one of them is selected (set 0 at creation).  Host bookkeeping only: no GPU call; work already queued keeps the buffers it captured"""
+        self._ck(self._lib.mina_ctx_select_index_set(self._h, ctypes.c_uint32(int(index_set))), "mina_ctx_select_index_set")
+
+    def index_set(self) -> int:
+        self._lib.mina_ctx_index_set.restype = ctypes.c_uint32
+        return int(self._lib.mina_ctx_index_set(self._h))
 
     def lane_streams(self) -> dict:
         """test-facing: streams the context's lanes hold now, and streams its culprit searches have created so far"""
