@@ -281,6 +281,20 @@ def precheck_proofs():
     return out
 
 
+def well_formed_proof(seed=5100):
+    """the state half of ONE well-formed proof, built as precheck_proofs builds its default one (short range, same epoch, candidate longer: FORMAT and CONSENSUS
+    pass): -> (the 17 state dicts, states bytes, expected hashes 17*32 -- labels, the pre-check only compares them --, the 16 snarked ledger hashes 16*32)"""
+    from oracle import mina_state_ref as S
+    sts = [synth(seed + i, 1000 + i) for i in range(STATES)]
+    for s_, length in ((sts[15], 1015), (sts[16], 990)):
+        cs = s_["body"]["consensus_state"]
+        cs["epoch_count"] = 7; cs["staking_epoch_data"]["lock_checkpoint"] = 12345678901234567890; cs["blockchain_length"] = length
+    data = b"".join(bincode_state(s_) for s_ in sts)
+    exp = b"".join(hashlib.sha256(b"label %d" % i).digest() for i in range(STATES))
+    led = b"".join(int(S.snarked_ledger_hash(s_)).to_bytes(32, "little") for s_ in sts[:16])
+    return sts, data, exp, led
+
+
 def frontend_inputs(proofs, pad=5):
     """-> blob, begin u64[], end u64[], expected bytes, ledger bytes, and u8[]"""
     blob = bytearray(); begin, end = [], []
