@@ -690,6 +690,29 @@ int mina_ctx_chain_inverse_stats(mina_ctx *ctx, uint64_t *gcd_launches, uint64_t
  * Like the installers, not to be called while another thread queues work on the context.  set: 0 | 1, MINA_ERR_ARG otherwise. */
 int mina_ctx_select_index_set(mina_ctx *ctx, uint32_t set);
 uint32_t mina_ctx_index_set(const mina_ctx *ctx);
+/* MIXED jobs: proofs of BOTH index sets of the context in one call (opt-in: nothing else launches these forms).  net[b] = 0 | 1 names the index set proof b is
+ * checked against (the numbering of mina_ctx_select_index_set), whichever set is selected; the selection is unchanged when a call returns.  Every kernel that reads
+ * index data has a `_net` twin that takes both sets' pointers and the byte array and resolves proof b's index once, then runs the body it shares with its kernel
+ * (kimchi_fq / _rows / _pub / _scalar / _ftcomm, pickles_digest / _scalar `_net_kernel`); the kernels that read no index are the ones every job launches.  The
+ * proofs of a mixed job therefore share one wrap-proof chain, one fold, one fixed-base MSM and one accumulator check.
+ * A byte other than 0 or 1 marks THAT proof malformed (the malformed word of mina_kimchi_to_batch_net, ok[b] = 0, a 0 verdict) and is never an out-of-range read.
+ * In a job the kimchi stage's malformed word is ONE word for the whole job, as for any malformed input: mina_state_job_batch_net_dev then answers 0 for every proof
+ * with flags[1] = 1, and mina_state_job_each_net_dev (and the boundary's search) finds that proof alone.
+ * Preconditions, checked on the host before anything is queued: net not NULL (MINA_ERR_ARG); both sets fully installed -- wrap index and step index -- and the same
+ * log2_domain in both wrap indexes (MINA_ERR_STATE).  The step side of a set is prepared on its first job, mixed or not; that step synchronises, as it always has.
+ * The `_net` stages of a mixed job invert by the power whatever mina_ctx_set_chain_inverse says (there are no `_gcd` twins of the `_net` kernels) and count as
+ * power-form launches in mina_ctx_chain_inverse_stats; the kernels that read no index (the public-input commitment's finish) follow the mode.  In the opening check the index commitments are no longer the same point for every proof: only h stays a
+ * batch-shared point, and the ft commitment is computed per proof (kimchi_ftcomm_net_kernel) instead of entering the MSM as its eight terms.
+ *   mina_kimchi_to_batch_net, mina_pickles_public_inputs_batch_net    the host-buffer forms of mina_kimchi_to_batch / mina_pickles_public_inputs_batch (net: host bytes)
+ *   mina_state_job_batch_net_dev, mina_state_job_each_net_dev         mina_state_job_batch_dev / mina_state_job_each_dev with d_net: batch bytes in HBM.  The culprit
+ *                                                                     search of _each_ re-queues the stages with the same bytes.
+ *   mina_ctx_mixed_job_stats    mixed jobs this context has queued through the two job calls since it was created (one per call, whatever fails; the passes a
+ *                               culprit search re-queues are not counted) and the proofs in them by the set their byte names (a byte other than 0 / 1 counts in
+ *                               neither).  The proofs are counted on the GPU, where the bytes are: the call waits for everything the context has queued.
+ * The masks form (mina_state_job_checks*) has no mixed form.  (The two host-buffer forms are declared beside the calls they mirror, below.) */
+int mina_state_job_batch_net_dev(mina_ctx *ctx, const mina_state_jobs *jobs, const void *d_net /* batch u8 */, void *d_verdicts, void *d_flags);
+int mina_state_job_each_net_dev(mina_ctx *ctx, const mina_state_jobs *jobs, const void *d_net /* batch u8 */, void *d_verdicts /* batch u32 */, void *d_flags /* 4 u32 or NULL */);
+int mina_ctx_mixed_job_stats(mina_ctx *ctx, uint64_t *jobs, uint64_t *proofs_set0, uint64_t *proofs_set1);
 /* Test-facing: *live = the streams the context's lanes hold now, *made_by_searches = the streams its culprit searches have created since the context was created
  * (the fan search creates the streams its lanes lack and destroys them when it is done; the grouped search creates none and queues on the job's lane only). */
 int mina_ctx_lane_streams(mina_ctx *ctx, uint32_t *live, uint64_t *made_by_searches);
@@ -880,6 +903,10 @@ typedef struct mina_pickles_statements {
  * ok[b] = 0: statement b is malformed (non-canonical element, unknown step domain); its public inputs are then unspecified. */
 int mina_pickles_public_inputs_batch(mina_ctx *ctx, const mina_pickles_statements *st, size_t batch, uint8_t *public_inputs_out /* b*40*32 */,
                                      uint8_t *ok /* b */);
+/* The MIXED forms of mina_kimchi_to_batch and mina_pickles_public_inputs_batch ("MIXED jobs", above): proof b against index set net[b] of the context. */
+int mina_kimchi_to_batch_net(mina_ctx *ctx, const mina_kimchi_proofs *proofs, const uint8_t *net /* batch */, mina_kimchi_batch_out *out);
+int mina_pickles_public_inputs_batch_net(mina_ctx *ctx, const mina_pickles_statements *st, size_t batch, const uint8_t *net /* batch */, uint8_t *public_inputs_out /* b*40*32 */,
+                                         uint8_t *ok /* b */);
 /* one serialized wrap proof + the application state (the tip's protocol-state hash) -> public_input_out[40*32] (Fq) and, if
  * derived_out != NULL, 7*32 bytes: combined_inner_product, b, zeta^(2^16), zeta^n, perm, xi, r (Fp).  Sponges run on the GPU. */
 int mina_pickles_public_input(mina_ctx *ctx, const uint8_t *wrap_proof, size_t len, int encoding, const uint8_t *app_state /* 32 */,
@@ -935,6 +962,13 @@ int mina_state_proof_split(const uint8_t *bytes, size_t len, size_t *proof_len, 
                                                   MINA_VERIFY_PACK_ON_DEVICE, no download of the records and `precheck` the GPU made.  Off by default; verdicts and masks
                                                   are unchanged.  Works together with the other flags.  The searches are counted on the device's context
                                                   (mina_ctx_search_stats of mina_verify_device_ctx).  Not measured on an MI355X yet (tools/bench_search.py). */
+#define MINA_VERIFY_MIXED_NETWORK_JOB 128u   /* network mode with both networks ready, equal wrap domains and step programs of the same kind (csrc/net_route.h
+                                                  mixed_pass_allowed): ONE pass serves the proofs of both networks that share the voted evaluation shape -- one job per
+                                                  chunk, the index set chosen per proof on the GPU ("MIXED jobs", above; counted by mina_ctx_mixed_job_stats on the
+                                                  device's context) -- instead of one pass per network, one after the other.  A pass whose proofs all claim one network
+                                                  runs as without the flag; so does everything where the conditions do not hold.  Verdicts are unchanged: a failed folded
+                                                  check goes through the culprit search on the chunk (from its device staging), a proof whose flag does not parse or whose
+                                                  shape differs is treated as without the flag.  mina_verify_state_checks_batch keeps grouping by network.  Off by default. */
 #include <stdbool.h>
 bool mina_verify_state(const uint8_t *proof, size_t proof_len, const uint8_t *pub_input, size_t pub_len);
 int mina_verify_state_batch(size_t n, const uint8_t *const *proofs, const size_t *proof_lens, const uint8_t *const *pub_inputs,

@@ -69,6 +69,10 @@ extern "C" int mina_ctx_create(int device_id, mina_ctx **out) {
     c->account_on_device = mb_verify_account_dev_on;
     c->state_job_each = mb_state_job_each_host;
     c->state_job_checks = mb_state_job_checks_host;
+    c->pickles_statements_net = mb_pickles_statements_net_dev;
+    c->kimchi_to_batch_net = mb_kimchi_to_batch_net_dev;
+    c->mixed_sets_check = mb_mixed_sets_check;
+    c->state_job_each_net = mb_state_job_each_net_host;
     *out = c;
     return MINA_OK;
 }
@@ -119,6 +123,17 @@ extern "C" int mina_ctx_select_index_set(mina_ctx *c, uint32_t set) {
     return MINA_OK;
 }
 extern "C" uint32_t mina_ctx_index_set(const mina_ctx *c) { return c ? c->index_set : 0; }
+extern "C" int mina_ctx_mixed_job_stats(mina_ctx *c, uint64_t *jobs, uint64_t *proofs_set0, uint64_t *proofs_set1) {
+    if (!c || !jobs || !proofs_set0 || !proofs_set1) return fail(MINA_ERR_ARG, "null argument");
+    uint64_t tot[2] = {0, 0};
+    if (c->mixed_totals.p) {                                    // summed on the device: behind everything the context has queued
+        HIPC(hipSetDevice(c->device));
+        HIPC(mb_ctx_wait_all(c));
+        HIPC(hipMemcpy(tot, c->mixed_totals.p, sizeof tot, hipMemcpyDeviceToHost));
+    }
+    *jobs = c->mixed_jobs; *proofs_set0 = tot[0]; *proofs_set1 = tot[1];
+    return MINA_OK;
+}
 
 extern "C" int mina_ctx_synchronize(mina_ctx *c) {
     if (!c) return fail(MINA_ERR_ARG, "null ctx");

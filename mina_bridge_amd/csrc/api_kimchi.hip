@@ -77,15 +77,12 @@ template <int F, int LANES> __device__ __forceinline__ fe_t coop_sum(const fe_t 
     return a;
 }
 
+// the body of kimchi_fq_kernel and of its `_net` twin: (role, b, writer) are the wave's, `ix` the index proof b is checked against, ok = false: already malformed
 template <int LANES>
-__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(LANES == 3 ? 4 : 1, 8)))   // 3-lane form: the four waves per SIMD it had before the signed-digit forms (+ 6 VGPRs)
-kimchi_fq_kernel(uint32_t batch, uint32_t n_prev, FieldK kb, FieldK ks, const PoseidonParams *__restrict__ pp_b, const PoseidonParams *__restrict__ pp_s,
-                 const KimchiIndexDev *__restrict__ ix, KimchiIn in, KimchiOut out, fe_t *__restrict__ xf, uint32_t *__restrict__ bad_input, uint32_t nblk,
-                 const fe_t *__restrict__ pf_digest /* or null: role 1 computes it */, uint32_t pf_stride) { mb_wave_prio();
+__device__ __forceinline__ void kimchi_fq_body(uint32_t role, uint32_t b, bool writer, bool ok, uint32_t n_prev, const FieldK &kb, const FieldK &ks, const PoseidonParams *__restrict__ pp_b,
+                                               const PoseidonParams *__restrict__ pp_s, const KimchiIndexDev *__restrict__ ix, const KimchiIn &in, const KimchiOut &out, fe_t *__restrict__ xf,
+                                               uint32_t *__restrict__ bad_input, const fe_t *__restrict__ pf_digest /* or null: role 1 computes it */, uint32_t pf_stride) {
     constexpr int FB = FIELD_FP, FS = FIELD_FQ;                 // Pallas: base Fp, scalar Fq
-    bool writer; const uint32_t role = blockIdx.x / nblk, b = coop_role_item<LANES>(blockIdx.x % nblk, writer);       // one role per wave
-    if (b >= batch) return;
-    bool ok = true;
     if (role) {                                                 // digest of the recursion challenges
         const uint32_t cnt = n_prev * ix->log2_domain;
         const uint32_t *p = in.prev_chals + (size_t)b * cnt * 8;
@@ -120,6 +117,30 @@ kimchi_fq_kernel(uint32_t batch, uint32_t n_prev, FieldK kb, FieldK ks, const Po
     const fe_t digest = fe_to_mont<FS>(fe_from_mont<FB>(fq.squeeze()), ks.r2);      // on a copy upstream; p < q: always fits.  fq is dead after this
     if (writer) { x[XF_DIGEST] = digest; if (!ok) *bad_input = 1u; }
 }
+template <int LANES>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(LANES == 3 ? 4 : 1, 8)))   // 3-lane form: the four waves per SIMD it had before the signed-digit forms (+ 6 VGPRs)
+kimchi_fq_kernel(uint32_t batch, uint32_t n_prev, FieldK kb, FieldK ks, const PoseidonParams *__restrict__ pp_b, const PoseidonParams *__restrict__ pp_s,
+                 const KimchiIndexDev *__restrict__ ix, KimchiIn in, KimchiOut out, fe_t *__restrict__ xf, uint32_t *__restrict__ bad_input, uint32_t nblk,
+                 const fe_t *__restrict__ pf_digest, uint32_t pf_stride) { mb_wave_prio();
+    bool writer; const uint32_t role = blockIdx.x / nblk, b = coop_role_item<LANES>(blockIdx.x % nblk, writer);       // one role per wave
+    if (b >= batch) return;
+    kimchi_fq_body<LANES>(role, b, writer, true, n_prev, kb, ks, pp_b, pp_s, ix, in, out, xf, bad_input, pf_digest, pf_stride);
+}
+// ---- the `_net` twins: the same bodies for a job that holds proofs of BOTH index sets of the context (ix0 / ix1, and the token programs where a stage runs one);
+// net[b] = 0 | 1 picks proof b's (kimchi_dev.cuh net_second), any other byte marks it malformed.  No `_gcd` twins of these: a mixed job inverts by the power
+// whatever mina_ctx_set_chain_inverse says (and counts as power-form launches).
+// 3-lane form: TWO waves per SIMD at the least, not four -- the second index pointer and the byte would spill at 128 VGPRs, and a twin keeps nothing in scratch;
+// this is a latency chain, not a chip-filling kernel.
+template <int LANES>
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(LANES == 3 ? 2 : 1, 8)))
+kimchi_fq_net_kernel(uint32_t batch, uint32_t n_prev, FieldK kb, FieldK ks, const PoseidonParams *__restrict__ pp_b, const PoseidonParams *__restrict__ pp_s,
+                     const KimchiIndexDev *__restrict__ ix0, const KimchiIndexDev *__restrict__ ix1, const uint8_t *__restrict__ net, KimchiIn in, KimchiOut out,
+                     fe_t *__restrict__ xf, uint32_t *__restrict__ bad_input, uint32_t nblk, const fe_t *__restrict__ pf_digest, uint32_t pf_stride) { mb_wave_prio();
+    bool writer; const uint32_t role = blockIdx.x / nblk, b = coop_role_item<LANES>(blockIdx.x % nblk, writer);
+    if (b >= batch) return;
+    bool ok; const KimchiIndexDev *ix = net_second(net, b, ok) ? ix1 : ix0;
+    kimchi_fq_body<LANES>(role, b, writer, ok, n_prev, kb, ks, pp_b, pp_s, ix, in, out, xf, bad_input, pf_digest, pf_stride);
+}
 
 // negated public polynomial at zeta and zeta*omega:  -(x^n - 1)/n * sum_i p_i w^i / (x - w^i).  8 lanes per proof; work item = (side,
 // chunk of CH terms), round-robin over the lanes, each inverts its CH denominators with one field inversion; shuffle-tree sum.
@@ -143,11 +164,10 @@ template <int CH> struct PubLds {
 };
 template <int CH, class Inv, class Cols>
 __device__ __forceinline__ void kimchi_pub_body(uint32_t batch, uint32_t npub, const FieldK &ks, const KimchiIndexDev *__restrict__ ix, const KimchiIn &in, fe_t *__restrict__ xf,
-                                                uint32_t *__restrict__ bad_input, Cols &cols) {
+                                                uint32_t *__restrict__ bad_input, Cols &cols, bool ok = true) {
     constexpr int FS = FIELD_FQ;
     const uint32_t gid = blockIdx.x * 64 + threadIdx.x, b = gid >> 3, ln = gid & 7u;
     if (b >= batch) return;
-    bool ok = true;
     fe_t *x = xf + (size_t)b * KC_XF;
     const uint32_t k = ix->log2_domain;
     const fe_t zeta = x[XF_ZETA], zetaw = fe_mul<FS>(zeta, ix->omega);
@@ -192,6 +212,18 @@ kimchi_pub_gcd_kernel(uint32_t batch, uint32_t npub, FieldK ks, const KimchiInde
     PubLds<CH> cols{LdsStack{lds + threadIdx.x}};
     kimchi_pub_body<CH, FeInvGcd>(batch, npub, ks, ix, in, xf, bad_input, cols);
 }
+// the `_net` twin: the LDS columns at either CH (nothing in scratch), the inversion by the power
+template <int CH>
+__global__ void __launch_bounds__(64)
+kimchi_pub_net_kernel(uint32_t batch, uint32_t npub, FieldK ks, const KimchiIndexDev *__restrict__ ix0, const KimchiIndexDev *__restrict__ ix1, const uint8_t *__restrict__ net,
+                      KimchiIn in, fe_t *__restrict__ xf, uint32_t *__restrict__ bad_input) { mb_wave_prio();
+    __shared__ uint32_t lds[2 * CH * 8 * 64];
+    PubLds<CH> cols{LdsStack{lds + threadIdx.x}};
+    const uint32_t b = (blockIdx.x * 64 + threadIdx.x) >> 3;
+    if (b >= batch) return;
+    bool ok; const KimchiIndexDev *ix = net_second(net, b, ok) ? ix1 : ix0;
+    kimchi_pub_body<CH, FeInvPow>(batch, npub, ks, ix, in, xf, bad_input, cols, ok);
+}
 
 template <int LANES>
 __global__ void __launch_bounds__(64)
@@ -218,7 +250,7 @@ kimchi_fr_kernel(uint32_t batch, FieldK ks, const PoseidonParams *__restrict__ p
 template <class Inv>
 __device__ __forceinline__ void kimchi_scalar_body(uint32_t batch, uint32_t n_prev, const FieldK &ks, const KimchiIndexDev *__restrict__ ix, const KimchiToken *__restrict__ toks,
                                                    const fe_t *__restrict__ lits, const KimchiIn &in, const KimchiOut &out, fe_t *__restrict__ xf, uint32_t *__restrict__ bad_input,
-                                                   uint32_t *lds /* KC_SLOTS * 8 * 64 words */) {
+                                                   uint32_t *lds /* KC_SLOTS * 8 * 64 words */, bool ok = true) {
     constexpr int FS = FIELD_FQ;
     const uint32_t b = blockIdx.x * 64 + threadIdx.x;
     if (b >= batch) return;
@@ -230,7 +262,6 @@ __device__ __forceinline__ void kimchi_scalar_body(uint32_t batch, uint32_t n_pr
     const fe_t zeta = x[XF_ZETA];
     const fe_t zeta1 = fe_pow2k<FS>(zeta, k), zetaw = fe_mul<FS>(zeta, ix->omega);
     const fe_t zm1 = fe_sub<FS>(zeta1, ks.one);
-    bool ok = true;
     fe_t perm_scalar;
     FtEnv env{x[XF_ALPHA], x[XF_BETA], x[XF_GAMMA], zeta, zeta1, ix->omega, ix->omega_zk, ix->endo_coeff, ix->zk_roots, ix->shifts, ix->mds, lits, toks,
               k, ix->zk_rows, ix->perm_alpha_offset, ix->n_tokens};
@@ -277,6 +308,17 @@ kimchi_scalar_gcd_kernel(uint32_t batch, uint32_t n_prev, FieldK ks, const Kimch
     __shared__ uint32_t lds[KC_SLOTS * 8 * 64];
     kimchi_scalar_body<FeInvGcd>(batch, n_prev, ks, ix, toks, lits, in, out, xf, bad_input, lds);
 }
+// the `_net` twin: proof b runs the token program of its own set (a wave that holds both networks diverges in the interpreter; the boundary orders a pass by network)
+__global__ void __launch_bounds__(64)
+kimchi_scalar_net_kernel(uint32_t batch, uint32_t n_prev, FieldK ks, const KimchiIndexDev *__restrict__ ix0, const KimchiToken *__restrict__ toks0, const fe_t *__restrict__ lits0,
+                         const KimchiIndexDev *__restrict__ ix1, const KimchiToken *__restrict__ toks1, const fe_t *__restrict__ lits1, const uint8_t *__restrict__ net,
+                         KimchiIn in, KimchiOut out, fe_t *__restrict__ xf, uint32_t *__restrict__ bad_input) { mb_wave_prio();
+    __shared__ uint32_t lds[KC_SLOTS * 8 * 64];
+    const uint32_t b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= batch) return;
+    bool ok; const bool second = net_second(net, b, ok);
+    kimchi_scalar_body<FeInvPow>(batch, n_prev, ks, second ? ix1 : ix0, second ? toks1 : toks0, second ? lits1 : lits0, in, out, xf, bad_input, lds, ok);
+}
 
 // 8 lanes per proof: term j on lane j, then a shuffle tree; lane 0 normalises and writes row n_prev + 1.  The t commitments were
 // checked by the fq stage (a malformed one already failed the batch).  Only the host-buffer form (`mina_kimchi_to_batch`, which
@@ -309,15 +351,27 @@ __global__ void __launch_bounds__(64)
 kimchi_ftcomm_gcd_kernel(uint32_t batch, uint32_t n_prev, FieldK kb, const KimchiIndexDev *__restrict__ ix, KimchiIn in, KimchiOut out, const fe_t *__restrict__ xf) { mb_wave_prio();
     kimchi_ftcomm_body<FeInvGcd>(batch, n_prev, kb, ix, in, out, xf);
 }
+// the `_net` twin (no malformed word here: see net_second's two-argument form)
+__global__ void __launch_bounds__(64)
+kimchi_ftcomm_net_kernel(uint32_t batch, uint32_t n_prev, FieldK kb, const KimchiIndexDev *__restrict__ ix0, const KimchiIndexDev *__restrict__ ix1, const uint8_t *__restrict__ net,
+                         KimchiIn in, KimchiOut out, const fe_t *__restrict__ xf) { mb_wave_prio();
+    const uint32_t b = (blockIdx.x * 64 + threadIdx.x) >> 3;
+    if (b >= batch) return;
+    kimchi_ftcomm_body<FeInvPow>(batch, n_prev, kb, net_second(net, b) ? ix1 : ix0, in, out, xf);
+}
 
 // the rows of the commitment list that are copies: recursion accumulators, the public-input commitment, then the 43 columns
 // z, 6 selectors (index), 15 w, 15 coefficients (index), 6 sigma (index).  Row n_prev + 1 (ft) belongs to the ftcomm stage.
-__global__ void __launch_bounds__(256)
-kimchi_rows_kernel(uint32_t batch, uint32_t n_prev, const KimchiIndexDev *__restrict__ ix, KimchiIn in, uint32_t *__restrict__ comms) { mb_wave_prio();
+// Pick: the index of proof b -- the one index (kimchi_rows_kernel), or by the proof's byte (kimchi_rows_net_kernel)
+struct RowsOneIndex { const KimchiIndexDev *ix; __device__ __forceinline__ const KimchiIndexDev *operator()(size_t) const { return ix; } };
+struct RowsNetIndex { const KimchiIndexDev *ix0, *ix1; const uint8_t *net; __device__ __forceinline__ const KimchiIndexDev *operator()(size_t b) const { return net_second(net, (uint32_t)b) ? ix1 : ix0; } };
+template <class Pick>
+__device__ __forceinline__ void kimchi_rows_body(uint32_t batch, uint32_t n_prev, const Pick &pick, const KimchiIn &in, uint32_t *__restrict__ comms) {
     const uint32_t ncomms = n_prev + 2 + KC_COLS;
     const size_t gid = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (gid >= (size_t)batch * ncomms * 16) return;
     const uint32_t w = (uint32_t)(gid & 15u), row = (uint32_t)((gid >> 4) % ncomms); const size_t b = (gid >> 4) / ncomms;
+    const KimchiIndexDev *ix = pick(b);
     uint32_t val;
     if (row < n_prev) val = in.prev_comms[(b * n_prev + row) * 16 + w];
     else if (row == n_prev) val = in.pubcomm[b * 16 + w];
@@ -330,6 +384,21 @@ kimchi_rows_kernel(uint32_t batch, uint32_t n_prev, const KimchiIndexDev *__rest
         else val = ix->col_comm_words[(6 + (c - 22)) * 16 + w];
     }
     comms[gid] = val;
+}
+__global__ void __launch_bounds__(256)
+kimchi_rows_kernel(uint32_t batch, uint32_t n_prev, const KimchiIndexDev *__restrict__ ix, KimchiIn in, uint32_t *__restrict__ comms) { mb_wave_prio();
+    kimchi_rows_body(batch, n_prev, RowsOneIndex{ix}, in, comms);
+}
+__global__ void __launch_bounds__(256)
+kimchi_rows_net_kernel(uint32_t batch, uint32_t n_prev, const KimchiIndexDev *__restrict__ ix0, const KimchiIndexDev *__restrict__ ix1, const uint8_t *__restrict__ net, KimchiIn in,
+                       uint32_t *__restrict__ comms) { mb_wave_prio();
+    kimchi_rows_body(batch, n_prev, RowsNetIndex{ix0, ix1, net}, in, comms);
+}
+// (not part of the wrap-proof chain: no raised priority)  per-set proof counts of a mixed job (mina_ctx_mixed_job_stats): tot[s] += the proofs whose byte is s; any other byte counts in neither
+__global__ void __launch_bounds__(256)
+mixed_count_kernel(uint32_t batch, const uint8_t *__restrict__ net, unsigned long long *__restrict__ tot) {
+    const uint32_t b = blockIdx.x * 256 + threadIdx.x;
+    if (b < batch && net[b] <= 1u) atomicAdd(&tot[net[b]], 1ull);
 }
 
 }  // namespace mb
@@ -445,6 +514,42 @@ int mb_kimchi_to_batch_dev(mina_ctx *c, size_t batch, uint32_t n_prev, uint32_t 
     return MINA_OK;
 }
 
+// The same stages for a MIXED job: proof b against index set d_net[b] (0 | 1; a device pointer, one byte per proof) of the context, whichever set is selected.
+// The caller has checked mb_mixed_sets_check.  The ft row is always computed here (kimchi_ftcomm_net_kernel): its index point differs per proof, so the opening
+// check gets no expanded slot.  Every inversion is the power's: the stages count as power-form launches (mina_ctx_chain_inverse_stats).
+// d_count: two 64-bit totals in HBM the proofs are counted into by set, or null (the host-buffer form; the slices a culprit search re-queues).
+int mb_kimchi_to_batch_net_dev(mina_ctx *c, size_t batch, uint32_t n_prev, uint32_t npub, const mb::KimchiIn &in, const mb::KimchiOut &out, uint32_t *d_bad, const uint8_t *d_net,
+                               const void *pf_digest, uint32_t pf_stride, void *d_count) {
+    if (!d_net) return fail(MINA_ERR_ARG, "null argument");
+    const PoseidonParams *ppb = c->pparams[FIELD_FP].as<PoseidonParams>(), *pps = c->pparams[FIELD_FQ].as<PoseidonParams>();
+    ProfScope ps_(c, PS_KIMCHI);
+    Lane &L = *c->L;
+    int rc;
+    if ((rc = L.kc_xfer.ensure(batch * mb::KC_XF * sizeof(fe_t)))) return rc;
+    fe_t *xf = L.kc_xfer.as<fe_t>();
+    IndexSet &s0 = c->set_at(0), &s1 = c->set_at(1);
+    const mb::KimchiIndexDev *ix0 = s0.kimchi_index.as<mb::KimchiIndexDev>(), *ix1 = s1.kimchi_index.as<mb::KimchiIndexDev>();
+    const uint32_t B = (uint32_t)batch, ncomms = n_prev + 2 + mb::KC_COLS;
+    const FieldK &kb = c->fk[FIELD_FP], &ks = c->fk[FIELD_FQ];
+    mb::kimchi_rows_net_kernel<<<cdiv(batch * ncomms * 16, 256), 256, 0, L.stream>>>(B, n_prev, ix0, ix1, d_net, in, out.comms);
+    if (d_count) mb::mixed_count_kernel<<<cdiv(batch, 256), 256, 0, L.stream>>>(B, d_net, (unsigned long long *)d_count);
+    const uint32_t fq_roles = pf_digest ? 1u : 2u;
+    if ((rc = with_lanes<16, 8, 3>(transcript_lanes(c, batch, (size_t)mb_tune().kimchi_coop8_max), [&](auto lanes) {
+            constexpr int LN = decltype(lanes)::value;
+            mb::kimchi_fq_net_kernel<LN><<<fq_roles * coop_role_blocks<LN>(batch), 64, 0, L.stream>>>(B, n_prev, kb, ks, ppb, pps, ix0, ix1, d_net, in, out, xf, d_bad, coop_role_blocks<LN>(batch), (const fe_t *)pf_digest, pf_stride);
+            if (npub > 32 && npub <= 40) mb::kimchi_pub_net_kernel<10><<<cdiv(batch * 8, 64), 64, 0, L.stream>>>(B, npub, ks, ix0, ix1, d_net, in, xf, d_bad);
+            else mb::kimchi_pub_net_kernel<8><<<cdiv(batch * 8, 64), 64, 0, L.stream>>>(B, npub, ks, ix0, ix1, d_net, in, xf, d_bad);
+            mb::kimchi_fr_kernel<LN><<<cdiv(coop_threads<LN>(batch), 64), 64, 0, L.stream>>>(B, ks, pps, in, xf, d_bad);
+            return MINA_OK;
+        }))) return rc;
+    mb::kimchi_scalar_net_kernel<<<cdiv(batch, 64), 64, 0, L.stream>>>(B, n_prev, ks, ix0, s0.kimchi_tokens.as<mb::KimchiToken>(), s0.kimchi_literals.as<fe_t>(), ix1,
+                                                                        s1.kimchi_tokens.as<mb::KimchiToken>(), s1.kimchi_literals.as<fe_t>(), d_net, in, out, xf, d_bad);
+    mb::kimchi_ftcomm_net_kernel<<<cdiv(batch * 8, 64), 64, 0, L.stream>>>(B, n_prev, kb, ix0, ix1, d_net, in, out, xf);
+    c->chain_fermat_launches += 3;                              // pub, scalar, ftcomm
+    HIPC(hipGetLastError());
+    return MINA_OK;
+}
+
 int mb_ensure_lagrange_table(mina_ctx *c, int curve, uint32_t log2_domain, uint32_t npub);   // api_srs.hip
 int mb_pubcomm_dev(mina_ctx *c, size_t batch, uint32_t log2_domain, uint32_t npub, const uint32_t *d_pub, uint32_t *d_out16);   // api_state.hip
 
@@ -456,10 +561,12 @@ static int check_kimchi_in(mina_ctx *c, const mina_kimchi_proofs *p) {
     return MINA_OK;
 }
 
-// host-buffer form (tests / tooling): the BatchEvaluationProof rows back on the host
-extern "C" int mina_kimchi_to_batch(mina_ctx *c, const mina_kimchi_proofs *p, mina_kimchi_batch_out *o) {
+// host-buffer form (tests / tooling): the BatchEvaluationProof rows back on the host.  mixed: proof b against index set net[b] (mina_kimchi_to_batch_net)
+static int kimchi_to_batch_host(mina_ctx *c, const mina_kimchi_proofs *p, const uint8_t *net, bool mixed, mina_kimchi_batch_out *o) {
     int rc = check_kimchi_in(c, p);
     if (rc) return rc;
+    if (mixed && !net) return fail(MINA_ERR_ARG, "null argument");
+    if (mixed && (rc = mb_mixed_sets_check(c))) return rc;
     if (!o || !o->sponge_state || !o->sponge_pos || !o->cip || !o->evalpoints || !o->polyscale || !o->evalscale || !o->comms) return fail(MINA_ERR_ARG, "null output");
     HIPC(hipSetDevice(c->device));
     c->use_lane0();
@@ -469,7 +576,7 @@ extern "C" int mina_kimchi_to_batch(mina_ctx *c, const mina_kimchi_proofs *p, mi
     Lane &L = *c->L;
     struct Sec { const void *src; size_t bytes; size_t off; };
     std::vector<Sec> secs = {{p->public_inputs, B * p->npub * 32, 0}, {p->prev_chals, B * p->n_prev * k * 32, 0}, {p->prev_comms, B * p->n_prev * 64, 0}, {p->w_comm, B * 15 * 64, 0},
-                             {p->z_comm, B * 64, 0}, {p->t_comm, B * 7 * 64, 0}, {p->evals, B * mb::KC_COLS * 64, 0}, {p->ft_eval1, B * 32, 0}};
+                             {p->z_comm, B * 64, 0}, {p->t_comm, B * 7 * 64, 0}, {p->evals, B * mb::KC_COLS * 64, 0}, {p->ft_eval1, B * 32, 0}, {net, mixed ? B : 0, 0}};
     size_t total = 0; for (auto &s : secs) { s.off = total; total += (s.bytes + 255) & ~(size_t)255; }
     const size_t o_state = total, o_pos = o_state + B * 96, o_cip = o_pos + ((B * 8 + 255) & ~(size_t)255), o_pts = o_cip + B * 32, o_v = o_pts + B * 64, o_u = o_v + B * 32,
                  o_comms = o_u + B * 32, o_ft = o_comms + B * ncomms * 64, o_pc = o_ft + B * 32, o_bad = o_pc + B * 64, all = o_bad + 256;
@@ -484,7 +591,8 @@ extern "C" int mina_kimchi_to_batch(mina_ctx *c, const mina_kimchi_proofs *p, mi
     else { std::vector<uint8_t> hb(B * 64); uint8_t h1[64]; if ((rc = mina_srs_get_h(c, CURVE_PALLAS, h1))) return rc; c->use_lane0(); for (size_t i = 0; i < B; ++i) memcpy(&hb[i * 64], h1, 64); HIPC(hipMemcpyAsync(d + o_pc, hb.data(), B * 64, hipMemcpyHostToDevice, L.stream)); HIPC(hipStreamSynchronize(L.stream)); }
     mb::KimchiIn in{W(secs[0].off), W(secs[1].off), W(secs[2].off), W(secs[3].off), W(secs[4].off), W(secs[5].off), W(secs[6].off), W(secs[7].off), W(o_pc)};
     mb::KimchiOut out{W(o_state), W(o_pos), W(o_cip), W(o_pts), W(o_v), W(o_u), W(o_comms), W(o_ft)};
-    if ((rc = mb_kimchi_to_batch_dev(c, B, p->n_prev, p->npub, in, out, W(o_bad), nullptr, nullptr, 0))) return rc;
+    if (mixed) { if ((rc = mb_kimchi_to_batch_net_dev(c, B, p->n_prev, p->npub, in, out, W(o_bad), d + secs[8].off, nullptr, 0, nullptr))) return rc; }
+    else if ((rc = mb_kimchi_to_batch_dev(c, B, p->n_prev, p->npub, in, out, W(o_bad), nullptr, nullptr, 0))) return rc;
     std::vector<uint8_t> back(all - o_state);
     HIPC(hipMemcpyAsync(back.data(), d + o_state, back.size(), hipMemcpyDeviceToHost, L.stream));
     HIPC(hipStreamSynchronize(L.stream));
@@ -495,3 +603,5 @@ extern "C" int mina_kimchi_to_batch(mina_ctx *c, const mina_kimchi_proofs *p, mi
     if (o->malformed) { uint32_t f; memcpy(&f, R(o_bad), 4); *o->malformed = f ? 1 : 0; }
     return MINA_OK;
 }
+extern "C" int mina_kimchi_to_batch(mina_ctx *c, const mina_kimchi_proofs *p, mina_kimchi_batch_out *o) { return kimchi_to_batch_host(c, p, nullptr, false, o); }
+extern "C" int mina_kimchi_to_batch_net(mina_ctx *c, const mina_kimchi_proofs *p, const uint8_t *net, mina_kimchi_batch_out *o) { return kimchi_to_batch_host(c, p, net, true, o); }

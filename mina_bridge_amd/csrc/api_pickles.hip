@@ -318,14 +318,12 @@ pickles_expand_kernel(uint32_t batch, FieldK kp, FieldK kq, PicklesIn in, fe_t *
     }
 }
 
+// the body of pickles_digest_kernel and of its `_net` twin: (role, b, writer) are the wave's, `ix` the step index of proof b, ok = false: already malformed
 template <int LANES>
-__global__ void __launch_bounds__(64)
-pickles_digest_kernel(uint32_t batch, FieldK kp, FieldK kq, const PoseidonParams *__restrict__ pp_p, const PoseidonParams *__restrict__ pp_q,
-                      const PicklesIndexDev *__restrict__ ix, PicklesIn in, fe_t *__restrict__ xe, uint32_t *__restrict__ ok_out, uint32_t nblk) { mb_wave_prio();
-    bool writer; const uint32_t role = blockIdx.x / nblk, b = coop_role_item<LANES>(blockIdx.x % nblk, writer);       // one role per wave
-    if (b >= batch) return;
+__device__ __forceinline__ void pickles_digest_body(uint32_t role, uint32_t b, bool writer, bool ok, const FieldK &kp, const FieldK &kq, const PoseidonParams *__restrict__ pp_p,
+                                                    const PoseidonParams *__restrict__ pp_q, const PicklesIndexDev *__restrict__ ix, const PicklesIn &in, fe_t *__restrict__ xe,
+                                                    uint32_t *__restrict__ ok_out) {
     fe_t *x = xe + (size_t)b * px_stride(in.n_old);
-    bool ok = true;
     if (role == 0) {                                        // digest of the step-side old challenges
         DevSponge<FIELD_FP, LANES> sp; sponge_init(sp, pp_p);
 #pragma unroll 1
@@ -360,6 +358,25 @@ pickles_digest_kernel(uint32_t batch, FieldK kp, FieldK kq, const PoseidonParams
     }
     if (!ok) ok_out[b] = 0u;
 }
+template <int LANES>
+__global__ void __launch_bounds__(64)
+pickles_digest_kernel(uint32_t batch, FieldK kp, FieldK kq, const PoseidonParams *__restrict__ pp_p, const PoseidonParams *__restrict__ pp_q,
+                      const PicklesIndexDev *__restrict__ ix, PicklesIn in, fe_t *__restrict__ xe, uint32_t *__restrict__ ok_out, uint32_t nblk) { mb_wave_prio();
+    bool writer; const uint32_t role = blockIdx.x / nblk, b = coop_role_item<LANES>(blockIdx.x % nblk, writer);       // one role per wave
+    if (b >= batch) return;
+    pickles_digest_body<LANES>(role, b, writer, true, kp, kq, pp_p, pp_q, ix, in, xe, ok_out);
+}
+// The `_net` twins (a job that holds proofs of BOTH index sets of the context): net[b] = 0 | 1 picks proof b's step index (kimchi_dev.cuh net_second), any other
+// byte fails that proof (ok_out[b] = 0).  No `_gcd` twins of these: a mixed job inverts by the power whatever mina_ctx_set_chain_inverse says.
+template <int LANES>
+__global__ void __launch_bounds__(64)
+pickles_digest_net_kernel(uint32_t batch, FieldK kp, FieldK kq, const PoseidonParams *__restrict__ pp_p, const PoseidonParams *__restrict__ pp_q, const PicklesIndexDev *__restrict__ ix0,
+                          const PicklesIndexDev *__restrict__ ix1, const uint8_t *__restrict__ net, PicklesIn in, fe_t *__restrict__ xe, uint32_t *__restrict__ ok_out, uint32_t nblk) { mb_wave_prio();
+    bool writer; const uint32_t role = blockIdx.x / nblk, b = coop_role_item<LANES>(blockIdx.x % nblk, writer);
+    if (b >= batch) return;
+    bool ok; const PicklesIndexDev *ix = net_second(net, b, ok) ? ix1 : ix0;
+    pickles_digest_body<LANES>(role, b, writer, ok, kp, kq, pp_p, pp_q, ix, in, xe, ok_out);
+}
 
 template <int LANES>
 __global__ void __launch_bounds__(64)
@@ -389,14 +406,13 @@ pickles_tick_kernel(uint32_t batch, FieldK kp, const PoseidonParams *__restrict_
 template <class Inv>
 __device__ __forceinline__ void pickles_scalar_body(uint32_t batch, const FieldK &kp, const FieldK &kq, const PicklesIndexDev *__restrict__ ix, const KimchiToken *__restrict__ toks,
                                                     const fe_t *__restrict__ lits, const PicklesIn &in, const fe_t *__restrict__ xe, uint32_t *__restrict__ pub_out,
-                                                    uint32_t *__restrict__ ok_out, uint32_t *lds /* KC_SLOTS * 8 * 64 words */) {
+                                                    uint32_t *__restrict__ ok_out, uint32_t *lds /* KC_SLOTS * 8 * 64 words */, bool ok = true) {
     constexpr int F = FIELD_FP;
     const uint32_t b = blockIdx.x * 64 + threadIdx.x;
     if (b >= batch) return;
     LdsStack st{lds + threadIdx.x};
     const fe_t *x = xe + (size_t)b * px_stride(in.n_old);
     const uint8_t *misc = in.misc + (size_t)b * 32;
-    bool ok = true;
     uint32_t dom = 0; { bool found = false; for (uint32_t d = 0; d < ix->n_domains; ++d) if (ix->domain_log2[d] == misc[0]) { dom = d; found = true; } ok = ok && found; }
     const uint32_t k = ix->domain_log2[dom];
     const uint32_t *ev = in.evals + (size_t)b * in.n_evals * 16;
@@ -484,17 +500,24 @@ pickles_scalar_gcd_kernel(uint32_t batch, FieldK kp, FieldK kq, const PicklesInd
     __shared__ uint32_t lds[KC_SLOTS * 8 * 64];
     pickles_scalar_body<FeInvGcd>(batch, kp, kq, ix, toks, lits, in, xe, pub_out, ok_out, lds);
 }
+__global__ void __launch_bounds__(64)
+pickles_scalar_net_kernel(uint32_t batch, FieldK kp, FieldK kq, const PicklesIndexDev *__restrict__ ix0, const KimchiToken *__restrict__ toks0, const fe_t *__restrict__ lits0,
+                          const PicklesIndexDev *__restrict__ ix1, const KimchiToken *__restrict__ toks1, const fe_t *__restrict__ lits1, const uint8_t *__restrict__ net,
+                          PicklesIn in, const fe_t *__restrict__ xe, uint32_t *__restrict__ pub_out, uint32_t *__restrict__ ok_out) { mb_wave_prio();
+    __shared__ uint32_t lds[KC_SLOTS * 8 * 64];
+    const uint32_t b = blockIdx.x * 64 + threadIdx.x;
+    if (b >= batch) return;
+    bool ok; const bool second = net_second(net, b, ok);
+    pickles_scalar_body<FeInvPow>(batch, kp, kq, second ? ix1 : ix0, second ? toks1 : toks0, second ? lits1 : lits0, in, xe, pub_out, ok_out, lds, ok);
+}
 
 }  // namespace mb
 
 // queue the four stages on the current lane: d_pub (b*40*8 words) and d_ok (b u32, 1 = well-formed) are device buffers
-int mb_pickles_dev(mina_ctx *c, size_t batch, const mb::PicklesIn &in, uint32_t *d_pub, uint32_t *d_ok) {
-    if (!c->have_pickles_dev) return fail(MINA_ERR_STATE, "no step index installed");
-    if (!c->have_kimchi) return fail(MINA_ERR_STATE, "no wrap verifier index installed");
-    if (in.n_old > 4 || in.n_evals < mb::KC_COLS || in.n_evals > N_STEP_COLS) return fail(MINA_ERR_ARG, "bad n_old / n_evals");
-    Lane &L = *c->L;
+// the Tick sponge after the 28 wrap index commitments of the SELECTED set, cached in its step index: once per (wrap index, step index) pair; synchronises when it runs
+static int pickles_ms_prepare(mina_ctx *c) {
     int rc;
-    if (!c->pickles_ms_valid) {     // the Tick sponge after the 28 wrap index commitments: once per (wrap index, step index) pair
+    if (!c->pickles_ms_valid) {
         Lane *keep = c->L;
         std::vector<uint8_t> tape(28, MINA_TAPE_ABSORB_G), stt(96); uint32_t pos[2];
         std::vector<uint8_t> dummy(32);
@@ -508,6 +531,21 @@ int mb_pickles_dev(mina_ctx *c, size_t batch, const mb::PicklesIn &in, uint32_t 
         c->pickles_ms_valid = true;
         c->L = keep;
     }
+    return MINA_OK;
+}
+// d_net null: the selected set.  d_net given (device bytes, one per proof): a MIXED job, proof b against set d_net[b] of the context -- the caller has checked
+// mb_mixed_sets_check; the step side of both sets is prepared here, each selected in turn (host bookkeeping; the selection is back where it was on return).
+int mb_pickles_dev(mina_ctx *c, size_t batch, const mb::PicklesIn &in, uint32_t *d_pub, uint32_t *d_ok, const uint8_t *d_net) {
+    if (!c->have_pickles_dev) return fail(MINA_ERR_STATE, "no step index installed");
+    if (!c->have_kimchi) return fail(MINA_ERR_STATE, "no wrap verifier index installed");
+    if (in.n_old > 4 || in.n_evals < mb::KC_COLS || in.n_evals > N_STEP_COLS) return fail(MINA_ERR_ARG, "bad n_old / n_evals");
+    Lane &L = *c->L;
+    int rc;
+    if (d_net && c->pickles_ms_valid && c->parked.pickles_ms_valid) {}      // the steady state: both prepared, the selection is not touched
+    else if (d_net) {
+        const uint32_t sel = c->index_set;
+        for (uint32_t k : {1u - sel, sel}) { c->select_index_set(k); if ((rc = pickles_ms_prepare(c))) { c->select_index_set(sel); return rc; } }
+    } else if ((rc = pickles_ms_prepare(c))) return rc;
     const mb::PicklesIndexDev *ix = c->pickles_index.as<mb::PicklesIndexDev>();
     if ((rc = L.pk_xe.ensure(batch * mb::px_stride(in.n_old) * sizeof(fe_t)))) return rc;
     fe_t *xe = L.pk_xe.as<fe_t>();
@@ -517,13 +555,21 @@ int mb_pickles_dev(mina_ctx *c, size_t batch, const mb::PicklesIn &in, uint32_t 
     ProfScope ps_(c, PS_PICKLES);
     HIPC(hipMemsetD32Async((hipDeviceptr_t)d_ok, 1, batch, L.stream));   // a program that names an optional evaluation a proof lacks (outside a skipped region) fails THAT proof (pickles_scalar_kernel)
     mb::pickles_expand_kernel<<<cdiv(batch * (50 + 16 * in.n_old), 256), 256, 0, L.stream>>>(B, kp, kq, in, xe);
+    IndexSet &s0 = c->set_at(0), &s1 = c->set_at(1);
+    const mb::PicklesIndexDev *ix0 = s0.pickles_index.as<mb::PicklesIndexDev>(), *ix1 = s1.pickles_index.as<mb::PicklesIndexDev>();
     if ((rc = with_lanes<16, 8, 3>(transcript_lanes(c, batch, 1024), [&](auto lanes) {
             constexpr int LN = decltype(lanes)::value;
-            mb::pickles_digest_kernel<LN><<<3 * coop_role_blocks<LN>(batch), 64, 0, L.stream>>>(B, kp, kq, ppp, ppq, ix, in, xe, d_ok, coop_role_blocks<LN>(batch));
+            if (d_net) mb::pickles_digest_net_kernel<LN><<<3 * coop_role_blocks<LN>(batch), 64, 0, L.stream>>>(B, kp, kq, ppp, ppq, ix0, ix1, d_net, in, xe, d_ok, coop_role_blocks<LN>(batch));
+            else mb::pickles_digest_kernel<LN><<<3 * coop_role_blocks<LN>(batch), 64, 0, L.stream>>>(B, kp, kq, ppp, ppq, ix, in, xe, d_ok, coop_role_blocks<LN>(batch));
             mb::pickles_tick_kernel<LN><<<cdiv(coop_threads<LN>(batch), 64), 64, 0, L.stream>>>(B, kp, ppp, in, xe, d_ok);
             return MINA_OK;
         }))) return rc;
-    if (c->gcd_launch()) mb::pickles_scalar_gcd_kernel<<<cdiv(batch, 64), 64, 0, L.stream>>>(B, kp, kq, ix, c->pickles_tokens.as<mb::KimchiToken>(), c->pickles_literals.as<fe_t>(), in, xe, d_pub, d_ok);
+    if (d_net) {
+        mb::pickles_scalar_net_kernel<<<cdiv(batch, 64), 64, 0, L.stream>>>(B, kp, kq, ix0, s0.pickles_tokens.as<mb::KimchiToken>(), s0.pickles_literals.as<fe_t>(), ix1,
+                                                                             s1.pickles_tokens.as<mb::KimchiToken>(), s1.pickles_literals.as<fe_t>(), d_net, in, xe, d_pub, d_ok);
+        ++c->chain_fermat_launches;
+    }
+    else if (c->gcd_launch()) mb::pickles_scalar_gcd_kernel<<<cdiv(batch, 64), 64, 0, L.stream>>>(B, kp, kq, ix, c->pickles_tokens.as<mb::KimchiToken>(), c->pickles_literals.as<fe_t>(), in, xe, d_pub, d_ok);
     else mb::pickles_scalar_kernel<<<cdiv(batch, 64), 64, 0, L.stream>>>(B, kp, kq, ix, c->pickles_tokens.as<mb::KimchiToken>(), c->pickles_literals.as<fe_t>(), in, xe, d_pub, d_ok);
     HIPC(hipGetLastError());
     return MINA_OK;
@@ -542,7 +588,21 @@ int mb_pickles_check(mina_ctx *c, const mina_pickles_statements *s) {
     if (!c->have_kimchi) return fail(MINA_ERR_STATE, "no wrap verifier index installed");
     return MINA_OK;
 }
-int mb_pickles_statements_dev(mina_ctx *c, size_t batch, const mina_pickles_statements *s, uint32_t *d_pub, uint32_t *d_ok) { return mb_pickles_dev(c, batch, pickles_in_of(*s), d_pub, d_ok); }
+int mb_pickles_statements_dev(mina_ctx *c, size_t batch, const mina_pickles_statements *s, uint32_t *d_pub, uint32_t *d_ok) { return mb_pickles_dev(c, batch, pickles_in_of(*s), d_pub, d_ok, nullptr); }
+int mb_pickles_statements_net_dev(mina_ctx *c, size_t batch, const mina_pickles_statements *s, uint32_t *d_pub, uint32_t *d_ok, const uint8_t *d_net) {
+    if (!d_net) return fail(MINA_ERR_ARG, "null argument");
+    return mb_pickles_dev(c, batch, pickles_in_of(*s), d_pub, d_ok, d_net);
+}
+// What a mixed (`_net`) launch relies on, checked on the host before anything is queued: both index sets of the context fully installed (wrap index, step index and
+// its host half) and the same wrap domain in both.  MINA_ERR_STATE otherwise.
+int mb_mixed_sets_check(mina_ctx *c) {
+    for (uint32_t k = 0; k < 2; ++k) {
+        const IndexSet &s = c->set_at(k);
+        if (!s.have_kimchi || !s.have_pickles_dev || !s.step_host || !((const StepIndexHost *)s.step_host)->installed) return fail(MINA_ERR_STATE, "a mixed job needs both index sets fully installed");
+    }
+    if (c->set_at(0).kimchi_log2 != c->set_at(1).kimchi_log2) return fail(MINA_ERR_STATE, "a mixed job needs the same wrap domain in both index sets");
+    return MINA_OK;
+}
 // where the statements kernel of the current lane left kimchi's digest of the wrap-side old challenges: first element and stride (fe_t units)
 void mb_pickles_kimchi_digest(mina_ctx *c, const mina_pickles_statements *s, const void **first, uint32_t *stride) {
     *first = c->L->pk_xe.as<fe_t>() + mb::px_kdig(s->n_old); *stride = mb::px_stride(s->n_old);
@@ -557,11 +617,13 @@ size_t mb_pickles_sections(const mina_pickles_statements *s, const void ***slots
     return 12;
 }
 
-extern "C" int mina_pickles_public_inputs_batch(mina_ctx *c, const mina_pickles_statements *s, size_t batch, uint8_t *pub_out, uint8_t *ok_out) {
-    if (!c || !pub_out || !ok_out) return fail(MINA_ERR_ARG, "null argument");
+// mixed: proof b against index set net[b] of the context (mina_pickles_public_inputs_batch_net)
+static int pickles_public_inputs_host(mina_ctx *c, const mina_pickles_statements *s, size_t batch, const uint8_t *net, bool mixed, uint8_t *pub_out, uint8_t *ok_out) {
+    if (!c || !pub_out || !ok_out || (mixed && !net)) return fail(MINA_ERR_ARG, "null argument");
     int rc = mb_pickles_check(c, s);
     if (rc) return rc;
     if (batch == 0 || batch > 65536) return fail(MINA_ERR_ARG, "bad batch");
+    if (mixed && (rc = mb_mixed_sets_check(c))) return rc;
     HIPC(hipSetDevice(c->device));
     c->use_lane0();
     Lane &L = *c->L;
@@ -569,19 +631,27 @@ extern "C" int mina_pickles_public_inputs_batch(mina_ctx *c, const mina_pickles_
     mb_pickles_sections(s, slots, strides, &d);
     size_t total = 0, offs[12];
     for (int i = 0; i < 12; ++i) { offs[i] = total; total += (batch * strides[i] + 255) & ~(size_t)255; }
+    const size_t o_net = total; if (mixed) total += (batch + 255) & ~(size_t)255;
     if ((rc = L.host_stage.ensure(total + 16))) return rc;
     for (int i = 0; i < 12; ++i) if (strides[i]) memcpy((uint8_t *)L.host_stage.p + offs[i], *slots[i], batch * strides[i]);
+    if (mixed) memcpy((uint8_t *)L.host_stage.p + o_net, net, batch);
     if ((rc = L.st_in.ensure(total + 16))) return rc;
     HIPC(hipMemcpyAsync(L.st_in.p, L.host_stage.p, total, hipMemcpyHostToDevice, L.stream));
     for (int i = 0; i < 12; ++i) *slots[i] = L.st_in.as<uint8_t>() + offs[i];
     if ((rc = L.pk_pub.ensure(batch * mb::PK_PUB * 32)) || (rc = L.pk_ok.ensure(batch * 4))) return rc;
-    if ((rc = mb_pickles_dev(c, batch, pickles_in_of(d), L.pk_pub.as<uint32_t>(), L.pk_ok.as<uint32_t>()))) return rc;
+    if ((rc = mb_pickles_dev(c, batch, pickles_in_of(d), L.pk_pub.as<uint32_t>(), L.pk_ok.as<uint32_t>(), mixed ? L.st_in.as<uint8_t>() + o_net : nullptr))) return rc;
     std::vector<uint32_t> okw(batch);
     HIPC(hipMemcpyAsync(pub_out, L.pk_pub.p, batch * mb::PK_PUB * 32, hipMemcpyDeviceToHost, L.stream));
     HIPC(hipMemcpyAsync(okw.data(), L.pk_ok.p, batch * 4, hipMemcpyDeviceToHost, L.stream));
     HIPC(hipStreamSynchronize(L.stream));
     for (size_t i = 0; i < batch; ++i) ok_out[i] = okw[i] ? 1 : 0;
     return MINA_OK;
+}
+extern "C" int mina_pickles_public_inputs_batch(mina_ctx *c, const mina_pickles_statements *s, size_t batch, uint8_t *pub_out, uint8_t *ok_out) {
+    return pickles_public_inputs_host(c, s, batch, nullptr, false, pub_out, ok_out);
+}
+extern "C" int mina_pickles_public_inputs_batch_net(mina_ctx *c, const mina_pickles_statements *s, size_t batch, const uint8_t *net, uint8_t *pub_out, uint8_t *ok_out) {
+    return pickles_public_inputs_host(c, s, batch, net, true, pub_out, ok_out);
 }
 
 static int upload_step_index(mina_ctx *c, const StepIndexHost &st) {

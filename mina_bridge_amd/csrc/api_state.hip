@@ -551,6 +551,7 @@ struct Section { const void **slot; size_t bytes; };
 // malformed: word [1] of the failed job's flags (a malformed opening input: the rows it left cannot be re-checked).
 struct CulpritSearch {
     mina_ctx *const c; Lane &L; const mina_state_jobs &d; const bool rows_ok;
+    const uint8_t *d_net = nullptr;                    // a mixed job's bytes (StateJobPlan::d_net): a slice that re-queues the wrap-proof leg takes its own
     const size_t B = d.batch, k = d.k, m = d.n_comms, np = d.n_evalpoints;
     mina_kimchi_proofs kslice{}; mina_pickles_statements sslice{};
     // The opening leg of well-formed proofs does not repeat its transcripts: the prepared rows of the failed batch are still on their
@@ -617,7 +618,9 @@ struct CulpritSearch {
                     if (ipa_leg && rows_ok) { if ((r = mb_ipa_recheck_rows(c, lo, cnt, flags_at[q]))) return r; continue; }
                     mina_state_jobs sj = slice(d, lo, cnt);
                     if (ipa_leg) sj.with_accumulator = 0; else { sj.with_ipa = 0; sj.npub = 0; sj.kimchi = nullptr; }
-                    if ((r = mb_state_jobs_on_lane(c, &sj, v, flags_at[q]))) return r;
+                    StateJobPlan sp; sp.count_mixed = false;
+                    if (d_net && ipa_leg) sp.d_net = d_net + lo;
+                    if ((r = mb_state_jobs_on_lane(c, &sj, v, flags_at[q], sp))) return r;
                 }
                 for (size_t q = 0; q < w; ++q) {
                     uint32_t f[4];
@@ -689,14 +692,15 @@ struct CulpritSearch {
 // one verdict byte per proof on the host.  When a folded check fails: a run without the folded legs for the per-proof chain verdicts, then the search for the
 // culprits of each failed leg -- in groups on lane L alone (mina_ctx_set_search_groups) or over the fan's lanes.  Waits for lane L.  flags: the four words of the
 // whole job's folded checks ([0] opening verdict, [1] malformed opening input, [2] accumulator verdict), or null.
-static int state_job_each(mina_ctx *c, Lane &L, const mina_state_jobs &d, uint8_t *verdicts, uint32_t *flags) {
+// d_net (StateJobPlan): a mixed job.
+static int state_job_each(mina_ctx *c, Lane &L, const mina_state_jobs &d, uint8_t *verdicts, uint32_t *flags, const uint8_t *d_net = nullptr, bool count_mixed = true) {
     c->L = &L;
     const size_t B = d.batch;
     int rc;
     if ((rc = L.st_verdicts.ensure(2 * B * 4 + 16))) return rc;
     uint32_t *dv = L.st_verdicts.as<uint32_t>(), *df = dv + B, *ds = df + 4;
     // small, latency-bound batches: the three independent legs go to three lanes (lane 0 plus two helpers), joined by events
-    StateJobPlan plan; plan.d_stmt_out = ds;
+    StateJobPlan plan; plan.d_stmt_out = ds; plan.d_net = d_net; plan.count_mixed = count_mixed;
     if (B <= 1024 && c->nlanes == 1 && &L == &c->lanes[0]) { plan.wrap = &c->lanes[1]; plan.acc = &c->lanes[2]; }
     if ((rc = mb_state_jobs_on_lane(c, &d, dv, df, plan))) return rc;
     std::vector<uint32_t> hv(2 * B + 4);
@@ -716,6 +720,7 @@ static int state_job_each(mina_ctx *c, Lane &L, const mina_state_jobs &d, uint8_
         }
     }
     CulpritSearch cs(c, L, d, hv[B + 1] != 0);
+    cs.d_net = d_net;
     if ((rc = cs.run(ipa_ok, acc_ok, ipa_each, acc_each))) return rc;
     for (size_t b = 0; b < B; ++b) verdicts[b] = (chain_each[b] && ipa_each[b] && acc_each[b] && stmt_each[b]) ? 1 : 0;
     return MINA_OK;
@@ -903,10 +908,25 @@ int mb_state_job_each_host(mina_ctx *c, const mina_state_jobs *jobs, uint8_t *ve
     return state_job_each(c, *c->L, *jobs, verdicts, nullptr);
 }
 
-extern "C" int mina_state_job_each_dev(mina_ctx *c, const mina_state_jobs *jobs, void *d_verdicts, void *d_flags) {
+// the same for a mixed job (ctx.h StateJobPlan::d_net): what the boundary's fallback runs over a failed mixed chunk (mina_ctx::state_job_each_net).  The chunk's own
+// job counted it and its proofs (mina_ctx_mixed_job_stats): this pass counts nothing.
+int mb_state_job_each_net_host(mina_ctx *c, const mina_state_jobs *jobs, const uint8_t *d_net, uint8_t *verdicts) {
     int rc = mb_check_jobs(c, jobs);
     if (rc) return rc;
-    if (!d_verdicts) return fail(MINA_ERR_ARG, "null argument");
+    if (!verdicts || !d_net) return fail(MINA_ERR_ARG, "null argument");
+    if ((rc = mb_mixed_sets_check(c))) return rc;
+    HIPC(hipSetDevice(c->device));
+    c->use_lane0();
+    if ((rc = mina_state_jobs_prepare(c, jobs->log2_domain, jobs->npub))) return rc;
+    c->use_lane0();
+    return state_job_each(c, *c->L, *jobs, verdicts, nullptr, d_net, false);
+}
+
+static int state_job_each_dev(mina_ctx *c, const mina_state_jobs *jobs, const void *d_net, bool mixed, void *d_verdicts, void *d_flags) {
+    int rc = mb_check_jobs(c, jobs);
+    if (rc) return rc;
+    if (!d_verdicts || (mixed && !d_net)) return fail(MINA_ERR_ARG, "null argument");
+    if (mixed && (rc = mb_mixed_sets_check(c))) return rc;
     if (((uintptr_t)d_verdicts | (uintptr_t)d_flags) & 3u) return fail(MINA_ERR_ARG, "verdicts and flags are 32-bit words: 4-byte alignment");
     if (!c->have_state_salts && jobs->with_states) return fail(MINA_ERR_STATE, "call mina_state_jobs_prepare first");
     HIPC(hipSetDevice(c->device));
@@ -915,13 +935,17 @@ extern "C" int mina_state_job_each_dev(mina_ctx *c, const mina_state_jobs *jobs,
     const size_t B = jobs->batch;
     std::vector<uint8_t> each(B);
     std::vector<uint32_t> words(B + 4);
-    if ((rc = state_job_each(c, L, *jobs, each.data(), &words[B]))) { c->L = &L; return rc; }
+    if ((rc = state_job_each(c, L, *jobs, each.data(), &words[B], mixed ? (const uint8_t *)d_net : nullptr))) { c->L = &L; return rc; }
     c->L = &L;
     for (size_t b = 0; b < B; ++b) words[b] = each[b];
     HIPC(hipMemcpyAsync(d_verdicts, words.data(), B * 4, hipMemcpyHostToDevice, L.stream));
     if (d_flags) HIPC(hipMemcpyAsync(d_flags, &words[B], 16, hipMemcpyHostToDevice, L.stream));
     HIPC(hipStreamSynchronize(L.stream));
     return MINA_OK;
+}
+extern "C" int mina_state_job_each_dev(mina_ctx *c, const mina_state_jobs *jobs, void *d_verdicts, void *d_flags) { return state_job_each_dev(c, jobs, nullptr, false, d_verdicts, d_flags); }
+extern "C" int mina_state_job_each_net_dev(mina_ctx *c, const mina_state_jobs *jobs, const void *d_net, void *d_verdicts, void *d_flags) {
+    return state_job_each_dev(c, jobs, d_net, true, d_verdicts, d_flags);
 }
 
 extern "C" int mina_ctx_set_search_groups(mina_ctx *c, uint32_t groups) {

@@ -322,9 +322,11 @@ namespace {
 // network: the DECLARED network (legacy mode; -1 = none).  net_mode / set / ready: network mode -- the job serves index set `set` (= the network of its proofs), and
 // ready[n] says whether set n holds a full configuration (net_route.h); outside network mode set = 0.
 struct Shape { bool kimchi = false, statements = false, feature_aware = false; uint32_t k = 0, n_prev = 2, n_old = 0, n_ev = 0; int network = -1;
-               bool net_mode = false; int set = 0; bool ready[2] = {false, false}; };
+               bool net_mode = false; int set = 0; bool ready[2] = {false, false};
+               bool mixed = false; };      // MINA_VERIFY_MIXED_NETWORK_JOB: the job serves BOTH networks (net_route.h mixed_pass_allowed): set = 0 is selected, S_NET holds each proof's set
 enum Sec : int { S_REC = 0, S_NF, S_EXP, S_PRE, S_APRE, S_ASG, S_ARHO, S_LR, S_DELTA, S_SG, S_Z1, S_Z2, S_PCM, S_WC, S_ZC, S_TC, S_EV, S_FT1, S_PCH,
-                 S_PLONK, S_BP, S_OLD, S_CM, S_WOLD, S_WSG, S_DG, S_SEV, S_PI, S_SFT, S_APP, S_MISC, S_RB, S_SB, NSEC };
+                 S_PLONK, S_BP, S_OLD, S_CM, S_WOLD, S_WSG, S_DG, S_SEV, S_PI, S_SFT, S_APP, S_MISC, S_RB, S_SB,
+                 S_NET /* a mixed pass alone: one byte per proof, its index set (StateJobPlan::d_net); no bytes otherwise */, NSEC };
 struct Layout {
     size_t stride[NSEC] = {0}, off[NSEC] = {0}, total = 0, cap = 0;
     void build(const Shape &sh, size_t cap_) {
@@ -340,6 +342,7 @@ struct Layout {
                 stride[S_PLONK] = 64; stride[S_BP] = 256; stride[S_OLD] = (size_t)sh.n_old * 256; stride[S_CM] = (size_t)sh.n_old * 64; stride[S_WOLD] = 480; stride[S_WSG] = 64;
                 stride[S_DG] = 32; stride[S_SEV] = (size_t)sh.n_ev * 64; stride[S_PI] = 64; stride[S_SFT] = 32; stride[S_APP] = 32; stride[S_MISC] = 32;
             }
+            if (sh.mixed) stride[S_NET] = 1;
         }
         total = 0;
         for (int i = 0; i < NSEC; ++i) {
@@ -401,7 +404,8 @@ void parse_proof_half(const Shape &sh, const Layout &lay, uint8_t *base, size_t 
         // (network mode: a proof of the OTHER network, when that network's set is ready, has a pass of its own as well -- against that set; net_route.h)
         const size_t n_old = w.step_old_bulletproof_challenges.size(), n_ev = w.prev_evals.size();
         const mb::NetRoute rt = mb::net_route(sh.net_mode ? mb::NET_NETWORK : mb::NET_LEGACY, sh.network, sh.ready, (int)pi.is_state_proof_from_devnet);
-        if (!rt.reject && rt.set != sh.set) { hb.shape = 0; hb.deferred = 1; }
+        if (sh.mixed) *lay.at(base, S_NET, b) = (uint8_t)rt.set;      // a mixed pass serves either ready network: the proof's set travels with it (0 where rejected)
+        if (!sh.mixed && !rt.reject && rt.set != sh.set) { hb.shape = 0; hb.deferred = 1; }
         else if (w.lr.size() != sh.k || w.step_challenge_polynomial_commitments.size() != sh.n_prev || (uses_lookups(w) && !sh.feature_aware) || n_old > 4 || n_ev < 43 || n_ev > 62 ||
             w.prev_public_input.zeta.empty() || w.prev_public_input.zeta_omega.empty() || rt.reject) hb.shape = 0;
         else if (sh.statements && (n_old != sh.n_old || n_ev != sh.n_ev)) { hb.shape = 0; hb.deferred = 1; }
@@ -580,6 +584,10 @@ struct NetConfigs {
     void read(Device &D, uint32_t flags) { for (int n = 0; n < 2; ++n) { cf[n] = read_config(D, flags, -1, n); ready[n] = cf[n].kimchi; } }
     Shape serve(int n) const { Shape sh = shape_of_config(cf[n]); sh.net_mode = true; sh.ready[0] = ready[0]; sh.ready[1] = ready[1]; return sh; }
     // the set a proof's job runs against: its network's when ready; a proof of a network that is not ready fails the kimchi step in a job of a ready one
+    bool mixed_allowed(uint32_t flags) const {       // net_route.h mixed_pass_allowed over the two configurations
+        const unsigned k[2] = {cf[0].k, cf[1].k}; const bool fa[2] = {cf[0].feature_aware, cf[1].feature_aware};
+        return mb::mixed_pass_allowed(mb::NET_NETWORK, ready, k, fa, (flags & MINA_VERIFY_MIXED_NETWORK_JOB) != 0);
+    }
     int set_for(int flag) const { const mb::NetRoute rt = mb::net_route(mb::NET_NETWORK, -1, ready, flag); return !rt.reject ? rt.set : (ready[0] ? 0 : (ready[1] ? 1 : (flag ? 1 : 0))); }
 };
 // the network flag of a serialized public input; -1 where it does not parse
@@ -843,7 +851,9 @@ struct ShapePass {
         c->select_index_set((uint32_t)sh.set);                        // network mode: the pass's set, per job (the caller holds D.mu); otherwise set 0, which is selected already
         JobStructs js; make_jobs(sh, lay, ch.slot->dev.as<uint8_t>(), ch.n, true, true, true, js);
         uint32_t *dv = verdict_words(ch), *df = dv + ch.n, *ds = df + 4;
-        const int rc = mb_state_jobs_on_lane(c, &js.j, dv, df, chunk_plan(ch, phase, ds));
+        StateJobPlan plan = chunk_plan(ch, phase, ds);
+        if (sh.mixed) plan.d_net = lay.at(ch.slot->dev.as<uint8_t>(), S_NET, 0);      // a mixed pass: the set per proof, from the chunk's staging (uploaded with the wrap-proof halves)
+        const int rc = mb_state_jobs_on_lane(c, &js.j, dv, df, plan);
         c->use_lane0();
         return rc;
     }
@@ -968,7 +978,9 @@ struct ShapePass {
         // chunk's job -- through its pointer to the shared body of mina_state_job_batch / mina_state_job_each_dev, and searches in groups of 64: no second upload,
         // and nothing of what the GPU packed comes back to the host.  A context without the pointer keeps the host-buffer path.
         mina_ctx *const X = tu.search_ctx ? D.sc : c;
-        const bool from_dev = (flags & MINA_VERIFY_GROUPED_SEARCH) && X->state_job_each;
+        // A mixed chunk is always searched from its device staging, through the `_net` form of that body (the host-buffer job has no mixed form).
+        const bool from_dev = sh.mixed || ((flags & MINA_VERIFY_GROUPED_SEARCH) && X->state_job_each);
+        if (sh.mixed && !X->state_job_each_net) return fail(MINA_ERR_STATE, "this context cannot search a mixed chunk");
         if (pack && !from_dev) {                  // ... whose records, field counts and `precheck` were made on the GPU (the chunk's job is complete: harvest waited for it)
             uint8_t *hb_ = (uint8_t *)ch.slot->host.p; const uint8_t *db_ = ch.slot->dev.as<uint8_t>();
             HIPC(hipSetDevice(c->device));
@@ -982,8 +994,8 @@ struct ShapePass {
             X->select_index_set((uint32_t)sh.set);                    // the failed pass's set, on the view (its own selection) or on `c` (under D.mu)
             if (!from_dev) return mina_state_job_batch(X, &js.j, v.data());
             const uint32_t keep = X->search_groups;
-            X->search_groups = 64u;
-            const int r = X->state_job_each(X, &js.j, v.data());
+            if (flags & MINA_VERIFY_GROUPED_SEARCH) X->search_groups = 64u;
+            const int r = sh.mixed ? X->state_job_each_net(X, &js.j, lay.at((const uint8_t *)ch.slot->dev.as<uint8_t>(), S_NET, 0), v.data()) : X->state_job_each(X, &js.j, v.data());
             X->search_groups = keep;
             return r;
         };
@@ -1067,7 +1079,12 @@ struct ShapePass {
             for (size_t i = 0; i < m; ++i) if (net[i] >= 0) ++votes[net[i]];
             const int serve = (votes[0] || votes[1]) ? (votes[1] > votes[0] ? 1 : 0) : nc.set_for(0);
             cf = nc.cf[serve]; sh = nc.serve(serve);
-            for (size_t i = 0; i < m; ++i) if (net[i] == serve) mine.push_back(idx[i]);
+            // MINA_VERIFY_MIXED_NETWORK_JOB: ONE pass for both networks where the rule allows it (net_route.h), the pass holds proofs of both, the pairs are full ones
+            // (a statement stage per set) and the context can queue and search a mixed job; set 0 is selected, each proof's set travels in S_NET
+            if (votes[0] && votes[1] && nc.mixed_allowed(flags) && nc.cf[0].statements && nc.cf[1].statements && c->kimchi_to_batch_net && c->pickles_statements_net && c->state_job_each_net) {
+                cf = nc.cf[0]; sh = nc.serve(0); sh.mixed = true;
+            }
+            for (size_t i = 0; i < m; ++i) if (sh.mixed ? net[i] >= 0 : net[i] == serve) mine.push_back(idx[i]);
         } else { cf = read_config(D, flags, network); sh = shape_of_config(cf); }
         if (!cf.usable) return MINA_OK;
         if (!cf.kimchi && !(flags & MINA_VERIFY_ALLOW_MISSING_KIMCHI)) return MINA_OK;          // the kimchi step cannot run: nothing can pass
@@ -1114,6 +1131,18 @@ struct ShapePass {
     }
 };
 int run_device_shape(Device &D, const CallIn &in, const std::vector<size_t> &idx, uint8_t *verdicts, const CallEnv &env, std::vector<size_t> &deferred) {
+    if (env.net_mode && (env.flags & MINA_VERIFY_MIXED_NETWORK_JOB)) {
+        // A pass that may serve both networks takes its proofs ordered by network (a stable partition: mainnet, devnet, then the ones whose flag does not parse), so
+        // that at most one wave per launch holds both and the scalar stages' token programs diverge in that wave only.  Verdicts scatter through idx as ever.
+        NetConfigs nc; nc.read(D, env.flags);
+        if (nc.mixed_allowed(env.flags)) {
+            std::vector<int> key(idx.size());
+            mb_parallel_for(idx.size(), [&](size_t i) { const int f = pub_network(in.pubs[idx[i]], in.pub_lens[idx[i]]); key[i] = f < 0 ? 2 : f; });
+            std::vector<size_t> ordered; ordered.reserve(idx.size());
+            for (int k = 0; k < 3; ++k) for (size_t i = 0; i < idx.size(); ++i) if (key[i] == k) ordered.push_back(idx[i]);
+            return ShapePass(D, in, ordered, verdicts, env, deferred).run();
+        }
+    }
     return ShapePass(D, in, idx, verdicts, env, deferred).run();
 }
 

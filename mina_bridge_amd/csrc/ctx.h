@@ -22,6 +22,7 @@
 using namespace mb;
 
 struct mina_ctx;
+namespace mb { struct KimchiIn; struct KimchiOut; }   // api_kimchi.hip (state_job.hip restates them)
 // A VIEW of a context (round 5): its own lanes, streams and workspaces, while everything INSTALLED -- field constants, both SRS with their window tables, Poseidon
 // tables, salts, verifier / step index -- is borrowed from the parent (no second copy of the tables).  The boundary runs the culprit search of a failed chunk on a
 // view, so that the search needs neither the parent's lock nor a drained device (api_verify.hip Device::sc).  mb_ctx_refresh_view (below mina_ctx) re-reads the
@@ -326,6 +327,20 @@ struct mina_ctx : Installed {
     // mb_state_job_each_host).  Filled by mina_ctx_create; the boundary hands a failed chunk's device staging to it under MINA_VERIFY_GROUPED_SEARCH, and a context
     // without it -- the stand-in contexts of the ThreadSanitizer tier -- keeps the host-buffer path.
     int (*state_job_each)(mina_ctx *c, const mina_state_jobs *dev_jobs, uint8_t *verdicts) = nullptr;
+    // MIXED jobs (StateJobPlan::d_net: proof b against index set d_net[b]; include/mina_verify.h "MIXED jobs").  The two stages of the wrap-proof leg that read index
+    // data, in their `_net` forms (api_pickles.hip mb_pickles_statements_net_dev, api_kimchi.hip mb_kimchi_to_batch_net_dev).  Filled by mina_ctx_create; state_job.hip
+    // reaches them through the pointers, and a context without them -- the stand-in contexts of the trace and ThreadSanitizer tiers, which link no kernel -- cannot
+    // queue a mixed job (MINA_ERR_STATE).
+    // mixed_jobs, mixed_totals (mina_ctx_mixed_job_stats): jobs queued with d_net, counted as they are queued; their proofs by set, two 64-bit words summed on the
+    // device by the kimchi stage's counting launch (the bytes are in HBM), allocated and zeroed by the first mixed job (mb_ctx_mixed_totals).
+    int (*pickles_statements_net)(mina_ctx *c, size_t batch, const mina_pickles_statements *s, uint32_t *d_pub, uint32_t *d_ok, const uint8_t *d_net) = nullptr;
+    int (*kimchi_to_batch_net)(mina_ctx *c, size_t batch, uint32_t n_prev, uint32_t npub, const mb::KimchiIn &in, const mb::KimchiOut &out, uint32_t *d_bad, const uint8_t *d_net,
+                               const void *pf_digest, uint32_t pf_stride, void *d_count) = nullptr;
+    // state_job_each for a mixed job (api_state.hip mb_state_job_each_net_host): per-proof verdict bytes of a job in HBM with its bytes d_net, on lane 0, waited for.
+    // The boundary's fallback runs it over a failed mixed chunk's device staging; a context without it never gets a mixed pass (api_verify.hip ShapePass::run).
+    int (*state_job_each_net)(mina_ctx *c, const mina_state_jobs *dev_jobs, const uint8_t *d_net, uint8_t *verdicts) = nullptr;
+    int (*mixed_sets_check)(mina_ctx *c) = nullptr;      // mb_mixed_sets_check: the preconditions of a mixed launch, MINA_ERR_STATE where they do not hold
+    uint64_t mixed_jobs = 0; DevBuf mixed_totals;
     // The masks form of the job (api_state.hip mb_state_job_checks_host): `passed` / `ran` words (host) of a job whose inputs are in HBM, on lane 0, waited for.
     // front: the front end's d_masks in HBM (d_front), or host words to upload (front), or neither; deny: host words or null.  Filled by mina_ctx_create; the boundary's
     // mina_verify_state_checks_batch reaches the body through it, and a context without it -- the stand-in contexts of the ThreadSanitizer tier -- answers proof by
@@ -361,6 +376,15 @@ static inline int mb_ctx_state_dedup(mina_ctx *c, bool on) {
         c->dedup_states = 0;
     }
     c->state_dedup = on;
+    return MINA_OK;
+}
+
+// the device words of mina_ctx_mixed_job_stats, allocated and zeroed before the context's first mixed job (that once, it waits for lane 0)
+static inline int mb_ctx_mixed_totals(mina_ctx *c) {
+    if (c->mixed_totals.p) return MINA_OK;
+    int rc = c->mixed_totals.ensure(16);
+    if (rc) return rc;
+    if (hipMemsetAsync(c->mixed_totals.p, 0, 16, c->lanes[0].stream) != hipSuccess || hipStreamSynchronize(c->lanes[0].stream) != hipSuccess) return MINA_ERR_HIP;
     return MINA_OK;
 }
 
@@ -446,6 +470,10 @@ struct StateJobPlan {
     HashLaunch hash;
     const FoldExport *fold_export = nullptr;
     const struct LegStreams *lent = nullptr;                    // device-resident jobs only (state_job.hip dev_fork_lanes): the streams lent to wrap / acc / states for this job
+    // A MIXED job: proof b is checked against index set d_net[b] (batch bytes in HBM, 0 | 1) of the context instead of the selected one -- the wrap-proof leg queues the
+    // `_net` forms of the Pickles statement and kimchi stages and an opening check whose only batch-shared point is h.  Null: today's launches.
+    // count_mixed: false for the passes a culprit search re-queues (mina_ctx_mixed_job_stats counts a job and its proofs once).
+    const uint8_t *d_net = nullptr; bool count_mixed = true;
 };
 // What dev_fork_lanes lends the helper lanes of a device-resident job, which own no stream: plan A's three of the pipeline lane, or plan B's roles (StreamPlan:
 // wrap = W1, acc = W2, states = the lane's carrier, H or H1).  acc_first: the accumulator leg shares the hashes' lane and goes AHEAD of them
@@ -459,6 +487,7 @@ int mb_state_frontend_on_lane(mina_ctx *c, size_t batch, const void *d_blob, siz
 int mb_verify_account_dev_on(mina_ctx *c, size_t n, const uint8_t *const *proofs, const size_t *proof_lens, const uint8_t *const *pubs, const size_t *pub_lens,
                              uint32_t *passed, uint32_t *ran, Lane *lane, std::mutex *enq_mu);   // api_account_dev.hip: the same on the device, from the bytes as they are
 int mb_state_job_each_host(mina_ctx *c, const mina_state_jobs *dev_jobs, uint8_t *verdicts);   // api_state.hip
+int mb_state_job_each_net_host(mina_ctx *c, const mina_state_jobs *dev_jobs, const uint8_t *d_net, uint8_t *verdicts);   // api_state.hip: the same for a mixed job
 int mb_state_job_checks_host(mina_ctx *c, const mina_state_jobs *dev_jobs, const uint32_t *d_front, const uint32_t *front, const uint32_t *deny, uint32_t *passed, uint32_t *ran);   // api_state.hip
 int mb_state_hashes_early(mina_ctx *c, Lane *LS, size_t ns_total, size_t lo, size_t cnt, const uint32_t *d_records, const uint32_t *d_nfields, hipEvent_t after, HashLaunch hash);   // state_job.hip
 // The device layer under state_job.hip, defined where the kernels are (api_state.hip): the argument checks of a job, the state hashes of a leg on the current
@@ -474,6 +503,11 @@ void mb_launch_challenge_to_field_fq(hipStream_t stream, uint32_t n, FieldK fk, 
 int mb_pubcomm_dev(mina_ctx *c, size_t batch, uint32_t log2_domain, uint32_t npub, const uint32_t *d_pub, uint32_t *d_out16);      // api_state.hip
 int mb_pickles_statements_dev(mina_ctx *c, size_t batch, const mina_pickles_statements *s, uint32_t *d_pub, uint32_t *d_ok);      // api_pickles.hip
 void mb_pickles_kimchi_digest(mina_ctx *c, const mina_pickles_statements *s, const void **first, uint32_t *stride);
+// The MIXED forms (the `_net` twins of the index-reading kernels): proof b against index set d_net[b] (0 | 1, device bytes) of the context, whichever is selected.
+int mb_mixed_sets_check(mina_ctx *c);                                                                                               // api_pickles.hip: both sets fully installed, equal wrap domains; else MINA_ERR_STATE
+int mb_pickles_statements_net_dev(mina_ctx *c, size_t batch, const mina_pickles_statements *s, uint32_t *d_pub, uint32_t *d_ok, const uint8_t *d_net);   // api_pickles.hip
+int mb_kimchi_to_batch_net_dev(mina_ctx *c, size_t batch, uint32_t n_prev, uint32_t npub, const mb::KimchiIn &in, const mb::KimchiOut &out, uint32_t *d_bad, const uint8_t *d_net,
+                               const void *pf_digest, uint32_t pf_stride, void *d_count);                                           // api_kimchi.hip
 
 // ---- host-side worker pool (api_core.hip): persistent threads, created on first use -- min(hardware threads / 2, 64), $MINA_HOST_THREADS
 // overrides.  A job is `n` independent items handed out in index order; `mb_pool_submit` returns at once (the boundary's pipeline parses

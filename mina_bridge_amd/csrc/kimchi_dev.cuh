@@ -35,6 +35,12 @@ template <int FS> __device__ __forceinline__ fe_t chal_endo(const fe_t &sq_plain
     return challenge_to_field<FS>(lo, hi, ks);
 }
 template <int F, int LANES> __device__ __forceinline__ void sponge_init(DevSponge<F, LANES> &s, const PoseidonParams *pp) { s.pp = pp; s.squeezed = 0; s.count = 0; s.s = fe_zero(); }
+// The `_net` twins (a job that holds proofs of both index sets of the context): net[b] = 0 | 1 names the set proof b is checked against.  Any other byte marks the
+// proof malformed (ok = false) and reads set 0: never an out-of-range read.  Resolved once at the top of a twin, which then runs the body it shares with its kernel.
+__device__ __forceinline__ bool net_second(const uint8_t *__restrict__ net, uint32_t b, bool &ok) { const uint32_t n = net[b]; ok = n <= 1u; return n == 1u; }
+// ... for the twins that have no malformed word to write (kimchi_rows_net_kernel, kimchi_ftcomm_net_kernel): the pick alone.  The flag is kimchi_fq_net_kernel's,
+// which every launch sequence of these twins contains (mb_kimchi_to_batch_net_dev) and which fails the proof whatever the copies and the ft row hold.
+__device__ __forceinline__ bool net_second(const uint8_t *__restrict__ net, uint32_t b) { return net[b] == 1u; }
 // interpreter stack + cache of one lane in LDS, word-major: the 64 lanes of a slot hit 64 banks.  KC_SLOTS * 8 * 64 words per block of 64
 static constexpr int KC_SLOTS = KC_STACK + KC_CACHE;
 struct LdsStack {

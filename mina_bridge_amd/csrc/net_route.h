@@ -25,4 +25,12 @@ inline NetRoute net_route(int mode, int declared, const bool ready[2], int flag)
     return f == declared ? NetRoute{0, false} : NetRoute{0, true};
 }
 
+// MINA_VERIFY_MIXED_NETWORK_JOB: may ONE pass (one job per chunk, the index set chosen per proof on the GPU: ctx.h StateJobPlan::d_net) serve the proofs of both
+// networks?  Iff the flag is set, the process is in network mode, both networks are ready, and the two pairs agree on what a job's shape depends on: the wrap
+// domain (k[n] = log2 of network n's) and whether the step program looks at a proof's features.  Otherwise the sequential passes run and nothing differs.
+// tests/test_mixed_route_model.py walks it over its whole domain (tests/fuzz/mixed_route_twin.cpp).
+inline bool mixed_pass_allowed(int mode, const bool ready[2], const unsigned k[2], const bool feature_aware[2], bool flag_set) {
+    return flag_set && mode == NET_NETWORK && ready[0] && ready[1] && k[0] == k[1] && feature_aware[0] == feature_aware[1];
+}
+
 }  // namespace mb

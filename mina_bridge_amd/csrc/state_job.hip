@@ -80,8 +80,10 @@ static int accumulator_leg(mina_ctx *c, const mina_state_jobs *j, Lane &A, const
 // front of the opening check: everything before runs on the lane's stream (W1), the opening check on `check` behind ONE event recorded on W1.
 // mb_ipa_batch_check_dev queues on the current lane's stream: for the length of that call, and no longer, the lane's handle names `check` (OnStream).
 struct OnStream { hipStream_t &handle; const hipStream_t own; OnStream(Lane &l, hipStream_t s) : handle(l.stream), own(l.stream) { handle = s; } ~OnStream() { handle = own; } };
-static int wrap_leg(mina_ctx *c, const mina_state_jobs *j, Lane &L, const FoldExport *fx, StateJobCarry &v, hipStream_t check) {
+// d_net (StateJobPlan::d_net): a mixed job -- the two stages that read index data run in their `_net` forms, through the context's pointers.
+static int wrap_leg(mina_ctx *c, const mina_state_jobs *j, Lane &L, const FoldExport *fx, StateJobCarry &v, hipStream_t check, const uint8_t *d_net, bool count) {
     c->L = &L;
+    if (d_net && j->kimchi && (!c->pickles_statements_net || !c->kimchi_to_batch_net)) return fail(MINA_ERR_STATE, "this context cannot queue a mixed job");
     const size_t B = j->batch;
     int rc;
     auto to_check = [&]() -> int { return check == L.stream ? MINA_OK : leg_order(L, L.stream, check); };
@@ -94,7 +96,8 @@ static int wrap_leg(mina_ctx *c, const mina_state_jobs *j, Lane &L, const FoldEx
     const uint32_t *pub = (const uint32_t *)j->public_inputs, *comm_override = nullptr;
     if (j->kimchi && j->kimchi->statements) {      // the Pickles statement -> the wrap circuit's public inputs, on this lane ahead of everything that reads them
         if ((rc = L.pk_pub.ensure(B * 40 * 32)) || (rc = L.pk_ok.ensure(B * 4))) return rc;
-        if ((rc = mb_pickles_statements_dev(c, B, j->kimchi->statements, L.pk_pub.as<uint32_t>(), L.pk_ok.as<uint32_t>()))) return rc;
+        if ((rc = d_net ? c->pickles_statements_net(c, B, j->kimchi->statements, L.pk_pub.as<uint32_t>(), L.pk_ok.as<uint32_t>(), d_net)
+                        : mb_pickles_statements_dev(c, B, j->kimchi->statements, L.pk_pub.as<uint32_t>(), L.pk_ok.as<uint32_t>()))) return rc;
         pub = L.pk_pub.as<uint32_t>(); v.stmt_ok = L.pk_ok.as<uint32_t>();
     }
     if (j->npub || j->kimchi) {
@@ -134,6 +137,15 @@ static int wrap_leg(mina_ctx *c, const mina_state_jobs *j, Lane &L, const FoldEx
     mb::KimchiIn in{pub, prev_chals, W(kp.prev_comms), W(kp.w_comm), W(kp.z_comm), W(kp.t_comm), W(kp.evals), W(kp.ft_eval1), comm_override};
     mb::KimchiOut out{L.kc_state.as<uint32_t>(), L.kc_pos.as<uint32_t>(), L.kc_cip.as<uint32_t>(), L.kc_pts.as<uint32_t>(), L.kc_v.as<uint32_t>(), L.kc_u.as<uint32_t>(),
                       L.kc_comms.as<uint32_t>(), nullptr};
+    mb::IpaDevIn iin{out.sponge_state, out.sponge_pos, out.cip, W(j->lr), W(j->delta), W(j->sg), W(j->z1), W(j->z2), out.evalpoints, out.evalscale, out.polyscale,
+                     out.comms, nullptr, W(j->rand_base), W(j->sg_rand_base)};
+    if (d_net) {
+        // The index commitments differ between the proofs of a mixed job: the ft row is computed per proof (no expanded slot) and h is the one batch-shared point.
+        if (count && (rc = mb_ctx_mixed_totals(c))) return rc;
+        if ((rc = c->kimchi_to_batch_net(c, B, kp.n_prev, kp.npub, in, out, v.kimchi_bad, d_net, pf_digest, pf_stride, count ? c->mixed_totals.p : nullptr))) return rc;
+        if (mb_tune().ipa_shared_points) { sh.shared_h = 1; sh.nshared = 1; }
+        return opening_check(sh, iin);
+    }
     mb::IpaExpand ex;
     if ((rc = mb_kimchi_to_batch_dev(c, B, kp.n_prev, kp.npub, in, out, v.kimchi_bad, &ex, pf_digest, pf_stride))) return rc;
     sh.expand_slot = kp.n_prev + 1; sh.per += mb::IPA_EXPAND - 1;          // the ft commitment enters the MSM as its 8 terms
@@ -143,8 +155,6 @@ static int wrap_leg(mina_ctx *c, const mina_state_jobs *j, Lane &L, const FoldEx
         for (uint32_t i = kp.n_prev + 24; i < kp.n_prev + 45; ++i) m |= (uint64_t)1 << i;      // 15 coefficients + 6 sigma
         sh.shared_lo = (uint32_t)m; sh.shared_hi = (uint32_t)(m >> 32); sh.shared_h = 1; sh.shared_expand0 = 1; sh.nshared = 29;
     }
-    mb::IpaDevIn iin{out.sponge_state, out.sponge_pos, out.cip, W(j->lr), W(j->delta), W(j->sg), W(j->z1), W(j->z2), out.evalpoints, out.evalscale, out.polyscale,
-                     out.comms, nullptr, W(j->rand_base), W(j->sg_rand_base)};
     iin.expand = ex;
     return opening_check(sh, iin);
 }
@@ -209,6 +219,7 @@ int mb_state_jobs_on_lane(mina_ctx *c, const mina_state_jobs *j, uint32_t *d_ver
         if ((phase & MB_JOB_FINISH) && (rc = fork(LS))) return rc;      // (states == acc: forked a second time, as it is joined a second time below)
     }
     const size_t B = j->batch;
+    if (plan.d_net && plan.count_mixed && (phase & MB_JOB_LEGS)) ++c->mixed_jobs;      // mina_ctx_mixed_job_stats (the proofs are counted on the device: wrap_leg)
     StateJobCarry v;                                            // what the legs leave for the verdict kernel; the first leg that fails ends them (rc)
     rc = r.acc_ahead ? accumulator_leg(c, j, LA, plan.fold_export, v) : MINA_OK;
     if (!rc) rc = LS.st_ok.ensure(B * 4);                       // the chain_ok words, in either phase
@@ -221,7 +232,7 @@ int mb_state_jobs_on_lane(mina_ctx *c, const mina_state_jobs *j, uint32_t *d_ver
         // the opening check's STREAM: first as well, so that W2 has work while W1 runs the first stage of the wrap-proof leg.
         const bool before = &LA == &LI || r.roles;
         if (before && !r.acc_ahead) rc = accumulator_leg(c, j, LA, plan.fold_export, v);
-        if (!rc) rc = wrap_leg(c, j, LI, plan.fold_export, v, r.check());
+        if (!rc) rc = wrap_leg(c, j, LI, plan.fold_export, v, r.check(), plan.d_net, plan.count_mixed);
         if (!rc && !before && !r.acc_ahead) rc = accumulator_leg(c, j, LA, plan.fold_export, v);
     }
     if (!rc && phase == MB_JOB_LEGS) { *plan.carry = v; return MINA_OK; }      // the legs stay forked: MB_JOB_FINISH joins them
@@ -335,6 +346,15 @@ extern "C" int mina_state_job_batch_dev(mina_ctx *c, const mina_state_jobs *jobs
     if (int rc = mb_check_jobs(c, jobs)) return rc;
     if (!d_verdicts) return fail(MINA_ERR_ARG, "null argument");
     return dev_job(c, jobs, d_verdicts, d_flags, StateJobPlan{});
+}
+// the same job with proofs of both index sets of the context (include/mina_verify.h "MIXED jobs"): one plan field more, the same route
+extern "C" int mina_state_job_batch_net_dev(mina_ctx *c, const mina_state_jobs *jobs, const void *d_net, void *d_verdicts, void *d_flags) {
+    if (int rc = mb_check_jobs(c, jobs)) return rc;
+    if (!d_verdicts || !d_net) return fail(MINA_ERR_ARG, "null argument");
+    if (!c->mixed_sets_check) return fail(MINA_ERR_STATE, "this context cannot queue a mixed job");
+    if (int rc = c->mixed_sets_check(c)) return rc;
+    StateJobPlan plan; plan.d_net = (const uint8_t *)d_net;
+    return dev_job(c, jobs, d_verdicts, d_flags, plan);
 }
 
 // SURVEY.md 8e.2 for the WHOLE job (the `north_star` variant: "a single reduce of partial sums over xGMI"): this shard's proofs go through every stage of the

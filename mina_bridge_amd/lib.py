@@ -47,6 +47,7 @@ EXPORTS = [
     "mina_verify_account_files", "mina_verify_account_checks", "mina_verify_account_ctx", "mina_account_hash_batch", "mina_account_abi_encode", "mina_verify_configure", "mina_verify_shutdown", "mina_verify_global_ctx", "mina_poseidon_params_name",
     "mina_verify_device_count", "mina_verify_device_ctx", "mina_verify_set_network", "mina_verify_install_verifier_index", "mina_verify_install_step_index", "mina_verify_set_poseidon_params",
     "mina_verify_install_verifier_index_net", "mina_verify_install_step_index_net", "mina_verify_drop_network_indexes", "mina_verify_networks", "mina_ctx_select_index_set", "mina_ctx_index_set",
+    "mina_kimchi_to_batch_net", "mina_pickles_public_inputs_batch_net", "mina_state_job_batch_net_dev", "mina_state_job_each_net_dev", "mina_ctx_mixed_job_stats",
     "mina_poseidon_install_default_params",
     "verify_mina_state_ffi", "verify_account_inclusion_ffi", "verify_mina_state_ffi_u32", "verify_account_inclusion_ffi_u32",
     "mina_verify_queue_create", "mina_verify_queue_destroy", "mina_verify_queue_submit", "mina_verify_queue_flush", "mina_verify_queue_poll", "mina_verify_queue_wait", "mina_verify_queue_fd", "mina_verify_queue_stats",
@@ -271,6 +272,7 @@ VERIFY_DEDUP_STATES = 8   # the boundary hashes each distinct protocol state of 
 VERIFY_ACCOUNT_ON_DEVICE = 32   # verify_account / _batch / _checks upload a call's bytes as they are and run the whole Proof-of-Account job on the GPU (MinaContext.account_job_dev); verdicts unchanged
 VERIFY_PACK_ON_DEVICE = 16   # the boundary packs and pre-checks the protocol states of a chunk on the GPU (MinaContext.state_frontend_dev) instead of on its host pool; verdicts unchanged
 VERIFY_GROUPED_SEARCH = 64   # a chunk whose folded check failed is searched for its culprits in groups of 64 from its staging in HBM (MinaContext.set_search_groups, state_job_each_dev); verdicts unchanged
+VERIFY_MIXED_NETWORK_JOB = 128   # network mode, both networks ready with equal wrap domains: ONE pass and one job per chunk for the proofs of both (index set chosen per proof on the GPU); verdicts unchanged
 
 
 def _bytes_arg(b):
@@ -1541,6 +1543,10 @@ class MinaContext:
         return out
 
     def kimchi_to_batch(self, kimchi, k: int) -> dict:
+        return self._kimchi_to_batch(kimchi, None, False)
+
+    def _kimchi_to_batch(self, kimchi, net, mixed: bool) -> dict:
+        """mixed: the `_net` form (kimchi_to_batch_net), proof b against index set net[b]"""
         kp, keep = kimchi
         B, nc = kp.batch, kp.n_prev + 45
         o = {"sponge_state": np.zeros((B, 96), np.uint8), "sponge_pos": np.zeros((B, 2), np.uint32), "cip": np.zeros((B, 32), np.uint8),
@@ -1549,6 +1555,12 @@ class MinaContext:
         out = KimchiBatchOut()
         for name in o:
             setattr(out, name, o[name].ctypes.data)
+        if mixed:
+            nb = None if net is None else np.ascontiguousarray(net, np.uint8)
+            if nb is not None and nb.size != B:
+                raise ValueError("net: one byte per proof")
+            self._ck(self._lib.mina_kimchi_to_batch_net(self._h, ctypes.byref(kp), None if nb is None else _p(nb), ctypes.byref(out)), "mina_kimchi_to_batch_net")
+            return o
         self._ck(self._lib.mina_kimchi_to_batch(self._h, ctypes.byref(kp), ctypes.byref(out)), "mina_kimchi_to_batch")
         return o
 
@@ -1599,3 +1611,35 @@ class MinaContext:
     def state_job_batch_dev(self, d_jobs, d_verdicts: int, d_flags: int = 0):
         self._ck(self._lib.mina_state_job_batch_dev(self._h, ctypes.byref(d_jobs), ctypes.c_void_p(d_verdicts), ctypes.c_void_p(d_flags) if d_flags else None),
                  "mina_state_job_batch_dev")
+
+    # ---- MIXED jobs: proofs of both index sets of the context in one call; net[b] = 0 | 1 names proof b's set (include/mina_verify.h "MIXED jobs")
+    def kimchi_to_batch_net(self, kimchi, k: int, net) -> dict:
+        """kimchi_to_batch with proof b checked against index set net[b] (one byte per proof; None reaches the library as NULL)"""
+        return self._kimchi_to_batch(kimchi, net, True)
+
+    def pickles_public_inputs_batch_net(self, statements, batch: int, net):
+        """pickles_public_inputs_batch with proof b checked against the step index of set net[b]"""
+        st, _keep = statements
+        nb = None if net is None else np.ascontiguousarray(net, np.uint8)
+        if nb is not None and nb.size != batch:
+            raise ValueError("net: one byte per proof")
+        pub = np.zeros((batch, 40, 32), np.uint8); ok = np.zeros(batch, np.uint8)
+        self._ck(self._lib.mina_pickles_public_inputs_batch_net(self._h, ctypes.byref(st), ctypes.c_size_t(batch), None if nb is None else _p(nb), _p(pub), _p(ok)),
+                 "mina_pickles_public_inputs_batch_net")
+        return pub, ok
+
+    def state_job_batch_net_dev(self, d_jobs, d_net: int, d_verdicts: int, d_flags: int = 0):
+        """state_job_batch_dev over proofs of both index sets; d_net: batch bytes in HBM"""
+        self._ck(self._lib.mina_state_job_batch_net_dev(self._h, ctypes.byref(d_jobs), ctypes.c_void_p(d_net or None), ctypes.c_void_p(d_verdicts), ctypes.c_void_p(d_flags or None)),
+                 "mina_state_job_batch_net_dev")
+
+    def state_job_each_net_dev(self, d_jobs, d_net: int, d_verdicts: int, d_flags: int = 0):
+        """state_job_each_dev over proofs of both index sets; d_net: batch bytes in HBM; waits for its lane"""
+        self._ck(self._lib.mina_state_job_each_net_dev(self._h, ctypes.byref(d_jobs), ctypes.c_void_p(d_net or None), ctypes.c_void_p(d_verdicts), ctypes.c_void_p(d_flags or None)),
+                 "mina_state_job_each_net_dev")
+
+    def mixed_job_stats(self) -> dict:
+        """mixed jobs this context has queued and their proofs by the index set their byte names (counted on the GPU: waits for what is queued)"""
+        a, b, d = ctypes.c_uint64(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+        self._ck(self._lib.mina_ctx_mixed_job_stats(self._h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(d)), "mina_ctx_mixed_job_stats")
+        return {"jobs": a.value, "proofs_set0": b.value, "proofs_set1": d.value}
